@@ -6,14 +6,21 @@ E = 6,558,720 edges, 120 levels), H=64, 4+4 structural rounds, LayerNorm, loss w
   python bench.py --gpus N --steps K --warmup W        (N > 1: starts its N ranks itself, one per GPU, over RCCL)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (what the driver does)
 
-Prints ONE JSON line on stdout (rank 0): whole-job graphs/s with inputs resident in HBM, plus
+Prints ONE JSON line on stdout (rank 0): whole-job graphs/s with inputs resident in HBM (`value`) and `ms_per_step`, the time
+of one of the K timed steps.  A plain run does only that: set-up, W warm-up steps, K timed steps, the line.
+  --dump-outputs DIR   after the timed steps, what the last timed step produced (its losses and confusion counts, every parameter
+                       after its Adam update, every parameter's gradient, the BatchNorm running statistics) as DIR/<name>.npy
+                       (float32 / float64); inputs are seeded, so two builds run with the same arguments can be compared
+  --full               also everything beyond the headline figure, after the timed steps:
+  `plan_ms`      batch construction (CSR, level tiles, colours; outside the timed region) cold and `plan_ms_steady` on a second batch;
+  `fresh_batches` a second timed loop over batches collated, copied and planned per step (--no-fresh skips it);
   `roofline`     dominant kernel (struct-stage backward): SURVEY.md §8(d) algorithmic bytes per launch / its HIP-event time,
                  both byte models (`frac_8d`, `frac_gather_model`), fabric bytes and MFMA-busy share from the committed PMC passes;
+                 the per-launcher HIP-event breakdown is taken in a separate short pass (profiling off while timing);
   `cpu_baseline` the oracle (vectorised PyTorch-CPU port, pinned to the reference's golden vectors) timed on the host cores on a
                  bounded sample of the same workload, plus the literal restatement (per-node subgraph scans, dense N x N mask)
-                 at config 1, which ties back to the survey's timing of the real reference.
-Batch construction (CSR, level tiles) is outside the timed region and reported as `plan_ms` (cold) / `plan_ms_steady`.
-The per-launcher HIP-event breakdown is taken in a separate short pass AFTER the timed loop (profiling off while timing).
+                 at config 1, which ties back to the survey's timing of the real reference (--no-cpu-baseline skips it);
+  `other_configs` configs 3 and 5, a short run each in a child process (1 GPU, config 2; --no-other-configs skips it).
 """
 import argparse
 import json
@@ -42,13 +49,22 @@ def parse_args():
     ap.add_argument('--batch', type=int, default=None, help='graphs per GPU (default: the config\'s)')
     ap.add_argument('--neg', choices=['sampled', 'fixed'], default='sampled',
                     help='negative edges drawn on the device every step (as the reference does) or fixed')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-fresh', action='store_true', help='skip the second timed loop over fresh batches (collate + H2D + plan per step)')
-    ap.add_argument('--loader-workers', type=int, default=8)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what is beyond the headline figure: plan build, fresh batches, HIP-event roofline, all-reduce, '
+                         'CPU baseline and loss parity, configs 3 / 5')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step produced (losses, parameters, gradients, BatchNorm statistics) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-fresh', action='store_true',
+                    help='with --full: skip the second timed loop over fresh batches (collate + H2D + plan per step)')
+    ap.add_argument('--loader-workers', type=int, default=8, help='with --full: loader threads of the fresh-batch loop')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the short config 3 / config 5 runs (child processes, after the timed loops) a default 1-GPU run appends as "other_configs"')
+                    help='with --full: skip the short config 3 / config 5 runs (child processes, after the timed loops) a 1-GPU run appends as "other_configs"')
     ap.add_argument('--master-port', type=int, default=29541)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def self_launch(a):
@@ -211,8 +227,8 @@ def other_configs(dev):
     torch.cuda.empty_cache()
     res = {}
     for k in (3, 5):
-        cmd = [sys.executable, os.path.abspath(__file__), '--config', str(k), '--steps', '6', '--warmup', '2', '--no-cpu-baseline', '--no-fresh',
-               '--no-other-configs']
+        cmd = [sys.executable, os.path.abspath(__file__), '--config', str(k), '--steps', '6', '--warmup', '2', '--full', '--no-cpu-baseline',
+               '--no-fresh', '--no-other-configs']
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
             d = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -222,6 +238,25 @@ def other_configs(dev):
         except Exception as exc:         # noqa: BLE001 (reported in the line)
             res['cfg%d' % k] = {'error': '%s: %s' % (type(exc).__name__, str(exc)[:200])}
     return res
+
+
+def dump_outputs(out_dir, model, vals):
+    """What the last timed step produced, as out_dir/<name>.npy: `losses` (recon, prob, func) and `confusion` (TP, FP, TN, FN) in
+    float64 (the step's metrics copy), and in float32 `param.<name>` (every parameter after the step's Adam update), `grad.<name>`
+    (the step's gradient of it) and `buffer.<name>` (BatchNorm running statistics).  About 2 MB at H=64."""
+    import numpy as np
+    out = {'losses': np.asarray(vals[:3], dtype=np.float64), 'confusion': np.asarray(vals[3:], dtype=np.float64)}
+    for k, p in model.named_parameters():
+        out['param.' + k] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            out['grad.' + k] = p.grad.detach().float().cpu().numpy()
+    for k, b in model.named_buffers():
+        if b.is_floating_point():
+            out['buffer.' + k] = b.detach().float().cpu().numpy()
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
 
 
 def main():
@@ -288,14 +323,16 @@ def main():
     build_plan(batch)
     torch.cuda.synchronize()
     plan_ms = (time.time() - t0) * 1e3
-    # steady state: the same construction on a second, equally shaped batch (allocator and kernels warm)
-    b2 = deepgate.CircuitBatch.from_arrays(arrays, device=dev)
-    torch.cuda.synchronize()
-    t0 = time.time()
-    build_plan(b2)
-    torch.cuda.synchronize()
-    plan_ms_steady = (time.time() - t0) * 1e3
-    del b2
+    plan_ms_steady = None
+    if a.full:
+        # steady state: the same construction on a second, equally shaped batch (allocator and kernels warm)
+        b2 = deepgate.CircuitBatch.from_arrays(arrays, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        build_plan(b2)
+        torch.cuda.synchronize()
+        plan_ms_steady = (time.time() - t0) * 1e3
+        del b2
 
     def sync_all():
         torch.cuda.synchronize()
@@ -323,13 +360,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     losses = vals[:3]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, vals)        # before anything below steps the model again
 
     # ---- second timed loop: FRESH batches.  Every step's batch is collated again from the per-graph arrays (in a rotated order: a
     #      different batch tensor every step), copied over PCIe and planned afresh — nothing of it is cached on the device.  Collate,
     #      copy and plan build run on the prefetcher's worker threads / streams beside the previous step (deepgate/prefetch.py: what
     #      Trainer.train uses); the reference's loop does the same work with DataLoader workers + `batch.to(device)` (trainer.py:189-195,223).
     fresh = None
-    if not a.no_fresh:
+    if a.full and not a.no_fresh:
         from deepgate.prefetch import BatchPrefetcher, _Staging, collate_into
         skip = ('neg_edge_index',) if a.neg == 'sampled' else ()
         # a SUSTAINED rate: enough untimed steps to drain what the prefetcher queued while nothing consumed, enough timed ones to average
@@ -368,29 +407,26 @@ def main():
                          'threads with their own HIP streams, overlapped with the previous step; PCIe-inclusive' % a.loader_workers}
 
     # ---- separate short pass: per-launcher HIP events (and the all-reduce alone), profiling was OFF in the timed loop
-    _hip.profile(True)
-    for _ in range(2):
-        step()
-    table = _hip.profile(False)
-    allreduce_ms = None
-    if world > 1:
-        f = tr.optimizer.flat_buffers()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sync_all()
-        ts = []
-        for _ in range(5):
-            s.record()
-            dist.all_reduce(f['grad'], op=dist.ReduceOp.SUM)
-            e.record()
-            torch.cuda.synchronize()
-            ts.append(s.elapsed_time(e))
-        allreduce_ms = sorted(ts)[2]
+    table, allreduce_ms = None, None
+    if a.full:
+        _hip.profile(True)
+        for _ in range(2):
+            step()
+        table = _hip.profile(False)
+        if world > 1:
+            f = tr.optimizer.flat_buffers()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            sync_all()
+            ts = []
+            for _ in range(5):
+                s.record()
+                dist.all_reduce(f['grad'], op=dist.ReduceOp.SUM)
+                e.record()
+                torch.cuda.synchronize()
+                ts.append(s.elapsed_time(e))
+            allreduce_ms = sorted(ts)[2]
 
     if rank == 0:
-        summ = _hip.profile_summary(table)
-        roof, order = roofline_record(summ, table, N, E, H, elapsed / a.steps)
-        for name, (calls, ms) in order:
-            print('  %-26s %6d calls %10.3f ms total %9.3f ms/call' % (name, calls, ms, ms / max(calls, 1)), file=sys.stderr)
         mode = 'f32 storage; dense products as bf16x3 split-precision MFMA, fp32 accumulate' if ops.PRECISION == 'x3' else 'f32 (fp32-input MFMA)'
         out = {
             'metric': 'circuit-graphs/sec (train step), AIG-64k batch=64 per GPU' if (a.config in (2, 4) and B == 64) else
@@ -404,12 +440,20 @@ def main():
                                    'H=64, 4+4 rounds, layernorm, weights [1,4,4], negatives %s; step includes the 7-scalar metrics copy (pinned, read one step behind)' % (
                                        a.config, ctype, B, cfg['n_nodes'], N, E, cfg['n_levels'], a.neg),
                        'global_batch': world * B, 'parallelism': 'dp%d' % world},
+            'losses': losses,
+        }
+    if rank == 0 and a.full:
+        summ = _hip.profile_summary(table)
+        roof, order = roofline_record(summ, table, N, E, H, elapsed / a.steps)
+        for name, (calls, ms) in order:
+            print('  %-26s %6d calls %10.3f ms total %9.3f ms/call' % (name, calls, ms, ms / max(calls, 1)), file=sys.stderr)
+        out.update({
             'plan_ms': plan_ms, 'plan_ms_steady': plan_ms_steady,
             # a loop that built every batch's plan (CSRs, level tiles, colour refinement) SERIALLY in front of its step; the prefetcher
             # overlaps that with the previous step: value_fresh_batches is the measured loop rate
             'value_with_plan_build': world * B / (elapsed / a.steps + plan_ms_steady * 1e-3),
-            'losses': losses, 'roofline': roof,
-        }
+            'roofline': roof,
+        })
         quot = batch._mgv_plan.quotient(batch._mgv_plan.xcls, 2 * rounds) if ops.QUOTIENT else []
         out['struct_encoder'] = {'half_rounds': 2 * rounds, 'rows_per_half_round': [s['C'] for s in quot] + [N] * (2 * rounds - len(quot)),
                                  'note': 'every node starts from ones (digae_layer.py:260): the first half rounds have few distinct rows (colour '
@@ -438,8 +482,9 @@ def main():
             out['cpu_baseline'] = cpu_baseline(a.config, H, rounds, seed_sd, hip_losses=hip_losses)
         if world == 1 and a.config == 2 and a.batch is None and not a.no_other_configs:
             # BASELINE.json's other single-GPU configurations (parity-test cases, not the metric): a short resident-batch run each, in a
-            # child process after this one's timed loops are over, so that the driver's default run records them too
+            # child process after this one's timed loops are over, so that a --full run records them too
             out['other_configs'] = other_configs(dev)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -9,6 +9,32 @@ for p in (ROOT, PKG_PARENT):
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 
+class GoldenArrays(dict):
+    """Array name -> array, with np.load's `files` list."""
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_golden(name):
+    """tests/golden/<name>.npz, or its parts <name>.0.npz, <name>.1.npz, ... merged (make_golden.py splits a fixture that would not
+    stay under 1 MiB as one file)."""
+    import glob
+
+    import numpy as np
+    path = os.path.join(GOLDEN, name + '.npz')
+    if os.path.exists(path):
+        return np.load(path)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + '.[0-9]*.npz')), key=lambda p: int(p.rsplit('.', 2)[1]))
+    if not parts:
+        raise FileNotFoundError(path)
+    z = GoldenArrays()
+    for p in parts:
+        with np.load(p) as f:
+            z.update((k, f[k]) for k in f.files)
+    return z
+
+
 def pytest_configure(config):
     config.addinivalue_line('markers', 'gpu: needs a real MI355X (run with -m gpu on the GPU box)')
 

@@ -21,6 +21,8 @@ Fixture families:
                   (xmg, [E,2] layout) incl. return_order_info levels (utils/dag_utils.py:10-37,80-88)
   g7_ckpt.npz +   a checkpoint written by the reference's Trainer.save after one Adam step (g1 aig setup),
   g7_ckpt_ref_aig.pth  the losses / parameters of the reference's NEXT step after Trainer.load of that file
+A family whose .npz would exceed 1 MiB (g2_*, g3_ops) is written as parts <name>.0.npz, <name>.1.npz, ... (save_fixture);
+the tests read either form through conftest.load_golden.
 """
 import argparse
 import importlib.util
@@ -451,9 +453,34 @@ def main():
         if a.only and a.only not in name:
             continue
         arrs = fn()
-        path = os.path.join(HERE, name + '.npz')
-        np.savez_compressed(path, **arrs)
-        print('%-10s %4d arrays %8.1f KB' % (name, len(arrs), os.path.getsize(path) / 1024))
+        paths = save_fixture(name, arrs)
+        print('%-10s %4d arrays %8.1f KB in %d file(s)' % (name, len(arrs), sum(os.path.getsize(p) for p in paths) / 1024, len(paths)))
+
+
+PART_BYTES = 900 * 1024     # a committed file stays under 1 MiB
+
+
+def save_fixture(name, arrs):
+    """<name>.npz, or — when the compressed arrays exceed PART_BYTES — consecutive parts <name>.0.npz, <name>.1.npz, ... of whole
+    arrays in their order (tests/conftest.py load_golden merges them).  Returns the paths written."""
+    import glob
+    import zlib
+    parts, cur, size = [], {}, 0
+    for k, v in arrs.items():
+        n = len(zlib.compress(np.asarray(v).tobytes()))
+        if cur and size + n > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    for old in glob.glob(os.path.join(HERE, glob.escape(name) + '.[0-9]*.npz')) + glob.glob(os.path.join(HERE, glob.escape(name) + '.npz')):
+        os.remove(old)
+    paths = [os.path.join(HERE, name + '.npz')] if len(parts) == 1 else [os.path.join(HERE, '%s.%d.npz' % (name, i)) for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) < 1 << 20, path
+    return paths
 
 
 if __name__ == '__main__':

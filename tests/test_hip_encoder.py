@@ -1,13 +1,12 @@
 """GPU parity: structural-encoder kernels (C ABI -> ops -> modules) against the golden vectors and
 the oracle.  Tolerances: fp32 arithmetic with a different (but fixed) summation order than the CPU
 reference -> 2e-4 relative on activations / gradients, stated per assert."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +18,7 @@ def _dev():
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name + '.npz'))
+    return load_golden(name)
 
 
 def close(a, b, rtol=2e-4, atol=2e-5, msg=''):

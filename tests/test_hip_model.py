@@ -2,14 +2,13 @@
 outputs, losses, gradients of every parameter and one Adam step against the golden vectors the
 reference produced, plus per-operator fixtures.  fp32 on both sides, different summation order:
 tolerances stated per assert (2e-4 relative to the tensor's scale unless noted)."""
-import os
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
 TYPES = ['aig', 'mig', 'xag', 'xmg']
@@ -22,7 +21,7 @@ def _dev():
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name + '.npz'))
+    return load_golden(name)
 
 
 def grad_atol():

@@ -1,19 +1,18 @@
 """Pin the oracle (oracle/ref_cpu.py) to the golden vectors the reference itself produced
 (tests/golden/make_golden.py).  CPU only."""
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import load_golden
 from oracle import ref_cpu as R
 
 TYPES = ['aig', 'mig', 'xag', 'xmg']
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name + '.npz'))
+    return load_golden(name)
 
 
 def close(a, b, rtol=1e-5, atol=1e-6):

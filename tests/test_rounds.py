@@ -3,14 +3,13 @@ HIP kernels only (level kernels' hidden-state variants, bf16x3 and exact fp32; c
 tensors.  GPU: two- and three-round models against the pinned oracle (bf16x3, exact-fp32 kernels, a batch with high fan-out
 lists), the stand-alone aggregator against the reference's own fixture (g3_ops: TFMlpAggr + GRU from a NON-zero state, outputs and
 every gradient) and against the oracle's restatement on random multigraphs."""
-import os
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import load_golden
 
 
 def close(a, b, rtol=2e-4, atol=2e-5, msg=''):
@@ -122,7 +121,7 @@ def test_standalone_aggregator_on_hip_matches_the_reference_fixture():
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     from deepgate.arch.tfmlp import TFMlpAggr
-    z = np.load(os.path.join(GOLDEN, 'g3_ops.npz'))
+    z = load_golden('g3_ops')
     H = z['lvl_hprev'].shape[1]
     dev = torch.device('cuda:0')
     aggr = TFMlpAggr(2 * H, H)

@@ -47,7 +47,9 @@ def run(z, bf16_states):
 
 
 def main():
-    z = np.load(os.path.join(ROOT, 'tests', 'golden', 'g2_aig.npz'))
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from conftest import load_golden
+    z = load_golden('g2_aig')
     l32, p32 = run(z, False)
     l16, p16 = run(z, True)
     keys = ('recon_loss', 'prob_loss', 'func_loss')

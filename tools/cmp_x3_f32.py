@@ -1,12 +1,14 @@
 """Diagnostic: bf16x3 vs exact-f32 struct-stage kernels on one fixture graph (max abs differences)."""
 import os, sys
-import numpy as np, torch
+import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'multi-gate-vae_amd'))
 from deepgate import ops
 from deepgate.graph_plan import GraphPlan
 
-z = np.load(os.path.join(ROOT, 'tests', 'golden', sys.argv[1] if len(sys.argv) > 1 else 'g2_xmg.npz'))
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+from conftest import load_golden
+z = load_golden((sys.argv[1] if len(sys.argv) > 1 else 'g2_xmg').replace('.npz', ''))
 dev = torch.device('cuda:0')
 ei = torch.tensor(z['in_edge_index'], device=dev)
 N, H = z['in_x'].shape[0], 64
