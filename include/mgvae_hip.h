@@ -450,6 +450,28 @@ int mgv_readout_head_fwd(int64_t N, int C, const float* A, const float* w, const
 /* given dprob[N]: dA = dy w, dw += sum dy A, db += sum dy with dy = dprob * [clamp inactive] */
 int mgv_readout_head_bwd(int64_t N, int C, const float* A, const float* w, const float* b, int clamp01, const float* dprob,
                          float* dA, float* dw, float* db, double* workspace, int64_t workspace_doubles, void* stream);
+/* ---- fused training-mode readout (arch/mlp.py MLP.forward with dim_in 64, dim_hidden 32, three layers = the pred_prob of
+ * dg_ae_model_aig.py:102-106; bf16x3 products).  Passes: hf -> y1, y1 -> y2, y2 -> prob forward; three backward passes that read
+ * y1, y2, dprob and hf and recompute activations, dropout masks (the hash of mgv_bn_act_fwd) and BN gradients in registers.
+ * wpack: mgv_readout_fused_pack_elems() bf16 = [W1][W2][W2^T][W1^T], each hi/lo planes in fragment order (mgv_wpack_bf16x3).
+ * workspace: >= mgv_readout_fused_ws_doubles(N) doubles (per-workgroup slab rows, added in a fixed order: no float atomics). */
+int mgv_readout_fused_pack_elems(void);
+int mgv_readout_fused_grad_floats(void);
+int mgv_readout_fused_ws_doubles(int64_t N);
+/* Forward: y1 = hf W1^T + b1, y2 = a1 W2^T + b2 with a_k = dropout(relu(bn_k(y_k))) (batch statistics; running buffers rm/rv
+ * updated as nn.BatchNorm1d: running = running * keep + momentum * value, keep = 1 - momentum, unbiased var), prob = clamp(a2 w3 + b3).
+ * Out: y1, y2 [N][32]; stats[128] = mean1, invstd1, mean2, invstd2 (kept for the backward); sums[128] (double) scratch; prob [N]. */
+int mgv_readout_fused_fwd(int64_t N, const float* hf, const void* wpack, const float* b1, const float* g1, const float* be1,
+                          float* rm1, float* rv1, const float* b2, const float* g2, const float* be2, float* rm2, float* rv2,
+                          const float* w3, const float* b3, float p1, float p2, uint64_t seed1, uint64_t seed2, float momentum,
+                          float keep, float eps, int clamp01, float* y1, float* y2, float* stats, double* sums, float* prob,
+                          double* workspace, int64_t workspace_doubles, void* stream);
+/* Backward from dprob [N]: dhf [N][64] and grads (mgv_readout_fused_grad_floats() floats: dW1[32][64], db1, dgamma1, dbeta1,
+ * dW2[32][32], db2, dgamma2, dbeta2, dw3[32], db3; overwritten); sums[128] (double) scratch. */
+int mgv_readout_fused_bwd(int64_t N, const float* hf, const float* y1, const float* y2, const float* stats, const float* dprob,
+                          const void* wpack, const float* g1, const float* be1, const float* g2, const float* be2, const float* w3,
+                          const float* b3, float p1, float p2, uint64_t seed1, uint64_t seed2, int clamp01, float* dhf,
+                          float* grads, double* sums, double* workspace, int64_t workspace_doubles, void* stream);
 /* nn.L1Loss, reduction mean (trainer.py:71,156): sum += sum |x - target|;  dx = *gscale/n * sign(x - target) */
 int mgv_l1_loss_fwd(int64_t n, const float* x, const float* target, double* sum, double* workspace, int64_t workspace_doubles,
                     void* stream);

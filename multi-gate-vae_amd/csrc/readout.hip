@@ -3,24 +3,12 @@
 // and their backward passes.  All streaming over [N, C] (C = dim_mlp = 32), C/4 lanes per row.
 #include "mgv_common.h"
 #include "mgv_slab.h"
+#include "mgv_dropout.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
 
 constexpr int kMaxC = 64;
-
-__device__ __forceinline__ uint32_t hash_u32(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return (uint32_t)x;
-}
-// inverted-dropout factor of element (row, col): 0 or 1/(1-p); the same counter-based stream is
-// regenerated in the backward pass
-__device__ __forceinline__ float drop_scale(uint64_t seed, int64_t elem, float p, float keep_scale) {
-    if (p <= 0.f) return 1.0f;
-    const uint32_t h = hash_u32(seed + 0x9E3779B97F4A7C15ULL * (uint64_t)(elem + 1));
-    const float u = (h >> 8) * (1.0f / 16777216.0f);
-    return u < p ? 0.f : keep_scale;
-}
 
 // sums[c] += sum_i Y[i][c],  sums[C + c] += sum_i Y[i][c]^2   (double)
 __global__ __launch_bounds__(kThreads) void k_colstats(int64_t N, int C, const float* Y, int ld, double* slab) {     // slab [gridDim][2C]

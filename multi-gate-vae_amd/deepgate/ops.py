@@ -1247,6 +1247,57 @@ class HeadFn(torch.autograd.Function):
         return da, dw.reshape(ctx.wshape), db, None
 
 
+class ReadoutMLPFn(torch.autograd.Function):
+    """Training-mode readout 64 -> 32 -> 32 -> 1 (arch/mlp.py MLP.forward, dg_ae_model_aig.py:102-106) in a few streaming passes
+    (csrc/readout_fused_x3.hip): the same arithmetic as linear() + BnReluDropFn + HeadFn (bf16x3 products, double batch statistics,
+    the same dropout masks for the same seeds, the running buffers updated in place), but only y1, y2 [N, 32] are kept between the
+    layers; activations, masks and BatchNorm gradients are recomputed in the backward passes."""
+
+    @staticmethod
+    def forward(ctx, hf, W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, rm1, rv1, rm2, rv2, p1, p2, seed1, seed2, momentum, eps, clamp01):
+        hfd = check(hf.detach().contiguous(), F32, 'hf')
+        N, dev = hfd.shape[0], hfd.device
+        par = [check(t.detach().contiguous(), F32, n) for t, n in ((W1, 'W1'), (b1, 'b1'), (g1, 'g1'), (be1, 'be1'), (W2, 'W2'), (b2, 'b2'),
+                                                                     (g2, 'g2'), (be2, 'be2'), (W3, 'W3'), (b3, 'b3'))]
+        W1d, b1d, g1d, be1d, W2d, b2d, g2d, be2d, W3d, b3d = par
+        assert W1d.shape == (32, 64) and W2d.shape == (32, 32) and W3d.shape == (1, 32)
+        for t in (rm1, rv1, rm2, rv2):
+            check(t, F32, 'running buffer')
+            assert t.is_contiguous()
+        pack = torch.empty(_hip.call_value('mgv_readout_fused_pack_elems'), dtype=torch.bfloat16, device=dev)
+        off = 0
+        for w, tr in ((W1d, False), (W2d, False), (W2d, True), (W1d, True)):
+            off = _pack_into(pack, off, w, tr)
+        y1 = torch.empty(N, 32, dtype=F32, device=dev)
+        y2 = torch.empty(N, 32, dtype=F32, device=dev)
+        stats = torch.empty(128, dtype=F32, device=dev)
+        sums = torch.empty(128, dtype=torch.float64, device=dev)
+        prob = torch.empty(N, 1, dtype=F32, device=dev)
+        ws = workspace(_hip.call_value('mgv_readout_fused_ws_doubles', N), dev, torch.float64)
+        _hip.call('mgv_readout_fused_fwd', N, ptr(hfd), ptr(pack), ptr(b1d), ptr(g1d), ptr(be1d), ptr(rm1), ptr(rv1), ptr(b2d), ptr(g2d),
+                  ptr(be2d), ptr(rm2), ptr(rv2), ptr(W3d), ptr(b3d), float(p1), float(p2), int(seed1), int(seed2), float(momentum),
+                  1 - momentum, float(eps), int(bool(clamp01)), ptr(y1), ptr(y2), ptr(stats), ptr(sums), ptr(prob), ptr(ws), ws.numel())
+        ctx.save_for_backward(hfd, y1, y2, stats, pack, g1d, be1d, g2d, be2d, W3d, b3d)
+        ctx.cfg = (float(p1), float(p2), int(seed1), int(seed2), int(bool(clamp01)))
+        return prob
+
+    @staticmethod
+    def backward(ctx, gprob):
+        hfd, y1, y2, stats, pack, g1, be1, g2, be2, W3, b3 = ctx.saved_tensors
+        p1, p2, seed1, seed2, clamp01 = ctx.cfg
+        N, dev = hfd.shape[0], hfd.device
+        gp = check(gprob.contiguous().reshape(-1), F32, 'gprob')
+        dhf = torch.empty_like(hfd)
+        grads = torch.empty(_hip.call_value('mgv_readout_fused_grad_floats'), dtype=F32, device=dev)
+        sums = torch.empty(128, dtype=torch.float64, device=dev)
+        ws = workspace(_hip.call_value('mgv_readout_fused_ws_doubles', N), dev, torch.float64)
+        _hip.call('mgv_readout_fused_bwd', N, ptr(hfd), ptr(y1), ptr(y2), ptr(stats), ptr(gp), ptr(pack), ptr(g1), ptr(be1), ptr(g2), ptr(be2),
+                  ptr(W3), ptr(b3), p1, p2, seed1, seed2, clamp01, ptr(dhf), ptr(grads), ptr(sums), ptr(ws), ws.numel())
+        sizes = (32 * 64, 32, 32, 32, 32 * 32, 32, 32, 32, 32, 1)
+        dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3 = torch.split(grads, sizes)
+        return (dhf, dW1.view(32, 64), db1, dg1, dbe1, dW2.view(32, 32), db2, dg2, dbe2, dW3.view(1, 32), db3) + (None,) * 11
+
+
 # ------------------------------------------------------------------------------------------------
 # VAE sampler + KL
 # ------------------------------------------------------------------------------------------------
