@@ -188,13 +188,18 @@ int mgv_class_pull_sum(int H, int64_t N, const float* gy_direct, const float* gy
  * utils/dag_utils.py:91-105 is replaced by the tile tables).  T gate types ("slots"), per slot:
  *   attn_u[T][2H] = Wk^T w_attn[H:],  Wvc[T][3H][2H] = W_ih Wv,  bvc[T][3H] = W_ih bv,  bih/bhh[T][3H].
  * order/tile_* : updated nodes sorted by (level, slot) cut into <=64-node single-slot tiles;
- * level_tile_ptr_host: HOST array [num_levels+1] of tile offsets.  hf must be zero on entry
- * (num_rounds = 1: every node is updated once from h0 = 0). */
+ * level_tile_ptr_host: HOST array [num_levels+1] of tile offsets.
+ * Round 1 (gh, h_prev and, backward, d_gh, g_hprev all NULL): hf must be zero on entry (every node is updated from h0 = 0).
+ * Rounds r >= 2 (dg_ae_model_aig.py:70 with num_rounds > 1; all four set): every updated gate's GRU starts from its state of the
+ * previous round.  hf holds the previous round's rows on entry (updated rows are rewritten), gh[N][3H] = W_hh h_prev + b_hh of each
+ * node's own aggregator (r, z, n blocks; formed by the caller with mgv_linear_*), h_prev[N][H], bhh[T][3H] zeros (b_hh is inside
+ * gh); backward: d_gh[N][3H] and g_hprev[N][H] = dh * z (rows of updated nodes written; the caller zeroes both), and the dbhh
+ * accumulator receives nothing meaningful (its gradient comes from the caller's linear kernels). */
 int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                        const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
                        const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
                        float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
-                       const float* bhh, void* stream);
+                       const float* bhh, const float* gh, const float* h_prev, void* stream);
 /* backward sweep, levels in reverse.  ghf[N][H] = dL/dhf from the losses; ghs[N][H] is ADDED to;
  * scratch: dzb[N][2H], alpha[E], dsc[E] (in-CSR edge order).  WvcT[T][2H][3H]. */
 int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
@@ -204,25 +209,8 @@ int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* l
                        const uint8_t* gslot, const float* hs, const float* hf, const float* attn_u,
                        const float* Wvc, const float* WvcT, const float* bvc, const float* bih, const float* bhh,
                        const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
-                       float* dWvc, float* dbvc, float* dbih, float* dbhh, void* stream);
-/* rounds r >= 2 on the fp32 kernels (dg_ae_model_aig.py:70 with num_rounds > 1): every updated gate's GRU starts from its state of
- * the previous round.  Same contract as mgv_func_sweep_round_fwd_x3 / _bwd_x3 below: hf holds the previous round's rows on entry
- * (updated rows are rewritten), gh[N][3H] = W_hh h_prev + b_hh of each node's own aggregator, h_prev[N][H], zero_bhh[T][3H] zeros;
- * backward: d_gh[N][3H] and g_hprev[N][H] = dh * z (rows of updated nodes written; the caller zeroes both), ghs is ADDED to. */
-int mgv_func_sweep_round_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                             const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                             const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
-                             float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
-                             const float* zero_bhh, const float* gh, const float* h_prev, void* stream);
-int mgv_func_sweep_round_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                             const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                             const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src,
-                             const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_slot,
-                             const uint8_t* gslot, const float* hs, const float* hf, const float* attn_u,
-                             const float* Wvc, const float* WvcT, const float* bvc, const float* bih, const float* zero_bhh,
-                             const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
-                             float* dWvc, float* dbvc, float* dbih, float* dbhh_unused, const float* gh, const float* h_prev,
-                             float* d_gh, float* g_hprev, void* stream);
+                       float* dWvc, float* dbvc, float* dbih, float* dbhh, const float* gh, const float* h_prev,
+                       float* d_gh, float* g_hprev, void* stream);
 
 /* the sweep on bf16x3 split-precision MFMA (H in {32, 64}, T <= 6).  Differences from the fp32 entry points:
  * wpack_bf16[T][4][6H^2] = per slot {Wvc_hi, Wvc_lo, WvcT_hi, WvcT_lo} as bf16 in MFMA fragment order
@@ -244,40 +232,9 @@ int mgv_func_sweep_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t
                           const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
                           const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
                           const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
-                          const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh, void* stream);
-int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                          const int32_t* order, const int32_t* order_span, int order_span_ints, int64_t n_active,
-                          const int32_t* tile_start, const int32_t* tile_count, const int32_t* tile_slot,
-                          const int32_t* slot_tiles, const int32_t* slot_tile_ptr_host, const int32_t* in_ptr,
-                          const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
-                          const int32_t* out_slot, const uint8_t* gslot, const float* hs, const float* hf,
-                          const float* attn_u, const void* wpack_bf16, const float* bvc, const float* bih,
-                          const float* bhh, const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc,
-                          float* d_attn_u, float* dWvc, float* dbvc, float* dbih, float* dbhh, float* scratch,
-                          int64_t scratch_elems,
-                          int skip_inactive_longer_than /* > 0: never-updated nodes with more consumers are left to mgv_sweep_pull_heavy */,
-                          /* updated gates with more than skip_active_longer_than consumers (an inverter of a clock-like input), ordered by
-                           * (level, id): nodes[K], node_seg_ptr[K+1], segment bounds, per-level ranges of nodes and segments as HOST arrays
-                           * [num_levels + 1] (GraphPlan.heavy_segments(True, active_by_level=True)); heavy_ws: (K + segments) * 2H floats.
-                           * Their pulls run per level by whole workgroups in front of the level's kernel.  0 / NULLs: none. */
-                          int heavy_active_n, const int32_t* heavy_nodes, const int32_t* heavy_node_seg_ptr, const int32_t* heavy_seg_e0,
-                          const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host, const int32_t* heavy_lvl_seg_ptr_host,
-                          float* heavy_ws, int skip_active_longer_than, void* stream);
-
-/* Rounds >= 2 of the functional sweep (dg_ae_model_aig.py:70-97 with num_rounds > 1: every gate is updated again, its GRU starting
- * from the node's state of the previous round; bf16x3, H in {32, 64}).  Same arguments as the two entries above plus
- *   gh[N][3H]     W_hh h_prev + b_hh of each node's own aggregator (r, z, n blocks), formed by the caller with mgv_linear_*;
- *   h_prev[N][H]  the previous round's states; `hf` must hold a copy of them on entry (rows of never-updated nodes stay);
- *   zero_bhh      [T][3H] zeros (b_hh is inside gh);
- * backward: d_gh[N][3H] (rows of updated nodes written) and g_hprev[N][H] = dh * z (the caller zeroes it: other rows are not written);
- * the dbhh accumulator receives nothing meaningful (its gradient comes from the caller's linear kernels). */
-int mgv_func_sweep_round_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                          const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
-                          const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
-                          const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
-                          const void* wpack_bf16, const float* bvc, const float* bih, const float* zero_bhh,
+                          const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh,
                           const float* gh, const float* h_prev, void* stream);
-int mgv_func_sweep_round_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
+int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                           const int32_t* order, const int32_t* order_span, int order_span_ints, int64_t n_active,
                           const int32_t* tile_start, const int32_t* tile_count, const int32_t* tile_slot,
                           const int32_t* slot_tiles, const int32_t* slot_tile_ptr_host, const int32_t* in_ptr,
@@ -296,6 +253,7 @@ int mgv_func_sweep_round_bwd_x3(int H, int64_t N, int T, int num_levels, const i
                           const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host, const int32_t* heavy_lvl_seg_ptr_host,
                           float* heavy_ws, int skip_active_longer_than,
                           const float* gh, const float* h_prev, float* d_gh, float* g_hprev, void* stream);
+
 /* ---- stand-alone TFMlpAggr (arch/tfmlp.py:31-46: an edge-list call outside the levelised sweep).  Attention pooling over a CSR by
  * destination: zbar[i][W] = sum_j alpha_ij x[j], alpha = softmax over i's sources of u . x[j] (PyG softmax: exp(s - max) / (sum + 1e-16));
  * the module's message is W_v zbar + b_v [deg > 0] (mgv_linear_*).  W = row width (2 * dim_hidden) in {32, 64, 128};
@@ -313,44 +271,6 @@ int mgv_sweep_pull_heavy(int H, int K, const int32_t* nodes, const int32_t* node
                          const int32_t* seg_e1, const int32_t* out_dst, const int32_t* out_slot, const uint8_t* gslot,
                          const float* alpha, const float* dsc, const float* dzb, const float* attn_u, float* partial_ws,
                          float* ghs, void* stream);
-
-/* ---- the levelised sweep as ONE persistent kernel per direction (csrc/sweep_persist_x3.hip; replaces the reference's Python level
- * loop dg_ae_model_aig.py:70-97 and arch/tfmlp.py:38-46 like mgv_func_sweep_*_x3, which launch once per level).  H = 64, round 1.
- * One 8-wave workgroup per CU, each dedicated to one aggregator slot with that slot's Wvc pack resident in LDS; levels are
- * separated by an XCD-hierarchical grid barrier (csrc/mgv_gridbar.h); rows other workgroups read are stored write-through; the
- * backward accumulates dWvc in registers across all levels (no per-node rows for a deferred weight-gradient pass).
- *   key_tile_ptr[num_levels*T + 1]  DEVICE: tile range of every (level, slot) key (tiles are sorted by level, then slot)
- *   wg_begin_host[T + 1]            HOST: workgroups [wg_begin[g], wg_begin[g+1]) serve slot g; wg_begin[T] = grid <= CU count
- *   slot_tile_ptr_host[T + 1]       HOST: tiles per slot (a slot with tiles must own a workgroup)
- *   sync_ws                         DEVICE: mgv_sweep_persist_sync_bytes() bytes, zeroed by the launcher before every launch
- *   sticky_status                   DEVICE: one uint32 the CALLER zeroes once; set (never cleared) when a barrier spin gave up
- * Returns MGV_EUNSUPPORTED (use the per-level launchers) for H != 64, N*2H*4 >= 4 GB, or a grid beyond the CU count.
- * mgv_sweep_persist_status copies the sticky word back (synchronises the stream): MGV_OK, or 1000 + the give-up code. */
-int mgv_sweep_persist_sync_bytes(void);                                                               /* a size, not a status */
-int mgv_sweep_persist_max_grid(void);                                                                 /* CU count of the current device */
-int mgv_func_sweep_fwd_persist_x3(int H, int64_t N, int T, int num_levels, const int32_t* key_tile_ptr,
-                                  const int32_t* wg_begin_host, const int32_t* slot_tile_ptr_host, const int32_t* order,
-                                  const int32_t* order_span, const int32_t* tile_start, const int32_t* tile_count,
-                                  const int32_t* in_ptr, const int32_t* in_src, const float* hs, float* hf,
-                                  const float* attn_u, const void* wpack_bf16, const float* bvc, const float* bih,
-                                  const float* bhh, void* sync_ws, void* sticky_status, void* stream);
-/* backward: wg_slab >= mgv_sweep_persist_slab_floats(H, grid) floats (one gradient partial row per workgroup, summed per slot in
- * workgroup order: deterministic); d_attn_u / dWvc / dbvc / dbih / dbhh are ADDED to; ghs is WRITTEN for every node (the pull of the
- * never-updated nodes follows as in mgv_func_sweep_bwd_x3; skip_inactive_longer_than as there).  The plan must hold no UPDATED gate
- * with more than 64 consumers (GraphPlan.heavy_segments(True, active_by_level=True) is None): such batches use mgv_func_sweep_bwd_x3. */
-int mgv_sweep_persist_slab_floats(int H, int grid);                                                   /* a size, not a status */
-int mgv_func_sweep_bwd_persist_x3(int H, int64_t N, int T, int num_levels, const int32_t* key_tile_ptr,
-                                  const int32_t* wg_begin_host, const int32_t* slot_tile_ptr_host, const int32_t* order,
-                                  const int32_t* order_span, const int32_t* tile_start, const int32_t* tile_count,
-                                  const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
-                                  const int32_t* out_dst, const int32_t* out_slot, const uint8_t* gslot, const float* hs,
-                                  const float* hf, const float* attn_u, const void* wpack_bf16, const float* bvc,
-                                  const float* bih, const float* bhh, const float* ghf, float* ghs, float* dzb,
-                                  float* alpha, float* dsc, float* d_attn_u, float* dWvc, float* dbvc, float* dbih,
-                                  float* dbhh, float* wg_slab, int64_t wg_slab_floats, int skip_inactive_longer_than,
-                                  void* sync_ws, void* sticky_status, void* stream);
-int mgv_sweep_persist_status(const void* sticky_status, void* stream);
-
 
 /* ---- inner-product decoder and reconstruction loss (digae_layer.py:26-29, dg_ae_model_aig.py:108-130).
  * s, t: row pointers with common row stride ld (the two halves of hs_decompose's output);

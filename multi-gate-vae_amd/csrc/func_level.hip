@@ -465,7 +465,7 @@ int launch_level(bool bwd, const LevelArgs& a, int ntiles, hipStream_t st) {
 }  // namespace mgv
 
 // Runs levels [1, L) forward.  level_tile_ptr is a HOST array of L+1 tile offsets.
-static int sweep_fwd_impl(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
+extern "C" int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                                   const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
                                   const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
                                   float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
@@ -494,26 +494,7 @@ static int sweep_fwd_impl(int H, int64_t N, int T, int num_levels, const int32_t
     return MGV_OK;
 }
 
-extern "C" int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                  const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                                  const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
-                                  float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
-                                  const float* bhh, void* stream) {
-    return sweep_fwd_impl(H, N, T, num_levels, level_tile_ptr_host, order, tile_start, tile_count, tile_slot, in_ptr, in_src, hs, hf, attn_u, Wvc,
-                          bvc, bih, bhh, nullptr, nullptr, stream);
-}
-
-extern "C" int mgv_func_sweep_round_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                        const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                                        const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
-                                        float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
-                                        const float* zero_bhh, const float* gh, const float* h_prev, void* stream) {
-    MGV_CHECK_ARG(gh && h_prev);
-    return sweep_fwd_impl(H, N, T, num_levels, level_tile_ptr_host, order, tile_start, tile_count, tile_slot, in_ptr, in_src, hs, hf, attn_u, Wvc,
-                          bvc, bih, zero_bhh, gh, h_prev, stream);
-}
-
-static int sweep_bwd_impl(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
+extern "C" int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                                   const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
                                   const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src,
                                   const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_slot,
@@ -558,32 +539,4 @@ static int sweep_bwd_impl(int H, int64_t N, int T, int num_levels, const int32_t
         default: return MGV_EUNSUPPORTED;
     }
     MGV_LAUNCH_RET();
-}
-
-extern "C" int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                  const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                                  const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src,
-                                  const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_slot,
-                                  const uint8_t* gslot, const float* hs, const float* hf, const float* attn_u,
-                                  const float* Wvc, const float* WvcT, const float* bvc, const float* bih, const float* bhh,
-                                  const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
-                                  float* dWvc, float* dbvc, float* dbih, float* dbhh, void* stream) {
-    return sweep_bwd_impl(H, N, T, num_levels, level_tile_ptr_host, order, tile_start, tile_count, tile_slot, in_ptr, in_src, out_ptr, out_dst,
-                          out_slot, gslot, hs, hf, attn_u, Wvc, WvcT, bvc, bih, bhh, ghf, ghs, dzb, alpha, dsc, d_attn_u, dWvc, dbvc, dbih, dbhh,
-                          nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int mgv_func_sweep_round_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                        const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
-                                        const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src,
-                                        const int32_t* out_ptr, const int32_t* out_dst, const int32_t* out_slot,
-                                        const uint8_t* gslot, const float* hs, const float* hf, const float* attn_u,
-                                        const float* Wvc, const float* WvcT, const float* bvc, const float* bih, const float* zero_bhh,
-                                        const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
-                                        float* dWvc, float* dbvc, float* dbih, float* dbhh_unused, const float* gh, const float* h_prev,
-                                        float* d_gh, float* g_hprev, void* stream) {
-    MGV_CHECK_ARG(gh && h_prev && d_gh && g_hprev);
-    return sweep_bwd_impl(H, N, T, num_levels, level_tile_ptr_host, order, tile_start, tile_count, tile_slot, in_ptr, in_src, out_ptr, out_dst,
-                          out_slot, gslot, hs, hf, attn_u, Wvc, WvcT, bvc, bih, zero_bhh, ghf, ghs, dzb, alpha, dsc, d_attn_u, dWvc, dbvc, dbih,
-                          dbhh_unused, gh, h_prev, d_gh, g_hprev, stream);
 }

@@ -661,12 +661,12 @@ extern "C" int mgv_sweep_zero_inactive(int H, int64_t N, const uint8_t* gslot, f
     MGV_LAUNCH_RET();
 }
 
-static int sweep_fwd_x3_impl(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                             const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
-                             const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
-                             const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
-                             const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh,
-                             const float* gh, const float* h_prev, void* stream) {
+extern "C" int mgv_func_sweep_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
+                                     const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
+                                     const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
+                                     const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
+                                     const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh,
+                                     const float* gh, const float* h_prev, void* stream) {
     MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && wpack_bf16 && bvc && bih && bhh && in_ptr);
     MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
     mgv::LevelX3Args a{};
@@ -693,27 +693,7 @@ static int sweep_fwd_x3_impl(int H, int64_t N, int T, int num_levels, const int3
     return MGV_OK;
 }
 
-extern "C" int mgv_func_sweep_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                     const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
-                                     const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
-                                     const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
-                                     const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh, void* stream) {
-    return sweep_fwd_x3_impl(H, N, T, num_levels, level_tile_ptr_host, order, order_span, order_span_ints, tile_start, tile_count, tile_slot, in_ptr, in_src, hs, hf,
-                             attn_u, wpack_bf16, bvc, bih, bhh, nullptr, nullptr, stream);
-}
-
-extern "C" int mgv_func_sweep_round_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                           const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
-                                           const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
-                                           const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
-                                           const void* wpack_bf16, const float* bvc, const float* bih, const float* zero_bhh,
-                                           const float* gh, const float* h_prev, void* stream) {
-    MGV_CHECK_ARG(gh && h_prev);
-    return sweep_fwd_x3_impl(H, N, T, num_levels, level_tile_ptr_host, order, order_span, order_span_ints, tile_start, tile_count, tile_slot, in_ptr, in_src, hs, hf,
-                             attn_u, wpack_bf16, bvc, bih, zero_bhh, gh, h_prev, stream);
-}
-
-static int sweep_bwd_x3_impl(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
+extern "C" int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                                      const int32_t* order, const int32_t* order_span, int order_span_ints, int64_t n_active,
                                      const int32_t* tile_start, const int32_t* tile_count, const int32_t* tile_slot,
                                      const int32_t* slot_tiles, const int32_t* slot_tile_ptr_host, const int32_t* in_ptr,
@@ -804,46 +784,6 @@ static int sweep_bwd_x3_impl(int H, int64_t N, int T, int num_levels, const int3
         default: return MGV_EUNSUPPORTED;
     }
     MGV_LAUNCH_RET();
-}
-
-extern "C" int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                     const int32_t* order, const int32_t* order_span, int order_span_ints, int64_t n_active,
-                                     const int32_t* tile_start, const int32_t* tile_count, const int32_t* tile_slot,
-                                     const int32_t* slot_tiles, const int32_t* slot_tile_ptr_host, const int32_t* in_ptr,
-                                     const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
-                                     const int32_t* out_slot, const uint8_t* gslot, const float* hs, const float* hf,
-                                     const float* attn_u, const void* wpack_bf16, const float* bvc, const float* bih,
-                                     const float* bhh, const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc,
-                                     float* d_attn_u, float* dWvc, float* dbvc, float* dbih, float* dbhh, float* scratch,
-                                     int64_t scratch_elems, int skip_inactive_longer_than, int heavy_active_n,
-                                     const int32_t* heavy_nodes, const int32_t* heavy_node_seg_ptr, const int32_t* heavy_seg_e0,
-                                     const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host,
-                                     const int32_t* heavy_lvl_seg_ptr_host, float* heavy_ws, int skip_active_longer_than, void* stream) {
-    return sweep_bwd_x3_impl(H, N, T, num_levels, level_tile_ptr_host, order, order_span, order_span_ints, n_active, tile_start, tile_count, tile_slot, slot_tiles,
-                             slot_tile_ptr_host, in_ptr, in_src, out_ptr, out_dst, out_slot, gslot, hs, hf, attn_u, wpack_bf16, bvc, bih, bhh, ghf, ghs, dzb,
-                             alpha, dsc, d_attn_u, dWvc, dbvc, dbih, dbhh, scratch, scratch_elems, skip_inactive_longer_than, heavy_active_n, heavy_nodes,
-                             heavy_node_seg_ptr, heavy_seg_e0, heavy_seg_e1, heavy_lvl_k_ptr_host, heavy_lvl_seg_ptr_host, heavy_ws, skip_active_longer_than, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-extern "C" int mgv_func_sweep_round_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
-                                     const int32_t* order, const int32_t* order_span, int order_span_ints, int64_t n_active,
-                                     const int32_t* tile_start, const int32_t* tile_count, const int32_t* tile_slot,
-                                     const int32_t* slot_tiles, const int32_t* slot_tile_ptr_host, const int32_t* in_ptr,
-                                     const int32_t* in_src, const int32_t* out_ptr, const int32_t* out_dst,
-                                     const int32_t* out_slot, const uint8_t* gslot, const float* hs, const float* hf,
-                                     const float* attn_u, const void* wpack_bf16, const float* bvc, const float* bih,
-                                     const float* bhh, const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc,
-                                     float* d_attn_u, float* dWvc, float* dbvc, float* dbih, float* dbhh, float* scratch,
-                                     int64_t scratch_elems, int skip_inactive_longer_than, int heavy_active_n,
-                                     const int32_t* heavy_nodes, const int32_t* heavy_node_seg_ptr, const int32_t* heavy_seg_e0,
-                                     const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host,
-                                     const int32_t* heavy_lvl_seg_ptr_host, float* heavy_ws, int skip_active_longer_than,
-                                     const float* gh, const float* h_prev, float* d_gh, float* g_hprev, void* stream) {
-    MGV_CHECK_ARG(gh && h_prev && d_gh && g_hprev);
-    return sweep_bwd_x3_impl(H, N, T, num_levels, level_tile_ptr_host, order, order_span, order_span_ints, n_active, tile_start, tile_count, tile_slot, slot_tiles,
-                             slot_tile_ptr_host, in_ptr, in_src, out_ptr, out_dst, out_slot, gslot, hs, hf, attn_u, wpack_bf16, bvc, bih, bhh, ghf, ghs, dzb,
-                             alpha, dsc, d_attn_u, dWvc, dbvc, dbih, dbhh, scratch, scratch_elems, skip_inactive_longer_than, heavy_active_n, heavy_nodes,
-                             heavy_node_seg_ptr, heavy_seg_e0, heavy_seg_e1, heavy_lvl_k_ptr_host, heavy_lvl_seg_ptr_host, heavy_ws, skip_active_longer_than, gh, h_prev, d_gh, g_hprev, stream);
 }
 
 // ghs[nodes[k]] = the pull of heavy never-updated nodes (skipped by mgv_func_sweep_bwd_x3 when skip_inactive_longer_than > 0), their

@@ -1,10 +1,9 @@
-// Device pieces shared by the per-level sweep kernels (func_level_x3.hip) and the persistent sweep kernels
-// (sweep_persist_x3.hip): argument block, LDS carving, index staging, attention forward / backward rows, the gate product.
+// Device pieces of the per-level sweep kernels (func_level_x3.hip): argument block, LDS carving, index staging, attention
+// forward / backward rows, the gate product.
 #pragma once
 #include "mgv_x3.h"
 #include "mgv_stamps.h"
 #include "mgv_slab.h"
-#include "mgv_gridbar.h"
 #include <algorithm>
 #include "../../include/mgvae_hip.h"
 
@@ -353,8 +352,7 @@ struct OutRows {
 // with zbar = sum_k alpha_k x_k re-formed here in fp32 from the source rows: the difference of two nearly equal rows is taken
 // exactly before the dot product.  (Subtracting d(zbar) . zbar with zbar read back from its bf16 hi/lo planes — 2^-17 relative —
 // left the attention-logit parameters attn_lin / msg_k with 1e-3 of their scale in error: their gradient IS this cancelling sum.)
-// (WT: the per-edge scalars of the list's tail leave write-through, for the persistent sweep whose other workgroups read them in-launch)
-template <int H, bool WT = false>
+template <int H>
 __device__ __forceinline__ void attn_bwd_row(const LevelX3Args& a, const InRows<H>& L, const int4& sp, const float4& us,
                                              const float4& uf, const float4& dzs, const float4& dzf, float m,
                                              float inv, int lr, float (&al)[kInRegs], float (&ds)[kInRegs], float4& gus, float4& guf) {
@@ -390,10 +388,7 @@ __device__ __forceinline__ void attn_bwd_row(const LevelX3Args& a, const InRows<
         const float al_e = __expf(group_sum<LPR>(dot4(us, xs) + dot4(uf, xf)) - m) * inv;
         const float4 cs = make_float4(xs.x - zs.x, xs.y - zs.y, xs.z - zs.z, xs.w - zs.w), cf = make_float4(xf.x - zf.x, xf.y - zf.y, xf.z - zf.z, xf.w - zf.w);
         const float ds_e = al_e * group_sum<LPR>(dot4(dzs, cs) + dot4(dzf, cf));
-        if (lr == 0) {
-            if (WT) { st1_wt(a.alpha + e, al_e); st1_wt(a.dsc + e, ds_e); }
-            else { a.alpha[e] = al_e; a.dsc[e] = ds_e; }
-        }
+        if (lr == 0) { a.alpha[e] = al_e; a.dsc[e] = ds_e; }
         gus = fma4(ds_e, xs, gus);
         guf = fma4(ds_e, xf, guf);
     }

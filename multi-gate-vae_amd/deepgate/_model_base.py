@@ -73,10 +73,10 @@ class FunctionalModel(nn.Module):
         self._hs_pass = None
         hf = ops.FuncSweepFn.apply(plan, hs_in, *self._sweep_params())
         # further rounds (dg_ae_model_aig.py:70; the reference default and train.py use 1): every gate is updated again, its GRU
-        # starting from the gate's previous state, on the same level kernels (ops.FuncSweepRoundFn)
+        # starting from the gate's previous state, on the same level kernels (b_hh is inside gh)
         for _ in range(self.num_rounds - 1):
             au, Wvc, bvc, bih, _ = self._sweep_params()
-            hf = ops.FuncSweepRoundFn.apply(plan, hs_in, hf, self._round_gh(plan, hf), au, Wvc, bvc, bih)
+            hf = ops.FuncSweepFn.apply(plan, hs_in, au, Wvc, bvc, bih, None, hf, self._round_gh(plan, hf))
         return hs, hf
 
     def _round_gh(self, plan, hf):

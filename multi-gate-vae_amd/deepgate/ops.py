@@ -687,7 +687,7 @@ _SWEEP_BWD_EVENT = None
 
 
 def _sweep_bwd_prep(plan, T, H, dev):
-    """Scratch and heavy-list arguments of mgv_func_sweep_bwd_x3 / mgv_func_sweep_round_bwd_x3."""
+    """Scratch and heavy-list arguments of mgv_func_sweep_bwd_x3."""
     ltp = plan.level_tile_ptr
     widest = max([ltp[i + 1] - ltp[i] for i in range(1, len(ltp) - 1)] + [1])
     # rows for the deferred weight gradient, small-gradient slabs of the widest level, 256 rows of weight-gradient partials
@@ -714,10 +714,6 @@ def _sweep_x3(H):
     return use_x3(H) and os.environ.get('MGV_SWEEP_X3', '1') != '0'
 
 
-# The sweep as ONE persistent kernel per direction (csrc/sweep_persist_x3.hip: slot-dedicated workgroups, weights resident in LDS, XCD
-# grid barrier, in-register weight gradient).  Built, parity-tested and MEASURED in round 4: not faster than the per-level kernels at any
-# batch size (config 2: forward 2.17 vs 2.00 ms, backward 8.2 vs 7.4 ms; one graph: 0.95 / 2.80 vs 1.01 / 2.84 ms), so it is
-# opt-in (MGV_SWEEP_PERSIST=1) and the per-level kernels stay the default.
 GROUPED_ROUND = True            # rounds >= 2: W_hh h_prev + b_hh of every updated gate as one grouped Linear (RoundGhFn); False: per gate type on the plain kernels
 
 # The level kernels read packed rows (GraphPlan.order_rows: spans + first in-edge sources + first consumers, one 128-byte line per
@@ -740,189 +736,74 @@ def _sweep_rows(plan, forward=False):
     return ptr(plan.order_span), 4
 
 
-PERSIST = os.environ.get('MGV_SWEEP_PERSIST', '0') == '1'
-
-
-def _persist_ws(dev):
-    """(barrier state, sticky status word) of the persistent sweep kernels on `dev`: the launchers zero the first before every
-    launch, the second is zeroed here once and only ever set by a kernel whose barrier gave up (persist_check)."""
-    key = ('persist', str(dev))
-    ws = _WS.get(key)
-    if ws is None:
-        nb = _hip.call_value('mgv_sweep_persist_sync_bytes')
-        ws = _WS[key] = (torch.zeros((nb + 3) // 4, dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int32, device=dev),
-                         _hip.call_value('mgv_sweep_persist_max_grid'))
-    return ws
-
-
-def persist_status(dev):
-    """The sticky status word as a device tensor (one int32; the trainer copies it back with the step metrics)."""
-    return _persist_ws(dev)[1][:1]
-
-
-def persist_check(dev=None):
-    """Raise if a persistent sweep kernel on `dev` ever gave up at its grid barrier (synchronises)."""
-    for key, ws in list(_WS.items()):
-        if key[0] == 'persist' and (dev is None or key[1] == str(dev)):
-            code = int(ws[1][0].item())
-            if code != 0:
-                raise HipLibraryError('persistent sweep kernel gave up at its grid barrier (code %d): its results are invalid' % code)
-
-
-def _persist_roles(plan, H, N):
-    """wg_begin (ctypes array) when the persistent sweep kernels serve this plan, else None (-> the per-level kernels)."""
-    if not (PERSIST and H == 64 and plan.num_levels > 2 and N * 2 * H * 4 < (1 << 32) and getattr(plan, 'key_tile_ptr', None) is not None):
-        return None
-    roles = plan.persist_roles(_persist_ws(plan.device)[2])
-    if roles is None:
-        return None
-    return (_hip.ctypes.c_int32 * len(roles))(*roles)
-
-
-class FuncSweepRoundFn(torch.autograd.Function):
-    """Round r >= 2 of the functional sweep (dg_ae_model_aig.py:70-97 with num_rounds > 1) on the HIP level kernels (bf16x3 or
-    exact fp32, as round 1): hf_new = sweep(hs, hf_prev) where every updated gate's GRU starts from its previous state.
+class FuncSweepFn(torch.autograd.Function):
+    """hf = sweep(hs) over levels 1..L-1 (dg_ae_model_aig.py:70-97) on the HIP level kernels, bf16x3 or exact fp32; parameters are
+    the per-slot composed tensors attn_u [T,2H], Wvc [T,3H,2H], bvc/bih/bhh [T,3H].
+    Rounds r >= 2 (num_rounds > 1) pass `hprev` [N, H], the previous round's states, from which every updated gate's GRU starts,
     `gh` [N, 3H] = W_hh h_prev + b_hh of each node's own aggregator, formed by the caller with ops.linear (so that autograd carries
-    its gradient to W_hh, b_hh and h_prev through the linear kernels); the level kernels add it to the gate pre-activations, mix
-    z * h_prev into the new state and leave d(gh) and dh * z on the way back.  High fan-out lists take the same pre-passes as in
-    round 1 (GraphPlan.heavy_segments)."""
+    its gradient to W_hh, b_hh and h_prev through the linear kernels), and bhh=None (b_hh is inside gh: a zero bias).  The level
+    kernels add gh to the gate pre-activations, mix z * h_prev into the new state and leave d(gh) and dh * z on the way back.
+    High fan-out lists take the same pre-passes in every round (GraphPlan.heavy_segments)."""
 
     @staticmethod
-    def forward(ctx, plan, hs, hprev, gh, attn_u, Wvc, bvc, bih):
+    def forward(ctx, plan, hs, attn_u, Wvc, bvc, bih, bhh, hprev=None, gh=None):
         hsd = check(hs.detach().contiguous(), F32, 'hs')
-        hp = check(hprev.detach().contiguous(), F32, 'h_prev')
-        ghd = check(gh.detach().contiguous(), F32, 'gh')
         N, H = hsd.shape
-        par = [check(t.detach().contiguous(), F32, 'sweep parameter') for t in (attn_u, Wvc, bvc, bih)]
-        T = par[0].shape[0]
-        assert plan.has_levels and plan.num_slots == T and plan.N == N and ghd.shape == (N, 3 * H) and hp.shape == (N, H)
+        T = attn_u.shape[0]
+        if bhh is None:
+            bhh = torch.zeros(T, 3 * H, dtype=F32, device=hsd.device)
+        par = [check(t.detach().contiguous(), F32, 'sweep parameter') for t in (attn_u, Wvc, bvc, bih, bhh)]
+        assert plan.has_levels and plan.num_slots == T and plan.N == N
+        hp = ghd = None
+        if hprev is not None:
+            hp = check(hprev.detach().contiguous(), F32, 'h_prev')
+            ghd = check(gh.detach().contiguous(), F32, 'gh')
+            assert ghd.shape == (N, 3 * H) and hp.shape == (N, H)
         ltp = (_hip.ctypes.c_int32 * len(plan.level_tile_ptr))(*plan.level_tile_ptr)
         wpack = sweep_wpack(par[1]) if _sweep_x3(H) else None
-        zb = torch.zeros(T, 3 * H, dtype=F32, device=hsd.device)
-        hf = hp.clone()                      # never-updated rows keep their state; every updated row is rewritten by its level
-        if wpack is not None:
-            _hip.call('mgv_func_sweep_round_fwd_x3', H, N, T, plan.num_levels, ltp, ptr(plan.order), *_sweep_rows(plan, True),
-                      ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd), ptr(hf),
-                      ptr(par[0]), ptr(wpack), ptr(par[2]), ptr(par[3]), ptr(zb), ptr(ghd), ptr(hp))
+        if hp is not None:
+            hf = hp.clone()                  # never-updated rows keep their state; every updated row is rewritten by its level
+        elif wpack is not None:
+            hf = torch.empty(N, H, dtype=F32, device=hsd.device)          # every updated row is written by its level; the rest here
+            _hip.call('mgv_sweep_zero_inactive', H, N, ptr(plan.gslot), ptr(hf))
         else:
-            _hip.call('mgv_func_sweep_round_fwd', H, N, T, plan.num_levels, ltp, ptr(plan.order), ptr(plan.tile_start),
+            hf = torch.zeros(N, H, dtype=F32, device=hsd.device)
+        if wpack is not None:
+            _hip.call('mgv_func_sweep_fwd_x3', H, N, T, plan.num_levels, ltp, ptr(plan.order), *_sweep_rows(plan, True),
+                      ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd), ptr(hf),
+                      ptr(par[0]), ptr(wpack), ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(ghd), ptr(hp))
+        else:
+            _hip.call('mgv_func_sweep_fwd', H, N, T, plan.num_levels, ltp, ptr(plan.order), ptr(plan.tile_start),
                       ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd), ptr(hf),
-                      ptr(par[0]), ptr(par[1]), ptr(par[2]), ptr(par[3]), ptr(zb), ptr(ghd), ptr(hp))
-        ctx.plan, ctx.par, ctx.ltp, ctx.wpack, ctx.zb = plan, par, ltp, wpack, zb
+                      *[ptr(t) for t in par], ptr(ghd), ptr(hp))
+        ctx.plan, ctx.par, ctx.ltp, ctx.wpack = plan, par, ltp, wpack
         ctx.save_for_backward(hsd, hf, hp, ghd)
         return hf
 
     @staticmethod
     def backward(ctx, ghf):
+        # start signal for work that should run BESIDE the (latency-bound) sweep backward of round 1 on another stream: the
+        # reconstruction branch's backward waits for it (ReconLossFn.backward), instead of starting beside the bandwidth-bound readout backward
+        global _SWEEP_BWD_EVENT
         plan, par = ctx.plan, ctx.par
         hs, hf, hp, ghd = ctx.saved_tensors
-        N, H = hs.shape
-        T = par[0].shape[0]
-        dev = hs.device
-        ghf = check(ghf.contiguous(), F32, 'ghf')
-        dzb = torch.empty(N, 2 * H, dtype=F32, device=dev)
-        alpha = torch.empty(max(plan.E, 1), dtype=F32, device=dev)
-        dsc = torch.empty(max(plan.E, 1), dtype=F32, device=dev)
-        grads = [torch.zeros_like(t) for t in par] + [torch.zeros_like(ctx.zb)]      # the last one (dbhh) is not meaningful here
-        d_gh = torch.zeros(N, 3 * H, dtype=F32, device=dev)          # rows of never-updated nodes stay zero
-        g_hprev = torch.zeros(N, H, dtype=F32, device=dev)           # (their states are constants of round 1: no gradient to carry)
-        if ctx.wpack is None:
-            ghs = torch.zeros(N, H, dtype=F32, device=dev)           # the fp32 kernels add to it
-            WvcT = par[1].transpose(1, 2).contiguous()
-            _hip.call('mgv_func_sweep_round_bwd', H, N, T, plan.num_levels, ctx.ltp, ptr(plan.order), ptr(plan.tile_start),
-                      ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(plan.out_ptr),
-                      ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]), ptr(par[1]),
-                      ptr(WvcT), ptr(par[2]), ptr(par[3]), ptr(ctx.zb), ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc),
-                      *[ptr(g) for g in grads], ptr(ghd), ptr(hp), ptr(d_gh), ptr(g_hprev))
-            return (None, ghs, g_hprev, d_gh, grads[0], grads[1], grads[2], grads[3])
-        ghs = torch.empty(N, H, dtype=F32, device=dev)
-        scratch, stp, hv, ha = _sweep_bwd_prep(plan, T, H, dev)
-        _hip.call('mgv_func_sweep_round_bwd_x3', H, N, T, plan.num_levels, ctx.ltp, ptr(plan.order), *_sweep_rows(plan),
-                  plan.n_active, ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.slot_tiles), stp,
-                  ptr(plan.in_ptr), ptr(plan.in_src), ptr(plan.out_ptr), ptr(plan.out_dst), ptr(plan.out_slot),
-                  ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]), ptr(ctx.wpack), ptr(par[2]), ptr(par[3]), ptr(ctx.zb),
-                  ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc), *[ptr(g) for g in grads], ptr(scratch),
-                  scratch.numel(), plan.HEAVY_ROW if hv is not None else 0, *ha, ptr(ghd), ptr(hp), ptr(d_gh), ptr(g_hprev))
-        if hv is not None:
-            # primary inputs (never updated) that drive thousands of gates: their pull by whole workgroups, per list segment
-            pw = workspace(hv['S'] * H, dev)
-            _hip.call('mgv_sweep_pull_heavy', H, hv['K'], ptr(hv['nodes']), ptr(hv['node_seg_ptr']), hv['S'], ptr(hv['seg_e0']), ptr(hv['seg_e1']),
-                      ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(alpha), ptr(dsc), ptr(dzb), ptr(par[0]), ptr(pw), ptr(ghs))
-        return (None, ghs, g_hprev, d_gh, grads[0], grads[1], grads[2], grads[3])
-
-
-class FuncSweepFn(torch.autograd.Function):
-    """hf = sweep(hs) over levels 1..L-1 (dg_ae_model_aig.py:70-97); parameters are the per-slot
-    composed tensors attn_u [T,2H], Wvc [T,3H,2H], bvc/bih/bhh [T,3H]."""
-
-    @staticmethod
-    def forward(ctx, plan, hs, attn_u, Wvc, bvc, bih, bhh):
-        hsd = check(hs.detach().contiguous(), F32, 'hs')
-        N, H = hsd.shape
-        par = [check(t.detach().contiguous(), F32, 'sweep parameter') for t in (attn_u, Wvc, bvc, bih, bhh)]
-        T = par[0].shape[0]
-        assert plan.has_levels and plan.num_slots == T and plan.N == N
-        ltp = (_hip.ctypes.c_int32 * len(plan.level_tile_ptr))(*plan.level_tile_ptr)
-        wpack = sweep_wpack(par[1]) if _sweep_x3(H) else None
-        if wpack is not None:
-            hf = torch.empty(N, H, dtype=F32, device=hsd.device)          # every updated row is written by its level; the rest here
-            _hip.call('mgv_sweep_zero_inactive', H, N, ptr(plan.gslot), ptr(hf))
-        else:
-            hf = torch.zeros(N, H, dtype=F32, device=hsd.device)
-        roles = _persist_roles(plan, H, N) if wpack is not None else None
-        if roles is not None:
-            sync, sticky, _ = _persist_ws(hsd.device)
-            stp = (_hip.ctypes.c_int32 * len(plan.slot_tile_ptr))(*plan.slot_tile_ptr)
-            _hip.call('mgv_func_sweep_fwd_persist_x3', H, N, T, plan.num_levels, ptr(plan.key_tile_ptr), roles, stp, ptr(plan.order),
-                      ptr(plan.order_span), ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd),
-                      ptr(hf), ptr(par[0]), ptr(wpack), ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(sync), ptr(sticky))
-        elif wpack is not None:
-            _hip.call('mgv_func_sweep_fwd_x3', H, N, T, plan.num_levels, ltp, ptr(plan.order), *_sweep_rows(plan, True),
-                      ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd), ptr(hf),
-                      ptr(par[0]), ptr(wpack), ptr(par[2]), ptr(par[3]), ptr(par[4]))
-        else:
-            _hip.call('mgv_func_sweep_fwd', H, N, T, plan.num_levels, ltp, ptr(plan.order), ptr(plan.tile_start),
-                      ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(hsd), ptr(hf),
-                      *[ptr(t) for t in par])
-        ctx.plan, ctx.par, ctx.ltp, ctx.wpack = plan, par, ltp, wpack
-        ctx.save_for_backward(hsd, hf)
-        return hf
-
-    @staticmethod
-    def backward(ctx, ghf):
-        # start signal for work that should run BESIDE the (latency-bound) sweep backward on another stream: the reconstruction
-        # branch's backward waits for it (ReconLossFn.backward), instead of starting beside the bandwidth-bound readout backward
-        global _SWEEP_BWD_EVENT
-        if ghf.is_cuda:
+        if hp is None and ghf.is_cuda:
             _SWEEP_BWD_EVENT = torch.cuda.Event()
             _SWEEP_BWD_EVENT.record()
-        plan, par = ctx.plan, ctx.par
-        hs, hf = ctx.saved_tensors
         N, H = hs.shape
         T = par[0].shape[0]
         dev = hs.device
         ghf = check(ghf.contiguous(), F32, 'ghf')
-        ghs = (torch.empty if ctx.wpack is not None else torch.zeros)(N, H, dtype=F32, device=dev)
+        ghs = (torch.empty if ctx.wpack is not None else torch.zeros)(N, H, dtype=F32, device=dev)    # (the fp32 kernels add to it)
         dzb = torch.empty(N, 2 * H, dtype=F32, device=dev)
         alpha = torch.empty(max(plan.E, 1), dtype=F32, device=dev)
         dsc = torch.empty(max(plan.E, 1), dtype=F32, device=dev)
-        grads = [torch.zeros_like(t) for t in par]
-        roles = _persist_roles(plan, H, N) if ctx.wpack is not None else None
-        if roles is not None and plan.heavy_segments(True, active_by_level=True) is None:
-            sync, sticky, _ = _persist_ws(dev)
-            stp = (_hip.ctypes.c_int32 * len(plan.slot_tile_ptr))(*plan.slot_tile_ptr)
-            hv = plan.heavy_segments(True, inactive_only=True)
-            slab = workspace(_hip.call_value('mgv_sweep_persist_slab_floats', H, roles[T]), dev)
-            _hip.call('mgv_func_sweep_bwd_persist_x3', H, N, T, plan.num_levels, ptr(plan.key_tile_ptr), roles, stp, ptr(plan.order),
-                      ptr(plan.order_span), ptr(plan.tile_start), ptr(plan.tile_count), ptr(plan.in_ptr), ptr(plan.in_src),
-                      ptr(plan.out_ptr), ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]),
-                      ptr(ctx.wpack), ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc),
-                      *[ptr(g) for g in grads], ptr(slab), slab.numel(), plan.HEAVY_ROW if hv is not None else 0, ptr(sync), ptr(sticky))
-            if hv is not None:
-                pw = workspace(hv['S'] * H, dev)
-                _hip.call('mgv_sweep_pull_heavy', H, hv['K'], ptr(hv['nodes']), ptr(hv['node_seg_ptr']), hv['S'], ptr(hv['seg_e0']), ptr(hv['seg_e1']),
-                          ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(alpha), ptr(dsc), ptr(dzb), ptr(par[0]), ptr(pw), ptr(ghs))
-            return (None, ghs, *grads)
+        grads = [torch.zeros_like(t) for t in par]      # rounds >= 2: the last one (dbhh) is not meaningful
+        d_gh = g_hprev = None
+        if hp is not None:
+            d_gh = torch.zeros(N, 3 * H, dtype=F32, device=dev)      # rows of never-updated nodes stay zero
+            g_hprev = torch.zeros(N, H, dtype=F32, device=dev)       # (their states are constants of round 1: no gradient to carry)
+        rnd = (ptr(ghd), ptr(hp), ptr(d_gh), ptr(g_hprev))
         if ctx.wpack is not None:
             scratch, stp, hv, ha = _sweep_bwd_prep(plan, T, H, dev)
             _hip.call('mgv_func_sweep_bwd_x3', H, N, T, plan.num_levels, ctx.ltp, ptr(plan.order), *_sweep_rows(plan),
@@ -930,20 +811,20 @@ class FuncSweepFn(torch.autograd.Function):
                       ptr(plan.in_ptr), ptr(plan.in_src), ptr(plan.out_ptr), ptr(plan.out_dst), ptr(plan.out_slot),
                       ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]), ptr(ctx.wpack), ptr(par[2]), ptr(par[3]), ptr(par[4]),
                       ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc), *[ptr(g) for g in grads], ptr(scratch),
-                      scratch.numel(), plan.HEAVY_ROW if hv is not None else 0, *ha)
+                      scratch.numel(), plan.HEAVY_ROW if hv is not None else 0, *ha, *rnd)
             if hv is not None:
                 # primary inputs (never updated) that drive thousands of gates: their pull by whole workgroups, per list segment
                 pw = workspace(hv['S'] * H, dev)
                 _hip.call('mgv_sweep_pull_heavy', H, hv['K'], ptr(hv['nodes']), ptr(hv['node_seg_ptr']), hv['S'], ptr(hv['seg_e0']), ptr(hv['seg_e1']),
                           ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(alpha), ptr(dsc), ptr(dzb), ptr(par[0]), ptr(pw), ptr(ghs))
-            return (None, ghs, *grads)
-        WvcT = par[1].transpose(1, 2).contiguous()
-        _hip.call('mgv_func_sweep_bwd', H, N, T, plan.num_levels, ctx.ltp, ptr(plan.order), ptr(plan.tile_start),
-                  ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(plan.out_ptr),
-                  ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]), ptr(par[1]),
-                  ptr(WvcT), ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc),
-                  *[ptr(g) for g in grads])
-        return (None, ghs, *grads)
+        else:
+            WvcT = par[1].transpose(1, 2).contiguous()
+            _hip.call('mgv_func_sweep_bwd', H, N, T, plan.num_levels, ctx.ltp, ptr(plan.order), ptr(plan.tile_start),
+                      ptr(plan.tile_count), ptr(plan.tile_slot), ptr(plan.in_ptr), ptr(plan.in_src), ptr(plan.out_ptr),
+                      ptr(plan.out_dst), ptr(plan.out_slot), ptr(plan.gslot), ptr(hs), ptr(hf), ptr(par[0]), ptr(par[1]),
+                      ptr(WvcT), ptr(par[2]), ptr(par[3]), ptr(par[4]), ptr(ghf), ptr(ghs), ptr(dzb), ptr(alpha), ptr(dsc),
+                      *[ptr(g) for g in grads], *rnd)
+        return (None, ghs, *grads[:4], grads[4] if hp is None else None, g_hprev, d_gh)
 
 
 # ------------------------------------------------------------------------------------------------

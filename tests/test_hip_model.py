@@ -162,7 +162,7 @@ def test_functional_level_op_vs_reference_fixture():
     ltp = (_hip.ctypes.c_int32 * len(plan.level_tile_ptr))(*plan.level_tile_ptr)
     P = _hip.ptr
     _hip.call('mgv_func_sweep_fwd', H, N, 1, plan.num_levels, ltp, P(plan.order), P(plan.tile_start), P(plan.tile_count),
-              P(plan.tile_slot), P(plan.in_ptr), P(plan.in_src), P(hs), P(hf), *[P(t) for t in par])
+              P(plan.tile_slot), P(plan.in_ptr), P(plan.in_src), P(hs), P(hf), *[P(t) for t in par], None, None)
     close(hf[torch.tensor(nodes, device=dev)], z['lvl0_hnew'], msg='hf of the level')
     # backward: upstream gradient on the level's rows
     ghf = torch.zeros(N, H, device=dev)
@@ -175,7 +175,7 @@ def test_functional_level_op_vs_reference_fixture():
     _hip.call('mgv_func_sweep_bwd', H, N, 1, plan.num_levels, ltp, P(plan.order), P(plan.tile_start), P(plan.tile_count),
               P(plan.tile_slot), P(plan.in_ptr), P(plan.in_src), P(plan.out_ptr), P(plan.out_dst), P(plan.out_slot),
               P(plan.gslot), P(hs), P(hf), P(par[0]), P(par[1]), P(WvcT), P(par[2]), P(par[3]), P(par[4]), P(ghf), P(ghs),
-              P(dzb), P(alpha), P(dsc), *[P(g) for g in grads])
+              P(dzb), P(alpha), P(dsc), *[P(g) for g in grads], None, None, None, None)
     close(ghs, z['lvl0_grad_node_state'][:, :H], msg='grad hs')
     # the gradient wrt the sources' hf is what their own tiles would pull: rebuild it on the host
     al, ds = alpha.cpu().numpy(), dsc.cpu().numpy()

@@ -77,7 +77,7 @@ def _model(ctype, H, rounds, seed=9):
 @pytest.mark.parametrize('H,ctype,rounds,precision', [(64, 'aig', 2, 'x3'), (32, 'xmg', 2, 'x3'), (64, 'mig', 3, 'x3'),
                                                       (16, 'mig', 2, 'x3'), (64, 'xag', 2, 'f32')])
 def test_two_round_model_against_the_oracle(H, ctype, rounds, precision):
-    """(H = 16 and precision f32: the exact-fp32 level kernels' hidden-state variants, mgv_func_sweep_round_fwd / _bwd)"""
+    """(H = 16 and precision f32: the exact-fp32 level kernels with the previous round's states, mgv_func_sweep_fwd / _bwd with gh, h_prev)"""
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     from deepgate import ops, synthetic as syn
