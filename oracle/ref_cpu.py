@@ -234,12 +234,16 @@ def sweep_fast(p, ctype, hs, plan):
     return _SweepFast.apply(hs, plan, names, *[p[k] for k in names])
 
 
-def readout_prob(p, hf, training, bn_state=None, p_drop=0.0, momentum=0.1, decisions=None):
+def readout_prob(p, hf, training, bn_state=None, p_drop=0.0, momentum=0.1, decisions=None, drop=None, taken=None):
     """pred_prob (dg_ae_model_aig.py:102-106) over MLP 64-32-32-1 with BatchNorm1d/ReLU/Dropout
     (mlp.py:27-47).  `bn_state` holds the running statistics (updated in place when training).
     `decisions` (checker aid, not in the reference): {'relu': [mask1, mask2], 'inside': mask} — the piecewise-linear branches another
     run took (which ReLUs passed, which outputs the clamp left alone), imposed here instead of decided here, so that two runs whose
-    pre-activations differ by rounding are compared on the SAME linear piece."""
+    pre-activations differ by rounding are compared on the SAME linear piece.
+    `drop` (checker aid): [factors1, factors2], the per-element dropout factors (0 or 1/(1-p), e.g. from `drop_factors`) that stand
+    in for `F.dropout` in training mode, so that a run can be held to the device's counter-based masks.
+    `taken` (checker aid, out-parameter): a dict that receives what THIS run decided on its own, whatever `decisions` imposes:
+    'relu' = [bn_out1 > 0, bn_out2 > 0] and 'pre_clamp' = the head's output in front of the clamp."""
     name = 'readout_prob.fc'
     y = hf
     for blk, (lin, bn) in enumerate(((0, 1), (4, 5))):
@@ -248,12 +252,57 @@ def readout_prob(p, hf, training, bn_state=None, p_drop=0.0, momentum=0.1, decis
         rv = p['%s.%d.running_var' % (name, bn)] if bn_state is None else bn_state['%s.%d.running_var' % (name, bn)]
         y = F.batch_norm(y, rm, rv, p['%s.%d.weight' % (name, bn)], p['%s.%d.bias' % (name, bn)],
                          training=training, momentum=momentum, eps=1e-5)
+        if taken is not None:
+            taken.setdefault('relu', []).append(y.detach() > 0)
         y = F.relu(y) if decisions is None else y * decisions['relu'][blk].to(y.dtype)
-        y = F.dropout(y, p_drop, training=training)
+        if drop is not None and training:
+            y = y * drop[blk].to(y.dtype)
+        else:
+            y = F.dropout(y, p_drop, training=training)
     y = linear(p, name + '.8', y)
+    if taken is not None:
+        taken['pre_clamp'] = y.detach()
     if decisions is not None:
         return torch.where(decisions['inside'], y, torch.clamp(y, min=0.0, max=1.0).detach())
     return torch.clamp(y, min=0.0, max=1.0)
+
+
+_M64 = (1 << 64) - 1
+
+
+def drop_hash_scalar(seed, elem):
+    """The upper 24 bits of `mgv::hash_u32(seed + 0x9E3779B97F4A7C15 * (elem + 1))` (csrc/mgv_dropout.h) for ONE element, in plain
+    Python integers reduced mod 2^64: the slow restatement the vectorised `drop_factors` is checked against."""
+    x = (seed + 0x9E3779B97F4A7C15 * (elem + 1)) & _M64
+    x ^= x >> 33
+    x = (x * 0xff51afd7ed558ccd) & _M64
+    x ^= x >> 33
+    x = (x * 0xc4ceb9fe1a85ec53) & _M64
+    x ^= x >> 33
+    return (x & 0xFFFFFFFF) >> 8
+
+
+def drop_factors(seed, n_rows, C, p):
+    """The dropout factors of the HIP readout as a specification (`mgv::drop_scale`, csrc/mgv_dropout.h), restated on the CPU:
+    a float64 [n_rows, C] tensor of 0 or 1/(1-p).  Element (row, col) has number row * C + col; its 64-bit wrap-around hash of
+    (seed, number) gives u = (upper 24 bits of the low 32) / 2^24, and the element is dropped when u < p, with p rounded to float32
+    as the kernels receive it (u is exact in float32, so the comparison is exact here too).  p <= 0: all ones.
+    Layer k of one readout step uses seed + 7919 * k (arch/mlp.py)."""
+    import numpy as np
+    p32 = np.float32(p)
+    if not p32 > 0:
+        return torch.ones(n_rows, C, dtype=torch.float64)
+    x = np.arange(1, n_rows * C + 1, dtype=np.uint64)          # uint64 ARRAY arithmetic wraps mod 2^64 (elem + 1)
+    x *= np.uint64(0x9E3779B97F4A7C15)
+    x += np.uint64(int(seed) & _M64)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xff51afd7ed558ccd)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xc4ceb9fe1a85ec53)
+    x ^= x >> np.uint64(33)
+    u = ((x & np.uint64(0xFFFFFFFF)) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    keep = ~(u < p32)
+    return torch.from_numpy(keep.reshape(n_rows, C).astype(np.float64)) * (1.0 / (1.0 - float(p32)))
 
 
 def decoder(s, t, edge_index, sigmoid=True):
@@ -289,13 +338,13 @@ def func_loss(hf, tt_pair_index, tt_sim):
 
 
 def run_batch(p, ctype, batch, training=True, bn_state=None, p_drop=0.0, s_rounds=4, t_rounds=4,
-              layernorm=True, num_rounds=1, plan=None, fast=False, decisions=None):
+              layernorm=True, num_rounds=1, plan=None, fast=False, decisions=None, drop=None, taken=None):
     """Trainer.run_batch (trainer.py:131-174).  The edge split keeps only its live effect — a
     permutation of the edges, to which the mean over edges is invariant — and never builds the dead
     N x N mask (preprocessing.py:56-69)."""
     hs, hf, s, t = model_forward(p, ctype, batch, s_rounds, t_rounds, layernorm, num_rounds, plan, fast)
     rl, pred_bin, gt_bin = recon_loss(p, hs, batch['edge_index'], batch['neg_edge_index'])
-    prob = readout_prob(p, hf, training, bn_state, p_drop, decisions=decisions)
+    prob = readout_prob(p, hf, training, bn_state, p_drop, decisions=decisions, drop=drop, taken=taken)
     # (`decisions`: see readout_prob; 'sign' = the L1 loss's branch per node, imposed)
     pl = F.l1_loss(prob, batch['prob']) if decisions is None else (decisions['sign'].to(prob.dtype) * (prob - batch['prob'].to(prob.dtype))).mean()
     fl, _ = func_loss(hf, batch['tt_pair_index'], batch['tt_sim'])

@@ -247,7 +247,30 @@ def test_dropout_mask_statistics_and_backward_consistency():
     assert abs(kept - 0.8) < 0.01, kept
     a2 = ops.BnReluDropFn.apply(y, g, b, rm.clone(), rv.clone(), True, 0.2, 1234, 0.1, 1e-5)
     assert torch.equal(a, a2)                       # same seed, same mask
-    a.sum().backward()                              # gradient flows only through kept elements
+    a.sum().backward(retain_graph=True)             # gradient flows only through kept elements
+    # ... which the backward has to find again from (seed, element): with bn_out > 0 everywhere, dz = upstream x factor, factor 0
+    # where the forward dropped and 1/(1-p) where it kept, and dy is the BatchNorm backward of that dz.  Held to float64 autograd
+    # through batch_norm x the forward's own factors (1e-5 of scale: an element-wise fp32 kernel with double column sums).
+    fac = (a.detach() != 0).double().cpu() / (1.0 - float(np.float32(0.2)))
+    y64 = y.detach().cpu().double().requires_grad_(True)
+    g64, b64 = g.cpu().double().requires_grad_(True), b.cpu().double().requires_grad_(True)
+    (torch.nn.functional.batch_norm(y64, None, None, g64, b64, training=True, eps=1e-5) * fac).sum().backward()
+    err = float((y.grad.cpu().double() - y64.grad).abs().max()) / float(y64.grad.abs().max())
+    assert err <= 1e-5, err
+    # one unit at a time: a dropped unit passes nothing back, a kept one 1/(1-p) times the BatchNorm backward of the one-hot
+    bn0 = torch.nn.functional.batch_norm(y64, None, None, g64, b64, training=True, eps=1e-5)
+    keep = a.detach() != 0
+    for want_kept in (False, True):
+        i, c = [int(v) for v in torch.nonzero(keep == want_kept)[1234].tolist()]
+        up = torch.zeros(N, C)
+        up[i, c] = 1.0
+        dy, = torch.autograd.grad(a, y, up.to(dev), retain_graph=True)
+        if not want_kept:
+            assert float(dy.abs().max()) == 0.0
+            continue
+        ref, = torch.autograd.grad(bn0, y64, up.double(), retain_graph=True)
+        ref = ref / (1.0 - float(np.float32(0.2)))
+        assert float((dy.cpu().double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
 
 
 def test_func_loss_decoder_and_confusion_vs_reference_fixture():
