@@ -306,6 +306,25 @@ int mgv_recon_loss_bwd_csr(int H, int64_t N, const float* s, const float* t, int
 int mgv_recon_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, const float* gscale, int K,
                           const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node, const int32_t* seg_e0,
                           const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws, float* out, void* stream);
+/* ---- link-prediction ranking metrics (digvae_model.py:177-189, digae_model.py:156-168: `test` decodes both edge sets with
+ * sigmoid=True, copies every score to the host and calls sklearn's roc_auc_score / average_precision_score).  Here the ranking stays
+ * on the device (csrc/link_metrics.hip): keys -> mgv_sort_pairs(4, n, keys, sorted, order, 32, ...) -> rank.
+ * link_keys: keys[P + Q] = the decoder's score sigmoid(<s[u], t[v]>) of every pair (positives first; the arithmetic of
+ * mgv_edge_dot_fwd) as a 32-bit key whose ASCENDING unsigned order is the DESCENDING score order; scores[P + Q] (nullable): the
+ * scores themselves; status[0] += number of NaN scores.  P == 0 or Q == 0: MGV_EINVAL; P + Q >= 2^31: MGV_EUNSUPPORTED. */
+int mgv_link_keys(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst, int64_t P,
+                  const int64_t* neg_src, const int64_t* neg_dst, int64_t Q, uint32_t* keys, float* scores, int32_t* status,
+                  void* stream);
+/* link_rank: sorted_keys / order as mgv_sort_pairs left them (element i is a positive iff order[i] < P; both 16-byte aligned).
+ * Tie group = maximal run of equal keys; per group g, highest score first: p_g / q_g its positives / negatives, TP_g / FP_g
+ * the counts through g.  out (six 8-byte words, written, not added to):
+ *   out[0] double AUC = U2 / (2 P Q),  U2 = sum_g p_g (2 (Q - FP_g) + q_g)   (mid-rank Mann-Whitney, an integer)
+ *   out[1] double AP  = sum_g p_g TP_g / (TP_g + FP_g) / P                    (sklearn's step-wise definition)
+ *   out[2..5] uint64 U2, P, Q, number of tie groups.
+ * Deterministic (no float atomics).  work: 8-byte aligned, work_ints >= mgv_link_rank_work_ints(n) (-1: n out of range). */
+int mgv_link_rank_work_ints(int64_t n);                                                              /* a size in 4-byte units */
+int mgv_link_rank(int64_t n, int64_t P, const uint32_t* sorted_keys, const int32_t* order, double* out, int32_t* work,
+                  int64_t work_ints, void* stream);
 /* negative sampling of the reconstruction loss (dg_ae_model_aig.py:115-119, torch_geometric negative_sampling): E pairs
  * uniform over {(u, v): u != v, (u, v) not an edge of the CSR}, from a counter-based generator (seed); cnt_out/cnt_in
  * [N] (zeroed by the caller) receive the pairs' per-source / per-destination counts, rank_out/rank_in [E] each pair's place inside

@@ -37,4 +37,6 @@ def get_parse_args(argv=None):
     parser.add_argument('--stage_epochs', type=int, nargs=3, default=[100, 60, 60],
                         help='epochs of the three training stages (train.py:81-85)')
     parser.add_argument('--save_dir', type=str, default='./exp')
+    parser.add_argument('--val_auc', action='store_true', help='validation phase: also rank every batch\'s positive edges against its '
+                        'sampled negatives on the device and log the mean ROC-AUC and average precision (digvae_model.py:177-189)')
     return parser.parse_args(argv)

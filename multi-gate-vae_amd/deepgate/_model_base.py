@@ -42,6 +42,7 @@ class FunctionalModel(nn.Module):
         self.readout_prob = MLP(dim_hidden, self.dim_mlp, 1, num_layer=3, p_drop=0.2, norm_layer='batchnorm',
                                 act_layer='relu')
         self.last_confusion = None
+        self.last_link_metrics = None
 
     # ---- forward ---------------------------------------------------------------------------------
     def _sweep_params(self):
@@ -101,10 +102,32 @@ class FunctionalModel(nn.Module):
     def pred_prob(self, hf, seed=None):
         return self.readout_prob(hf, clamp01=True, seed=seed)
 
-    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False):
+    def _draw_negatives(self, hs, pos_edge_index, plan, edge_keys=None):
+        """Negative pairs as recon_loss draws them: with the batch's plan the fused device sampler (pairs bucketed for an atomic-free
+        backward), else the torch rejection sampler."""
+        if plan is not None and hs.is_cuda and hs.shape[0] >= 2 and DEVICE_SAMPLER:
+            return negative_sampling_device(plan)
+        return negative_sampling(pos_edge_index, hs.shape[0], keys=edge_keys)
+
+    def link_metrics(self, hs, pos_edge_index, neg_edge_index=None, plan=None):
+        """ROC-AUC and average precision of the decoder on st = hs_decompose(hs): `pos_edge_index` ranked against `neg_edge_index`
+        (drawn as recon_loss draws them when None).  Added functionality: the reference's DG_AE Models have no such method, only
+        DirectedGAE / DirectedGVAE.test (digvae_model.py:177-189), whose definition of the two numbers this follows.  Returns the
+        device record of ops.link_record (float64[8]: AUC, AP, then the integer words) without a host synchronisation; `.tolist()`
+        or ops.read_link_records is the caller's."""
+        with torch.no_grad():
+            st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
+            if plan is not None and (plan.E != pos_edge_index.shape[1] or plan.N != hs.shape[0]):
+                plan = None
+            if neg_edge_index is None:
+                neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan)
+            return ops.link_record(st, None, pos_edge_index, neg_edge_index)
+
+    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the
-        hs_decompose node, in `self._hs_pass` for the level sweep (see forward)."""
+        hs_decompose node, in `self._hs_pass` for the level sweep (see forward).  `want_rank`: also rank the very pairs the loss
+        uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`."""
         if pass_hs and hs.requires_grad:
             st, self._hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         else:
@@ -114,8 +137,7 @@ class FunctionalModel(nn.Module):
         neg_csr = None
         if neg_edge_index is None:
             # with the batch's plan: fused device sampler, pairs bucketed for an atomic-free backward
-            neg_edge_index = negative_sampling_device(plan) if plan is not None and hs.is_cuda and hs.shape[0] >= 2 and DEVICE_SAMPLER \
-                else negative_sampling(pos_edge_index, hs.shape[0], keys=edge_keys)
+            neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan, edge_keys)
         if plan is not None and hs.is_cuda and torch.is_tensor(neg_edge_index) and neg_edge_index.shape[1] > 0:
             # given negatives: bucket them once (cached on the tensor's identity) so that their gradient needs no atomics either
             # kept on the batch's plan (like its pair lists), not on the model: several batches with fixed negatives each keep theirs
@@ -129,6 +151,7 @@ class FunctionalModel(nn.Module):
             neg_csr, neg_edge_index = neg_edge_index.csr, neg_edge_index.edge_index
         loss, counts, pred_bin = ops.ReconLossFn.apply(st, pos_edge_index, neg_edge_index, want_pred, plan, neg_csr)
         self.last_confusion = counts        # {TP, FP, TN, FN} on device, no host copy needed for metrics
+        self.last_link_metrics = ops.link_record(st, None, pos_edge_index, neg_edge_index) if want_rank else None
         Ep, En = pos_edge_index.shape[1], neg_edge_index.shape[1]
         gt_bin = None
         if want_pred:

@@ -66,3 +66,10 @@ class DirectedGVAE(torch.nn.Module):
         gt_bin = torch.zeros(Ep + En, dtype=torch.int32, device=s.device)
         gt_bin[:Ep] = 1
         return loss, pred_bin, gt_bin
+
+    def test(self, s, t, pos_edge_index, neg_edge_index):
+        """(ROC-AUC, average precision) of the decoder's scores of `pos_edge_index` against `neg_edge_index` on s, t as given
+        (digvae_model.py:177-189; nothing is sampled).  The reference copies every score to the host for sklearn; here the scores are
+        ranked on the device (ops.link_record) and one 64-byte record is read.  ValueError like sklearn's when one of the two sets is
+        empty or a score is NaN."""
+        return ops.read_link_records([ops.link_record(s, t, pos_edge_index, neg_edge_index)])[0]

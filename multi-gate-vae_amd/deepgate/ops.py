@@ -946,6 +946,84 @@ def confusion_counts(pred_bin, gt_bin):
 
 
 # ------------------------------------------------------------------------------------------------
+# link-prediction ranking metrics (digvae_model.py:177-189: decode, copy to the host, sklearn)
+# ------------------------------------------------------------------------------------------------
+LINK_RECORD_WORDS = 8       # AUC, AP (float64) | U2, P, Q, tie groups, NaN scores (int64) | spare
+
+
+def link_record(st_or_s, t=None, pos_edge_index=None, neg_edge_index=None, return_scores=False):
+    """One ranking of P positive against Q negative pairs, entirely on the device and without a host synchronisation
+    (csrc/link_metrics.hip: score keys -> radix sort -> two streaming passes).  Returns the 64-byte record the kernels wrote, a
+    float64[8] tensor: words 0-1 AUC and AP, words 2-6 (read through `.view(torch.int64)`) U2, P, Q, the number of tie groups and
+    the number of NaN scores (non-zero: the metrics mean nothing), word 7 unused; with `return_scores` also the fp32 scores that
+    were ranked, positives first.  `st_or_s`: the [N, 2H] `st` layout of recon_loss (t=None) or s [N, H] with t [N, H].
+    `neg_edge_index`: a [2, Q] tensor or a sampling.NegativeEdges.  No autograd: the metrics are piecewise constant."""
+    neg = getattr(neg_edge_index, 'edge_index', neg_edge_index)
+    P, Q = int(pos_edge_index.shape[1]), int(neg.shape[1])
+    if P == 0 or Q == 0:
+        # sklearn's behaviour for y_true with one class; both sizes are host values: nothing is launched
+        raise ValueError('Only one class present (%d positive, %d negative pairs): ROC-AUC and average precision are not defined' % (P, Q))
+    sd = check(st_or_s.detach().contiguous(), F32, 'st' if t is None else 's')
+    if t is None:
+        ld = sd.shape[1]
+        H = ld // 2
+        td = sd[:, H:]
+    else:
+        td = check(t.detach().contiguous(), F32, 't')
+        ld = H = sd.shape[1]
+        if td.shape != sd.shape:
+            raise HipLibraryError('s and t must have the same shape (got %s and %s)' % (tuple(sd.shape), tuple(td.shape)))
+    n = P + Q
+    if n >= 1 << 31:
+        raise HipLibraryError('mgv_link_keys failed: %s (%d pairs; the ranking holds fewer than 2^31)' % (_hip._ERR[-2], n))
+    ps, pd = _edge_rows(pos_edge_index)
+    ns, nd = _edge_rows(neg)
+    for name, e in (('pos_edge_index', ps), ('neg_edge_index', ns)):
+        if not e.is_cuda:
+            raise HipLibraryError('%s must live on the GPU (got %s)' % (name, e.device))
+    dev = sd.device
+    rec = torch.zeros(LINK_RECORD_WORDS, dtype=torch.float64, device=dev)
+    status = rec.view(I32)[12:13]                      # low half of int64 word 6
+    buf = torch.empty(3, n + (-n) % 4, dtype=I32, device=dev)      # keys, sorted keys, permutation: each on a 16-byte boundary
+    keys, skey, order = buf[0, :n], buf[1, :n], buf[2, :n]
+    scores = torch.empty(n, dtype=F32, device=dev) if return_scores else None
+    _hip.call('mgv_link_keys', H, ptr(sd), ptr(td), ld, ptr(ps), ptr(pd), P, ptr(ns), ptr(nd), Q, ptr(keys), ptr(scores), ptr(status))
+    t_i = _hip.call_value('mgv_sort_pairs_temp_ints', 4, n)
+    w_i = _hip.call_value('mgv_link_rank_work_ints', n)
+    if t_i < 0 or w_i < 0:
+        raise HipLibraryError('link metrics: no workspace size for %d pairs' % n)
+    temp = torch.empty(t_i + w_i + 2, dtype=I32, device=dev)
+    _hip.call('mgv_sort_pairs', 4, n, ptr(keys), ptr(skey), ptr(order), 32, ptr(temp), t_i)
+    work = temp[t_i + (t_i & 1):]                      # 8-byte aligned
+    _hip.call('mgv_link_rank', n, P, ptr(skey), ptr(order), ptr(rec), ptr(work), work.numel())
+    return (rec, scores) if return_scores else rec
+
+
+def link_auc_ap(st_or_s, t=None, pos_edge_index=None, neg_edge_index=None, return_scores=False):
+    """(metrics, status[, scores, counts]): `metrics` float64[2] = (AUC, AP) and `status` int64[1] = the number of NaN scores, both
+    on the device and both views of one link_record (no host synchronisation; a non-zero status means a NaN was ranked and the
+    metrics are void).  `return_scores`: also the ranked fp32 scores (positives first) and counts int64[4] = U2, P, Q, tie groups."""
+    out = link_record(st_or_s, t, pos_edge_index, neg_edge_index, return_scores)
+    rec = out[0] if return_scores else out
+    words = rec.view(torch.int64)
+    if return_scores:
+        return rec[:2], words[6:7], out[1], words[2:6]
+    return rec[:2], words[6:7]
+
+
+def read_link_records(records):
+    """[(auc, ap), ...] of link_record tensors as Python floats: ONE host read for all of them; ValueError if any ranked a NaN
+    (sklearn: "Input contains NaN")."""
+    if not records:
+        return []
+    host = torch.stack(list(records)).cpu()
+    bad = host.view(torch.int64)[:, 6]
+    if bool((bad != 0).any()):
+        raise ValueError('Input contains NaN: %d of the ranked scores are NaN' % int(bad.sum()))
+    return [(float(r[0]), float(r[1])) for r in host]
+
+
+# ------------------------------------------------------------------------------------------------
 # losses on node rows
 # ------------------------------------------------------------------------------------------------
 class L1LossFn(torch.autograd.Function):

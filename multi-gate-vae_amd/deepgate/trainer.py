@@ -62,6 +62,9 @@ class GraphLoader:
 
 
 class Trainer():
+    # the phase line of the reference's log (trainer.py:259-262); --val_auc appends ' |AUC: x.xxxx |AP: x.xxxx' to the val line
+    LOG_LINE = '{}| Epoch: {:}/{:} |Recon: {:.4f} |ACC: {:.2f} |Prob: {:.4f} |Func: {:.4f}|Net: {:.2f}s'
+
     def __init__(self, args, model, training_id='default', save_dir='./exp', lr=1e-4,
                  rc_prob_func_weight=[1.0, 4.0, 2.0], emb_dim=128, device='cpu', batch_size=32, num_workers=0,
                  distributed=True):
@@ -156,10 +159,11 @@ class Trainer():
             return True
         return False
 
-    def run_batch(self, batch, want_pred=True):
+    def run_batch(self, batch, want_pred=True, want_rank=False):
         """Forward + the three losses (trainer.py:131-174).  `general_train_test_split_edges` with zero
         val/test ratios only permutes the edges (preprocessing.py:41-50), to which the mean over edges is
-        invariant: train_pos_edge_index is the batch's edge_index."""
+        invariant: train_pos_edge_index is the batch's edge_index.  `want_rank`: also rank the loss's own pairs on the device
+        (ROC-AUC / average precision, ops.link_record); the record is returned under 'link_metrics'."""
         batch.train_pos_edge_index = batch.edge_index
         neg = getattr(batch, 'neg_edge_index', None)
         dev_is_cuda = next(self.model.parameters()).is_cuda
@@ -175,7 +179,8 @@ class Trainer():
                 if k is None:
                     k = batch._mgv_edge_keys = sorted_edge_keys(batch.edge_index, batch.num_nodes)
             return self.model.recon_loss(hs, batch.train_pos_edge_index, neg, want_pred=want_pred, edge_keys=k,
-                                         plan=getattr(batch, '_mgv_plan', None), **({'pass_hs': True} if pass_hs else {}))
+                                         plan=getattr(batch, '_mgv_plan', None), **({'pass_hs': True} if pass_hs else {}),
+                                         **({'want_rank': True} if want_rank else {}))
 
         def recon_on_side(hs):
             # reconstruction branch (hs_decompose -> decoder loss) on a second HIP stream, recorded BEFORE the level sweep: it
@@ -192,7 +197,7 @@ class Trainer():
             self.model.after_hs_out = None          # the model must not keep this step's loss graph alive
             main = torch.cuda.current_stream()
             main.wait_stream(side)
-            for t in (loss, pred_bin, gt_bin, self.model.last_confusion):
+            for t in (loss, pred_bin, gt_bin, self.model.last_confusion, self.model.last_link_metrics if want_rank else None):
                 if t is not None:
                     t.record_stream(main)
         else:
@@ -208,6 +213,8 @@ class Trainer():
         prob = self.model.pred_prob(hf_r)
         loss_status['prob_loss'] = self.reg_loss(prob, batch['prob'])
         loss_status['confusion'] = self.model.last_confusion
+        if want_rank:
+            loss_status['link_metrics'] = self.model.last_link_metrics
         return loss_status
 
     def _encoder_half_rounds(self):
@@ -293,8 +300,11 @@ class Trainer():
                             (vals[0], vals[1], vals[2], tp + tn, tp, fp, tn, fn)):
                 stats[k].update(v)
 
+        val_auc = bool(getattr(self.args, 'val_auc', False))
         for epoch in range(num_epoch):
             for phase in ['train', 'val']:
+                rank = val_auc and phase == 'val'
+                records = []             # per-batch link records of the phase, on the device until the phase ends
                 loader = train_loader if phase == 'train' else val_loader
                 self.model.train() if phase == 'train' else self.model.eval()
                 # collate, host-to-device copy and plan build of the next batches run on worker threads / their own HIP streams
@@ -308,7 +318,9 @@ class Trainer():
                             loss_status = self.train_step(batch)
                         else:
                             with torch.no_grad():
-                                loss_status = self.run_batch(batch, want_pred=False)
+                                loss_status = self.run_batch(batch, want_pred=False, **({'want_rank': True} if rank else {}))
+                            if rank:
+                                records.append(loss_status['link_metrics'])
                         # one small device->host copy per step (3 losses + 4 counters), read one step behind so that the host
                         # never waits for the step it has just enqueued
                         account(self.enqueue_metrics(loss_status))
@@ -319,10 +331,15 @@ class Trainer():
                 if phase == 'train' and self.model_epoch % 10 == 0 and self.rank == 0:
                     self.save(os.path.join(self.log_dir, 'model_{:}.pth'.format(self.model_epoch)))
                     self.save(os.path.join(self.log_dir, 'model_last.pth'))
+                rank_cols = ''
+                if rank:
+                    # one host read for the whole phase; raises if a batch ranked a NaN score
+                    pairs = ops.read_link_records(records)
+                    if pairs:
+                        rank_cols = ' |AUC: {:.4f} |AP: {:.4f}'.format(sum(a for a, _ in pairs) / len(pairs), sum(b for _, b in pairs) / len(pairs))
                 if self.local_rank == 0:
-                    line = '{}| Epoch: {:}/{:} |Recon: {:.4f} |ACC: {:.2f} |Prob: {:.4f} |Func: {:.4f}|Net: {:.2f}s\n'.format(
-                        phase, epoch, num_epoch, stats['recon'].avg, stats['acc'].avg * 100, stats['prob'].avg,
-                        stats['func'].avg, batch_time.avg)
+                    line = self.LOG_LINE.format(phase, epoch, num_epoch, stats['recon'].avg, stats['acc'].avg * 100, stats['prob'].avg,
+                                                stats['func'].avg, batch_time.avg) + rank_cols + '\n'
                     self.logger.write(line)
                     print(line, end='')
             self.model_epoch += 1

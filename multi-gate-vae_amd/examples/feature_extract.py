@@ -4,6 +4,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
 
     python examples/feature_extract.py --type aig --data_dir DIR [--checkpoint exp/e/stage_3.pth] --out emb.npz
     python examples/feature_extract.py --type aig --synthetic 4 --out emb.npz
+    python examples/feature_extract.py --type aig --synthetic 4 --link_metrics      # + ROC-AUC / AP of the decoder per batch
 """
 import argparse
 import os
@@ -28,6 +29,8 @@ def main(argv=None):
     ap.add_argument('--rounds', type=int, default=4)
     ap.add_argument('--batch_size', type=int, default=8)
     ap.add_argument('--out', default='embeddings.npz')
+    ap.add_argument('--link_metrics', action='store_true', help='also print ROC-AUC / average precision of the decoder: every batch\'s '
+                    'edges ranked against sampled non-edges (Model.link_metrics)')
     a = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
@@ -42,12 +45,14 @@ def main(argv=None):
         train, val = deepgate.NpzParser(a.data_dir, os.path.join(a.data_dir, 'graphs.npz'), os.path.join(a.data_dir, 'labels.npz'),
                                         a.type, random_shuffle=False, trainval_split=1.0).get_dataset()
         graphs = train + val
-    out, t0 = {}, time.time()
+    out, t0, records = {}, time.time(), []
     with torch.no_grad():
         for b0 in range(0, len(graphs), a.batch_size):
             chunk = graphs[b0:b0 + a.batch_size]
             batch = deepgate.CircuitBatch.from_arrays(synthetic.collate(chunk), device=dev)
             hs, hf = model(batch)
+            if a.link_metrics:
+                records.append(model.link_metrics(hs, batch.edge_index, plan=getattr(batch, '_mgv_plan', None)))
             ptr = batch.graph_ptr.tolist()
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
@@ -56,6 +61,10 @@ def main(argv=None):
     torch.cuda.synchronize()
     np.savez(a.out, **out)
     print('[INFO] %d graphs embedded in %.2f s -> %s' % (len(graphs), time.time() - t0, a.out))
+    if a.link_metrics:
+        pairs = deepgate.ops.read_link_records(records)          # one host read for all batches
+        print('[INFO] link prediction over %d batches: AUC %.4f, AP %.4f' % (len(pairs), sum(x for x, _ in pairs) / len(pairs),
+                                                                             sum(y for _, y in pairs) / len(pairs)))
 
 
 if __name__ == '__main__':
