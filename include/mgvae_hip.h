@@ -288,7 +288,8 @@ int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int6
 /* ds/dt += dL/ds, dL/dt for loss = sums[0]/Epos + sums[1]/Eneg scaled by the DEVICE scalar *gscale.
  * When the positive edges are the batch graph's own edges pass its two int32 CSRs (pos_out_* by
  * source, pos_in_* by destination): the positive half then runs as gathers without atomics;
- * NULL CSRs = arbitrary positive list, float atomics (one whole row per wave-instruction). */
+ * NULL CSRs = arbitrary positive list, float atomics (one whole row per wave-instruction).
+ * H in {16, 32, 64} (the atomic rows take one float per lane); any other H returns MGV_EUNSUPPORTED with ds / dt untouched. */
 int mgv_recon_loss_bwd(int H, int64_t N, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,
                        int64_t Epos, const int32_t* pos_out_ptr, const int32_t* pos_out_dst, const int32_t* pos_in_ptr,
                        const int32_t* pos_in_src, const int64_t* neg_src, const int64_t* neg_dst, int64_t Eneg,

@@ -542,6 +542,7 @@ extern "C" int mgv_recon_loss_bwd(int H, int64_t N, const float* s, const float*
     MGV_CHECK_ARG((Epos == 0 || (pos_src && pos_dst)) && (Eneg == 0 || (neg_src && neg_dst)));
     const bool pull = pos_out_ptr != nullptr;
     MGV_CHECK_ARG(!pull || (pos_in_ptr && (Epos == 0 || (pos_out_dst && pos_in_src))));
+    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;      // the atomic rows need one float per lane: refused before anything is launched
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (Epos > 0 && pull) {
         MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull<HH>), dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
