@@ -492,6 +492,32 @@ int mgv_seg_level_scan(int64_t G, const int32_t* counts, int seg, int32_t* work,
 int mgv_seg_level_fill(int64_t G, int64_t n_seg, const int32_t* gid, int seg, int base, const int32_t* work, int32_t* seg_ptr, int32_t* out_row,
                        int32_t* gid_next, int32_t* counts_next, void* stream);
 
+/* ---- DiGAE baseline layer, DirectedGCNConv (digae_layer.py:73-114; csrc/digcn_conv.hip).  The lists L(i) a node sums over arrive as a
+ * CSR (GraphPlan.csr(reverse): the in-CSR for edge_index as given, the out-CSR for torch.flip(edge_index, [0]), :131,146); with
+ * self_loops != 0 every node also sits once in its own list (add_self_loops, :94), without being stored in the CSR.
+ * scales (:98-105): r[i] = din(i)^-alpha with din = list length (+1), c[j] = dout(j)^-beta with dout = the opposite CSR's row length (+1);
+ * exact for an exponent of 0, 0 for a degree of 0. */
+int mgv_digcn_scales(int64_t N, const int32_t* list_ptr, const int32_t* opp_ptr, float alpha, float beta, int self_loops,
+                     float* r, float* c, void* stream);
+/* the propagate of :107-114 in exact fp32: out[i] = act(outer[i] * (sum_{j in L(i)} inner[j] y[j] [+ inner[i] y[i]])), H in {16,32,64,128},
+ * act = ReLU when relu != 0 (F.relu of :127,146).  Forward: outer = r, inner = c.  Backward (the pull that replaces autograd's scatter):
+ * the opposite CSR with outer = c, inner = r and mask = the forward's output z[N][H] when it went through the ReLU (a term's columns count
+ * where mask[j] > 0; NULL: no mask).  heavy_nodes[heavy_n]: every node whose list is longer than 64 (GraphPlan.heavy), summed by one
+ * workgroup each (0 / NULL: every list by its own lane group).  out must not alias y. */
+int mgv_digcn_gather(int H, int64_t N, const float* y, const int32_t* nbr_ptr, const int32_t* nbr_idx, const float* outer,
+                     const float* inner, const float* mask, int self_loops, int relu, int heavy_n, const int32_t* heavy_nodes,
+                     float* out, void* stream);
+/* first layer on at most 8 distinct feature rows (xcls[N] = row id, T[C][H] = rows W^T + b formed in weight space): the same sum reading
+ * one byte per neighbour, out[i] = act(r[i] * sum_k w_i[k] T[k]) with w_i[k] = sum of c[j] over the list entries of class k.
+ * bwd: dT[C][H] += sum_i w_i[k] r[i] [z[i] > 0] dz[i] (z NULL: no ReLU) through workspace rows added in index order
+ * (>= mgv_digcn_class_bwd_ws_floats(H, N) floats): no float atomics. */
+int mgv_digcn_class_fwd(int H, int64_t N, const uint8_t* xcls, const float* T, int C, const int32_t* nbr_ptr, const int32_t* nbr_idx,
+                        const float* outer, const float* inner, int self_loops, int relu, float* out, void* stream);
+int mgv_digcn_class_bwd_ws_floats(int H, int64_t N);                                                /* a size */
+int mgv_digcn_class_bwd(int H, int64_t N, const uint8_t* xcls, int C, const int32_t* nbr_ptr, const int32_t* nbr_idx, const float* outer,
+                        const float* inner, int self_loops, const float* z, const float* dz, float* dT, float* workspace,
+                        int64_t workspace_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

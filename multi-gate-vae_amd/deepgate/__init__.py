@@ -3,7 +3,7 @@
 Same names as the reference's package (DG_VAE/deepgate/__init__.py:1-10): `deepgate.Model` is the
 last `Model` imported there, i.e. the XAG one; `train.py` picks the per-type class explicitly."""
 from . import synthetic  # noqa: F401
-from . import digae_layer, digvae_model  # noqa: F401
+from . import digae_layer, digae_model, digvae_model  # noqa: F401
 from . import dg_ae_model_aig, dg_ae_model_mig, dg_ae_model_xmg, dg_ae_model_xag  # noqa: F401
 from .dg_ae_model_xag import Model  # noqa: F401
 from .trainer import Trainer, GraphLoader  # noqa: F401

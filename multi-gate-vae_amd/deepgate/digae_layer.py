@@ -1,7 +1,8 @@
 """Structural encoder / decoder surface of the reference (`DG_VAE/deepgate/digae_layer.py:26-33,
-232-297`) on top of the HIP kernels.  Module and parameter names, shapes, construction order
+73-211, 232-297`) on top of the HIP kernels.  Module and parameter names, shapes, construction order
 (hence seeded initialisation) and call signatures follow the reference, so its checkpoints load and
-`train.py` builds the encoder the same way; the arithmetic is `ops.StructEncoderFn`.
+`train.py` builds the encoder the same way; the arithmetic is `ops.StructEncoderFn` for the multi-gate
+encoder and `ops.DiGCNGatherFn` / `ops.DiGCNClassFn` around the linear kernels for the DiGAE baseline.
 """
 import torch
 import torch.nn as nn
@@ -33,6 +34,122 @@ class DirectedInnerProductDecoder(nn.Module):
         # dense N x N scores: only sensible for tiny graphs; not on the training path
         adj = ops.dense_scores(s, t)
         return torch.sigmoid(adj) if sigmoid else adj
+
+
+def _classes_once(x, classes, width):
+    """Integer one-hot rows -> (rows, ids) once per encoder call (feature_classes runs a torch.unique with a host read-back); float
+    rows and rows of another width are left to the layer."""
+    if classes is None and x is not None and not torch.is_floating_point(x) and x.shape[1] == width:
+        return feature_classes(x)
+    return classes
+
+
+class DirectedGCNConv(nn.Module):
+    """out_i = sum_{j in L(i)} din(i)^-alpha dout(j)^-beta (W x_j + b) (digae_layer.py:73-114).  The reference flips edge_index to turn
+    the layer round; here `reverse` picks the plan's other CSR.  `classes` = (rows [C, F], row id per node uint8 [N]) stands in for x:
+    the Linear is then applied to the C rows only.  `relu`: the F.relu the two-layer encoders put behind conv1, fused into the sum."""
+
+    def __init__(self, in_channels, out_channels, alpha=1.0, beta=0.0, self_loops=True, adaptive=False):
+        super().__init__()
+        self.lin = nn.Linear(in_channels, out_channels)
+        self.alpha = alpha
+        self.beta = beta
+        self.self_loops = self_loops
+        self.adaptive = adaptive             # stored, unused: the reference's adaptive branch is commented out (:78-83)
+
+    def forward(self, x, edge_index, plan=None, reverse=False, classes=None, relu=False):
+        F_ = self.lin.in_features
+        args = (reverse, self.alpha, self.beta, self.self_loops is True, relu)
+        if classes is None and not torch.is_floating_point(x) and x.shape[1] == F_:
+            classes = feature_classes(x)     # integer one-hot rows, what the reference's Models build (None: too many distinct rows)
+        if classes is not None:
+            rows, xcls = classes
+            if rows.shape[1] != F_:
+                raise ValueError('expected %d node features, got %d' % (F_, rows.shape[1]))
+            if plan is None:
+                plan = GraphPlan(edge_index, xcls.shape[0])
+            table = rows.to(self.lin.weight.device) @ self.lin.weight.t() + self.lin.bias      # [C, out]: weight space, autograd differentiates it
+            return ops.DiGCNClassFn.apply(table, plan, xcls, *args)
+        if x.shape[1] != F_:
+            raise ValueError('expected %d node features, got %d' % (F_, x.shape[1]))
+        if plan is None:
+            plan = GraphPlan(edge_index, x.shape[0])
+        pad = (-F_) % 16                     # the linear kernels' 16-column granule, as MultiGCNEncoder._forward_rows pads
+        xp = torch.nn.functional.pad(x.to(torch.float32), (0, pad)) if pad else x.to(torch.float32)
+        w = torch.nn.functional.pad(self.lin.weight, (0, pad)) if pad else self.lin.weight
+        return ops.DiGCNGatherFn.apply(ops.linear(xp.contiguous(), w, self.lin.bias), plan, *args)
+
+
+class SourceGCNConvEncoder(nn.Module):
+    """conv2(relu(conv1(x, ei)), flip(ei)) (digae_layer.py:118-133)."""
+    FIRST_REVERSE = False
+
+    def __init__(self, in_channels, hidden_channels, out_channels, alpha=1.0, beta=0.0, self_loops=True, adaptive=False):
+        super().__init__()
+        self.conv1 = DirectedGCNConv(in_channels, hidden_channels, alpha, beta, self_loops, adaptive)
+        self.conv2 = DirectedGCNConv(hidden_channels, out_channels, alpha, beta, self_loops, adaptive)
+
+    def forward(self, x, edge_index, plan=None, classes=None):
+        if plan is None:
+            plan = GraphPlan(edge_index, (classes[1] if classes is not None else x).shape[0])
+        h = self.conv1(x, edge_index, plan, self.FIRST_REVERSE, classes, relu=True)
+        return self.conv2(h, edge_index, plan, not self.FIRST_REVERSE)
+
+
+class TargetGCNConvEncoder(SourceGCNConvEncoder):
+    """conv2(relu(conv1(x, flip(ei))), ei) (digae_layer.py:137-152)."""
+    FIRST_REVERSE = True
+
+
+class DirectedGCNConvEncoder(nn.Module):
+    """The DiGAE baseline encoder of `--model AE` (digae_layer.py:156-165)."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, alpha=1.0, beta=0.0, self_loops=True, adaptive=False):
+        super().__init__()
+        self.source_conv = SourceGCNConvEncoder(in_channels, hidden_channels, out_channels, alpha, beta, self_loops, adaptive)
+        self.target_conv = TargetGCNConvEncoder(in_channels, hidden_channels, out_channels, alpha, beta, self_loops, adaptive)
+
+    def forward(self, s, t, edge_index, plan=None, classes=None):
+        if plan is None:
+            plan = GraphPlan(edge_index, (classes[1] if classes is not None else s).shape[0])
+        F_ = self.source_conv.conv1.lin.in_features
+        cs = _classes_once(s, classes, F_)
+        ct = cs if (classes is not None or t is s) else _classes_once(t, None, F_)
+        return self.source_conv(s, edge_index, plan, cs), self.target_conv(t, edge_index, plan, ct)
+
+
+class SingleLayerSourceGCNConvEncoder(nn.Module):
+    """conv(x, flip(ei)) (digae_layer.py:174-184)."""
+    REVERSE = True
+
+    def __init__(self, in_channels, out_channels, alpha=1.0, beta=0.0, self_loops=True, adaptive=False):
+        super().__init__()
+        self.conv = DirectedGCNConv(in_channels, out_channels, alpha, beta, self_loops, adaptive)
+
+    def forward(self, x, edge_index, plan=None, classes=None):
+        return self.conv(x, edge_index, plan, self.REVERSE, classes)
+
+
+class SingleLayerTargetGCNConvEncoder(SingleLayerSourceGCNConvEncoder):
+    """conv(x, ei) (digae_layer.py:188-198)."""
+    REVERSE = False
+
+
+class SingleLayerDirectedGCNConvEncoder(nn.Module):
+    """s_1 = source_conv(t_0), t_1 = target_conv(s_0): the reference's cross wiring (digae_layer.py:202-211)."""
+
+    def __init__(self, in_channels, out_channels, alpha=1.0, beta=0.0, self_loops=True, adaptive=False):
+        super().__init__()
+        self.source_conv = SingleLayerSourceGCNConvEncoder(in_channels, out_channels, alpha, beta, self_loops, adaptive)
+        self.target_conv = SingleLayerTargetGCNConvEncoder(in_channels, out_channels, alpha, beta, self_loops, adaptive)
+
+    def forward(self, s_0, t_0, edge_index, plan=None, classes=None):
+        if plan is None:
+            plan = GraphPlan(edge_index, (classes[1] if classes is not None else s_0).shape[0])
+        F_ = self.source_conv.conv.lin.in_features
+        cs = _classes_once(s_0, classes, F_)
+        ct = cs if (classes is not None or t_0 is s_0) else _classes_once(t_0, None, F_)
+        return self.source_conv(t_0, edge_index, plan, ct), self.target_conv(s_0, edge_index, plan, cs)
 
 
 class MultiGCNEncoder(nn.Module):

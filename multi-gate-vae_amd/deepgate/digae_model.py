@@ -1,0 +1,41 @@
+"""DirectedGAE (reference: DG_VAE/deepgate/digae_model.py:106-168): an encoder that returns (s, t), the directed inner-product
+decoder, the reconstruction loss and the link-prediction test on the HIP kernels.  The undirected GAE of the same file is not
+part of the DG_AE / AE training paths and is left out."""
+import torch
+
+from . import ops
+from .digae_layer import DirectedInnerProductDecoder
+from .sampling import negative_sampling
+
+
+class DirectedGAE(torch.nn.Module):
+    def __init__(self, encoder, decoder=None):
+        super().__init__()
+        self.encoder = encoder
+        self.decoder = DirectedInnerProductDecoder() if decoder is None else decoder
+
+    def forward(self, data):
+        """sigmoid(s t^T) over all node pairs (digae_model.py:118-122), within the size limit of ops.dense_scores."""
+        s, t = self.encoder(data.x, data.x, data.edge_index)
+        return self.decoder.forward_all(s, t)
+
+    def encode(self, *args, **kwargs):
+        return self.encoder(*args, **kwargs)
+
+    def decode(self, *args, **kwargs):
+        return self.decoder(*args, **kwargs)
+
+    def recon_loss(self, s, t, pos_edge_index, neg_edge_index=None):
+        """(pos_loss + neg_loss, pred_bin, gt_bin) of digae_model.py:133-154 in one fused loss kernel (ops.ReconLossFn)."""
+        if neg_edge_index is None:
+            neg_edge_index = negative_sampling(pos_edge_index, s.shape[0])
+        st = torch.cat([s, t], dim=1)
+        loss, _, pred_bin = ops.ReconLossFn.apply(st, pos_edge_index, neg_edge_index, True)
+        Ep, En = pos_edge_index.shape[1], neg_edge_index.shape[1]
+        gt_bin = torch.zeros(Ep + En, dtype=torch.int32, device=s.device)
+        gt_bin[:Ep] = 1
+        return loss, pred_bin, gt_bin
+
+    def test(self, s, t, pos_edge_index, neg_edge_index):
+        """(ROC-AUC, average precision) of the decoder's scores (digae_model.py:156-168), ranked on the device (ops.link_record)."""
+        return ops.read_link_records([ops.link_record(s, t, pos_edge_index, neg_edge_index)])[0]

@@ -196,6 +196,8 @@ class GraphPlan:
         from . import ops
         if self.has_levels and ops.PACKED_ROWS == 2:
             self.order_rows                  # (default: a plan builds its packed sweep rows when it comes back for a second step, ops._sweep_rows)
+        if isinstance(quotient_stages, (tuple, list, set)) and len(quotient_stages) == 0:
+            return self                      # an encoder without half rounds (DirectedGCNConvEncoder): no colour classes, no first-stage table
         counts = sorted({int(c) for c in (quotient_stages if isinstance(quotient_stages, (tuple, list, set)) else [quotient_stages]) if int(c) > 0})
         if xcls is not None and self.N > 0 and counts and ops.QUOTIENT:
             if all([len(self.quotient(xcls, c)) > 0 for c in counts]):

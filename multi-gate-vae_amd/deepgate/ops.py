@@ -652,6 +652,94 @@ def gather_sum(h, nbr_ptr=None, nbr_idx=None, plan=None, reverse=False):
     return agg, deg
 
 
+# ------------------------------------------------------------------------------------------------
+# DiGAE baseline layer (DirectedGCNConv, digae_layer.py:73-114)
+# ------------------------------------------------------------------------------------------------
+DIGCN_WIDTHS = (16, 32, 64, 128)
+
+
+def digcn_scales(plan, reverse, alpha, beta, self_loops):
+    """(r, c) of a DirectedGCNConv over plan.csr(reverse): r[i] = din(i)^-alpha, c[j] = dout(j)^-beta (digae_layer.py:98-105), one
+    launch, kept on the plan per (direction, alpha, beta, self_loops)."""
+    cache = plan.__dict__.setdefault('_digcn_scales', {})
+    key = (bool(reverse), float(alpha), float(beta), bool(self_loops))
+    if key not in cache:
+        lp, op = plan.csr(reverse)[0], plan.csr(not reverse)[0]
+        check(lp, I32, 'list_ptr'); check(op, I32, 'opp_ptr')
+        rc = torch.empty(2, max(plan.N, 1), dtype=F32, device=lp.device)
+        _hip.call('mgv_digcn_scales', plan.N, ptr(lp), ptr(op), key[1], key[2], int(key[3]), ptr(rc[0]), ptr(rc[1]))
+        cache[key] = (rc[0], rc[1])
+    return cache[key]
+
+
+def _digcn_gather(y, plan, reverse, outer, inner, mask, self_loops, relu):
+    N, H = y.shape
+    p, i = plan.csr(reverse)
+    hn, hnodes = plan.heavy(reverse)
+    out = torch.empty_like(y)
+    _hip.call('mgv_digcn_gather', H, N, ptr(y), ptr(p), ptr(i), ptr(outer), ptr(inner), ptr(mask), int(self_loops), int(relu),
+              hn, ptr(hnodes) if hn else None, ptr(out))
+    return out
+
+
+class DiGCNGatherFn(torch.autograd.Function):
+    """z = act(r_i * sum_{j in L(i)} c_j y_j) over plan.csr(reverse), exact fp32 (MessagePassing.propagate with the norm of
+    digae_layer.py:107-114, and the F.relu of :127,146 when `relu`).  Backward: the same kernel over the opposite CSR with the
+    two scales swapped and the ReLU mask read from z while gathering — a pull, no scatter."""
+
+    @staticmethod
+    def forward(ctx, y, plan, reverse, alpha, beta, self_loops, relu):
+        yd = check(y.detach().contiguous(), F32, 'y')
+        if yd.shape[0] != plan.N or yd.shape[1] not in DIGCN_WIDTHS:
+            raise HipLibraryError('DirectedGCNConv rows must be [%d, 16|32|64|128] (got %s)' % (plan.N, tuple(yd.shape)))
+        r, c = digcn_scales(plan, reverse, alpha, beta, self_loops)
+        z = _digcn_gather(yd, plan, reverse, r, c, None, self_loops, relu)
+        ctx.plan, ctx.args = plan, (reverse, self_loops, relu)
+        ctx.save_for_backward(r, c, z if relu else None)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        r, c, z = ctx.saved_tensors
+        reverse, self_loops, _ = ctx.args
+        g = check(gz.contiguous(), F32, 'gz')
+        return _digcn_gather(g, ctx.plan, not reverse, c, r, z, self_loops, False), None, None, None, None, None, None
+
+
+class DiGCNClassFn(torch.autograd.Function):
+    """The first layer when the node features are class rows (digae_layer.feature_classes): z = act(r_i * sum_{j in L(i)} c_j T[cls_j])
+    with T [C, H] = rows W^T + b formed by the caller in weight space; one byte per neighbour instead of a row.  Backward: dT."""
+
+    @staticmethod
+    def forward(ctx, T, plan, xcls, reverse, alpha, beta, self_loops, relu):
+        Td = check(T.detach().contiguous(), F32, 'T')
+        check(xcls, U8, 'xcls')
+        C, H = Td.shape
+        if xcls.shape[0] != plan.N or H not in DIGCN_WIDTHS or not 1 <= C <= 8:
+            raise HipLibraryError('DirectedGCNConv class table must be [1..8, 16|32|64|128] over %d nodes (got %s, %d)' % (plan.N, tuple(Td.shape), xcls.shape[0]))
+        r, c = digcn_scales(plan, reverse, alpha, beta, self_loops)
+        p, i = plan.csr(reverse)
+        z = torch.empty(plan.N, H, dtype=F32, device=Td.device)
+        _hip.call('mgv_digcn_class_fwd', H, plan.N, ptr(xcls), ptr(Td), C, ptr(p), ptr(i), ptr(r), ptr(c), int(self_loops), int(relu), ptr(z))
+        ctx.plan, ctx.args = plan, (reverse, self_loops, C)
+        ctx.save_for_backward(r, c, xcls, z if relu else None)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        r, c, xcls, z = ctx.saved_tensors
+        reverse, self_loops, C = ctx.args
+        plan = ctx.plan
+        g = check(gz.contiguous(), F32, 'gz')
+        H = g.shape[1]
+        p, i = plan.csr(reverse)
+        dT = torch.zeros(C, H, dtype=F32, device=g.device)
+        ws = workspace(_hip.call_value('mgv_digcn_class_bwd_ws_floats', H, plan.N), g.device)
+        _hip.call('mgv_digcn_class_bwd', H, plan.N, ptr(xcls), C, ptr(p), ptr(i), ptr(r), ptr(c), int(self_loops), ptr(z), ptr(g), ptr(dT),
+                  ptr(ws), ws.numel())
+        return dT, None, None, None, None, None, None, None
+
+
 class AttnPoolFn(torch.autograd.Function):
     """zbar[i] = sum_j softmax_j(u . x_j) x_j over i's in-edges (csrc/attn_pool.hip): the stand-alone TFMlpAggr call."""
 

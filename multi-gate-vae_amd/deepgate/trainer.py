@@ -218,9 +218,12 @@ class Trainer():
         return loss_status
 
     def _encoder_half_rounds(self):
-        """2 x rounds of the model's two structural encoders (what GraphPlan.quotient is asked for; a list), 8 when it cannot be told."""
+        """2 x rounds of the model's two structural encoders (what GraphPlan.quotient is asked for; a list), 8 when it cannot be told.
+        An encoder whose halves exist and have no rounds (the DiGAE baseline, DirectedGCNConvEncoder) has none: an empty list, and
+        the prefetcher then prepares neither colour classes nor first-stage tables."""
         enc = getattr(self.model, getattr(self.model, 'ENCODER_ATTR', 'struct_encoder'), None)
-        counts = {2 * int(getattr(getattr(enc, a, None), 'num_rounds', 4)) for a in ('source_conv', 'target_conv')}
+        halves = [getattr(enc, a, None) for a in ('source_conv', 'target_conv')]
+        counts = {2 * int(getattr(h, 'num_rounds', 4)) for h in halves if h is None or hasattr(h, 'num_rounds')}
         return sorted(counts)                # --s_rounds and --t_rounds may differ: both encoders' stage counts are warmed
 
     def _side_stream(self):

@@ -41,10 +41,15 @@ def main(argv=None):
 
     print('[INFO] Create Model')
     if 'DG' not in args.model:
-        raise SystemExit('--model AE (DirectedGCNConvEncoder) is outside the accelerated path')
-    encoder = deepgate.digae_layer.DirectMultiGCNEncoder(
-        dim_hidden=args.dim_hidden, dim_feature=args.dim_feature, enable_reverse=True,
-        s_rounds=args.s_rounds, t_rounds=args.t_rounds, layernorm=args.layernorm)
+        # the DiGAE baseline the multi-gate encoder is compared against (the reference's train.py:47-50 hard-codes in_channels=3 and
+        # then fails on the int64 one-hot rows; here the input width is the models' --dim_feature)
+        encoder = deepgate.digae_layer.DirectedGCNConvEncoder(
+            in_channels=args.dim_feature, hidden_channels=args.dim_hidden, out_channels=args.dim_hidden,
+            alpha=1.0, beta=0.0, self_loops=True, adaptive=False)
+    else:
+        encoder = deepgate.digae_layer.DirectMultiGCNEncoder(
+            dim_hidden=args.dim_hidden, dim_feature=args.dim_feature, enable_reverse=True,
+            s_rounds=args.s_rounds, t_rounds=args.t_rounds, layernorm=args.layernorm)
     if 'VAE' in args.model:
         raise SystemExit('the DG_VAE training path does not run in the reference either (SURVEY.md §3.4); '
                          'the sampler/KL operators are available as deepgate.digvae_model.DirectedGVAE')
