@@ -76,6 +76,9 @@ int mgv_struct_stage_rows_bwd(int H, int64_t N, const float* h_in, const int32_t
  * heavy_n / heavy_nodes / heavy_ws (0 / NULL / NULL when there are none): the nodes with more than 64 neighbours in this CSR
  * (a clock- or reset-like net), ascending, and 2 * heavy_n * H floats of scratch: their neighbour sums are formed by a pre-pass
  * with one workgroup per node instead of by one lane group inside the tile kernel (100,000 consumers: 38 ms per launch there).
+ * The pre-pass sums are read only where a tile takes the per-row path (its lists hold more than 504 entries together, or it is the
+ * partial last tile); a listed node in any other tile is summed by the tile, and a long list that is not named here is walked in place:
+ * the result is the same with and without the list.
  * table_own_idx (NULL = off): TABLE MODE for the half round that follows the (degree, class)-table one — h_in is the C-row table,
  * a node's own row is h_in[table_own_idx[node]], every nbr_idx entry carries its neighbour's table row in the top byte
  * (entry = node | row << 24, N < 2^24): the N x H expansion of the table is never gathered.  nbr_tagged = 0 with a table_own_idx:

@@ -31,7 +31,9 @@ struct StageX3Args {
     float* g_agg_out;
     float* dWc; float* dbc; float* dWhh; float* dbhh; float* dxtab; float* dlnw; float* dlnb;
     // rows with more than kHeavyRow neighbours (a clock/reset-like net), ascending node ids, and their neighbour sums formed by
-    // k_heavy_sums before the stage kernel starts: [heavy_n][H] over h_in, then [heavy_n][H] over gy_agg (backward only)
+    // k_heavy_sums before the stage kernel starts: [heavy_n][H] over h_in, then [heavy_n][H] over gy_agg (backward only).
+    // The sums are consulted on the GENERIC row path only (row_generic: a binary search of heavy_nodes): a listed row inside a
+    // chunked tile (list total <= 504) is summed by the tile like any other row, an unlisted long row is walked in place.
     int heavy_n; const int32_t* heavy_nodes; const float* heavy_a; const float* heavy_g;
     // table mode (the half round after the (degree, class)-table one): h_in is the C-row table, a neighbour entry carries its class in
     // the top byte (h row = entry >> 24, gradient row = entry & 0xffffff), a node's own h row is own_idx[node].  Normal mode: 0 / ~0 / NULL.
@@ -48,7 +50,11 @@ constexpr int kTPR = 2;                 // gate-gradient tiles staged in LDS per
 constexpr int XLD = 24;                 // row-major [64][16 (+8 pad)] planes of [deg, onehot(cls) x8, 1, 0..]
 constexpr int kNW = 8;                  // waves per workgroup (two per SIMD)
 constexpr int kThreadsX3 = kNW * 64;
-constexpr int kIdxCap = 512;            // neighbour entries of one tile kept in LDS (mean tile: ~100-140); larger lists take the generic path
+// Neighbour entries of one tile kept in LDS (mean tile: ~100-140).  The cut between the two row paths is NOT at kIdxCap: a full tile
+// takes the chunked path while its list total is <= kIdxCap - 8 = 504 (tile_dmax); 505 entries and more, and every partial last
+// tile, take the generic per-row path.  The 8 spare entries are what the chunked path's unconditional index reads may run past a
+// row's list (clamped to kIdxCap + 7, the loads they would feed are predicated off).
+constexpr int kIdxCap = 512;
 constexpr int kPtrPad = 80;             // 65 CSR pointers of a tile + the tile's maximum degree at [72], padded
 
 // 8 waves over a (64 rows) x (H hidden columns) output: across column tiles first, then row tiles
@@ -280,8 +286,8 @@ __device__ __forceinline__ void rows_chunked(const StageX3Args& a, int64_t base,
     }
 }
 
-// generic degree: per-row loops (rare tiles with a high fan-out node or an index list beyond LDS).  A row with more than kHeavyRow
-// neighbours takes its sums from the pre-pass (k_heavy_sums) when the caller listed it: walked here, one neighbour after the other
+// generic degree: per-row loops (a partial last tile, or a tile whose index list has more than kIdxCap - 8 entries).  A row with more than
+// kHeavyRow neighbours takes its sums from the pre-pass (k_heavy_sums) when the caller listed it: walked here, one neighbour after the other
 // by a single lane group, a 100,000-consumer net costs 38 ms per launch.
 constexpr int kHeavyRow = 64;
 
