@@ -118,10 +118,13 @@ int mgv_struct_stage_bwd2_x3(int H, int64_t N, const float* h_in, const int32_t*
 /* ---- Linear over node rows (hs_linear dg_ae_model_aig.py:64, hs_decompose :109, fc_{s,t}_{mu,logstd}
  * digvae_model.py:135-136, readout Linear layers mlp.py:29,38; also the dgrad with W^T):
  *   Y[N][M] = [X1 | X2] W^T + b     (X2/K2 = NULL/0 unless a torch.cat of two inputs is fused, :64)
- * K1+K2 multiple of 16 (<= 256), M in {16,32,64,128}; ld* = row strides in floats. */
+ * K1+K2 multiple of 16 (<= 256), K1 and K2 multiples of 4, M in {16,32,64,128}; ld* = row strides in floats, multiples of 4, ld1 >= K1,
+ * ld2 >= K2, ldy >= M (columns of a row beyond its M or K are neither read nor written).  N = 0 returns MGV_OK and launches nothing. */
 int mgv_linear_fwd(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                    const float* W, const float* b, int M, float* Y, int ldy, void* stream);
-/* dW[M][K1+K2] += dY^T [X1|X2],  db[M] += column sums of dY (db may be NULL) */
+/* dW[M][K1+K2] += dY^T [X1|X2],  db[M] += column sums of dY (db may be NULL).  dW and db ACCUMULATE: the caller zeroes them (or keeps
+ * an earlier sum in them).  (M, K1+K2) in {16,32}x{16,32}, (32,64), (64,16), (64,32), (64,64), (64,128), (128,64); the same stride rules as
+ * the forward (ld1 >= K1, ld2 >= K2, lddy >= M, multiples of 4).  The workgroups' partial sums meet in float atomics: not bit-reproducible. */
 int mgv_linear_wgrad(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                      const float* dY, int lddy, int M, float* dW, float* db, void* stream);
 /* the same layers on bf16x3 split-precision MFMA (see mgv_struct_stage_fwd_x3): HBM-bound instead of fp32-MFMA-bound.
@@ -137,7 +140,9 @@ int mgv_linear_fwd_x3(int64_t N, const float* X1, int K1, int ld1, const float* 
  * with its OWN aggregator's weights — here one launch over all tiles instead of an index_select / Linear / index_copy per gate type).
  * Row r of tile t is NODE order[tile_start[t] + r] (r < tile_count[t]); X / Y / R / dY rows are indexed by node.  fwd: tile t multiplies by
  * the pack of slot tile_slot[t] (wpack_bf16[T][2][M*K], fragment order as mgv_wpack_bf16x3 writes it) and adds b[tile_slot[t]][M];
- * tile_list (nullable) names the tiles to visit (ntiles entries; NULL: tiles 0 .. ntiles-1).  wgrad: dW[M][K] += dY^T X, db[M] += colsum(dY)
+ * tile_list (nullable) names the tiles to visit (ntiles entries; NULL: tiles 0 .. ntiles-1); a tile with tile_count[t] = 0 is allowed and
+ * contributes / writes nothing; rows of Y no listed tile names are not touched; b may be NULL (no bias); ntiles = 0 returns MGV_OK.
+ * wgrad: dW[M][K] += dY^T X, db[M] += colsum(dY) (both ACCUMULATE, fixed order: bit-identical from call to call; ldx >= K)
  * over the rows of the listed tiles (ONE slot's list: GraphPlan.slot_tiles).  Shapes at H = 64: (M, K) = (192, 64) and (64, 192) forward,
  * (192, 64) weight gradient. */
 int mgv_grouped_linear_supported(int M, int K);
@@ -156,13 +161,15 @@ int mgv_linear_fwd_x3_res(int64_t N, const float* X1, int K1, int ld1, const flo
                           void* stream);
 /* dW[M][K1+K2] += dY^T [X1 | X2], db[M] += column sums of dY (db nullable).  Deterministic: every workgroup leaves its partial in
  * its own row of `workspace` (at least mgv_linear_wgrad_x3_ws_floats(M, K1+K2, N) floats) and a second launch adds the rows in a
- * fixed order — no float atomics, bit-identical from call to call */
+ * fixed order — no float atomics, bit-identical from call to call.  dW and db ACCUMULATE (+=); strides as the forward takes them
+ * (ld1 >= K1, ld2 >= K2, lddy >= M, multiples of 4); a workspace shorter than the size below is refused with MGV_EINVAL */
 int mgv_linear_wgrad_x3_ws_floats(int M, int K, int64_t N);
 int mgv_linear_wgrad_x3(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                         const float* dY, int lddy, int M, float* dW, float* db, float* workspace, int64_t workspace_floats,
                         void* stream);
-/* agg[i] = sum_{j in nbr(i)} h[j], deg[i] = |nbr(i)| (deg may be NULL): the scatter-add half of
- * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34) */
+/* agg[i] = sum_{j in nbr(i)} h[j] added in list order, deg[i] = |nbr(i)| (deg may be NULL): the scatter-add half of
+ * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34).  H in {16, 32, 64, 128} here and in the three
+ * row-sum entries below; any other H (0 and other non-multiples of 4 included) returns MGV_EUNSUPPORTED before anything is computed. */
 int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                    float* agg, float* deg, void* stream);
 
@@ -170,7 +177,8 @@ int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* nbr_ptr, con
  * the node's (degree, feature class) pair, class_id[N] numbers the pairs 0..C-1.
  * expand: out[i] = table[class_id[i]]; pull_sum: out[c] += sum over nodes of class c of
  * (gy_direct[i] + sum_{j in nbr(i)} gy_agg[j]) (gy_agg may be NULL); C * H * 20 <= 160 KiB.  pull_sum is deterministic for
- * C <= 8: per-workgroup rows in `workspace` (>= mgv_class_pull_sum_ws_floats(H, N, C) floats), added in a fixed order. */
+ * C <= 8: per-workgroup rows in `workspace` (>= mgv_class_pull_sum_ws_floats(H, N, C) floats; 0 for an unsupported H), added in a fixed
+ * order; C > 8 meets in LDS float atomics inside a workgroup.  `out` ACCUMULATES (+=) in both forms. */
 int mgv_class_expand(int H, int64_t N, const float* table, const int32_t* class_id, float* out, void* stream);
 /* Segmented row sums in list order (one lane group per segment, no atomics): out[s][H] = sum over m in [seg_ptr[s], seg_ptr[s+1]) of
  * v(item(m)), item(m) = items ? items[m] : m, v(i) = direct[i] + (agg ? sum of agg[nbr_idx[e]] over i's nbr list : 0).  The per-class

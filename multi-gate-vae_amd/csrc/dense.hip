@@ -327,6 +327,9 @@ int launch_linear_wgrad(const LinArgs& a, hipStream_t st) {
     MGV_LAUNCH_RET();
 }
 
+// row widths of the row-sum kernels (one float4 per lane, kThreads / (H / 4) rows per workgroup): checked before anything divides by H / 4
+inline bool row_width_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
+
 }  // namespace mgv
 
 extern "C" int mgv_linear_fwd(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
@@ -350,7 +353,7 @@ extern "C" int mgv_linear_fwd(int64_t N, const float* X1, int K1, int ld1, const
 extern "C" int mgv_linear_wgrad(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                                 const float* dY, int lddy, int M, float* dW, float* db, void* stream) {
     MGV_CHECK_ARG(N >= 0 && X1 && dY && dW && K1 > 0 && K2 >= 0 && (K2 == 0 || X2));
-    MGV_CHECK_ARG(K1 % 4 == 0 && K2 % 4 == 0 && ld1 % 4 == 0 && (K2 == 0 || ld2 % 4 == 0) && lddy % 4 == 0 && lddy >= M);
+    MGV_CHECK_ARG(K1 % 4 == 0 && K2 % 4 == 0 && ld1 >= K1 && ld1 % 4 == 0 && (K2 == 0 || (ld2 >= K2 && ld2 % 4 == 0)) && lddy % 4 == 0 && lddy >= M);
     if (N == 0) return MGV_OK;
     mgv::LinArgs a{};
     a.N = N; a.X1 = X1; a.K1 = K1; a.ld1 = ld1; a.X2 = X2; a.K2 = K2; a.ld2 = ld2; a.dY = dY; a.lddy = lddy; a.dW = dW; a.db = db;
@@ -365,6 +368,7 @@ extern "C" int mgv_linear_wgrad(int64_t N, const float* X1, int K1, int ld1, con
 
 extern "C" int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                               float* agg, float* deg, void* stream) {
+    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && h && nbr_ptr && agg);
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
@@ -383,6 +387,7 @@ extern "C" int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* n
 
 extern "C" int mgv_seg_sum(int H, int64_t n_seg, const int32_t* seg_ptr, const int32_t* items, const float* direct, const float* agg,
                            const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* out_row, float* out, void* stream) {
+    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(n_seg >= 0 && seg_ptr && direct && out && (!agg || (nbr_ptr && nbr_idx)));
     if (n_seg == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -399,6 +404,7 @@ extern "C" int mgv_seg_sum(int H, int64_t n_seg, const int32_t* seg_ptr, const i
 }
 
 extern "C" int mgv_class_expand(int H, int64_t N, const float* table, const int32_t* class_id, float* out, void* stream) {
+    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && table && class_id && out);
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -421,13 +427,14 @@ static int class_pull_grid(int H, int64_t N) {
 
 // floats of workspace mgv_class_pull_sum needs: one row of C*H partial sums per workgroup
 extern "C" int mgv_class_pull_sum_ws_floats(int H, int64_t N, int C) {
-    if (N <= 0 || C <= 0 || H <= 0) return 0;
+    if (N <= 0 || C <= 0 || !mgv::row_width_ok(H)) return 0;
     return class_pull_grid(H, N) * C * H;
 }
 
 extern "C" int mgv_class_pull_sum(int H, int64_t N, const float* gy_direct, const float* gy_agg, const int32_t* nbr_ptr,
                                   const int32_t* nbr_idx, const int32_t* class_id, int C, float* out, float* workspace,
                                   int64_t workspace_floats, void* stream) {
+    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && gy_direct && class_id && out && C >= 1 && (int64_t)C * H * 4 * 5 <= 160 * 1024 && (!gy_agg || (nbr_ptr && nbr_idx)));
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);

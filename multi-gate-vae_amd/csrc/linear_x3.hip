@@ -380,7 +380,7 @@ extern "C" int mgv_linear_wgrad_x3(int64_t N, const float* X1, int K1, int ld1, 
                                    const float* dY, int lddy, int M, float* dW, float* db, float* workspace,
                                    int64_t workspace_floats, void* stream) {
     MGV_CHECK_ARG(N >= 0 && X1 && dY && dW && K1 > 0 && K2 >= 0 && (K2 == 0 || X2));
-    MGV_CHECK_ARG(K1 % 4 == 0 && K2 % 4 == 0 && ld1 % 4 == 0 && (K2 == 0 || ld2 % 4 == 0) && lddy % 4 == 0 && lddy >= M);
+    MGV_CHECK_ARG(K1 % 4 == 0 && K2 % 4 == 0 && ld1 >= K1 && ld1 % 4 == 0 && (K2 == 0 || (ld2 >= K2 && ld2 % 4 == 0)) && lddy % 4 == 0 && lddy >= M);
     if (N == 0) return MGV_OK;
     mgv::LinX3Args a{};
     a.N = N; a.X1 = X1; a.K1 = K1; a.ld1 = ld1; a.X2 = X2; a.K2 = K2; a.ld2 = ld2; a.dY = dY; a.lddy = lddy; a.dW = dW; a.db = db; a.slab = workspace;
@@ -429,7 +429,7 @@ extern "C" int mgv_grouped_linear_wgrad_x3_ws_floats(int M, int K, int64_t ntile
 extern "C" int mgv_grouped_linear_wgrad_x3(int64_t ntiles, const int32_t* tile_list, const int32_t* order, const int32_t* tile_start,
                                            const int32_t* tile_count, const float* X, int K, int ldx, const float* dY, int lddy, int M,
                                            float* dW, float* db, float* workspace, int64_t workspace_floats, void* stream) {
-    MGV_CHECK_ARG(ntiles >= 0 && order && tile_start && tile_count && X && dY && dW && K % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddy >= M);
+    MGV_CHECK_ARG(ntiles >= 0 && order && tile_start && tile_count && X && dY && dW && K % 4 == 0 && ldx >= K && ldx % 4 == 0 && lddy % 4 == 0 && lddy >= M);
     if (ntiles == 0) return MGV_OK;
     mgv::LinX3Args a{};
     a.N = 0; a.X1 = X; a.K1 = K; a.ld1 = ldx; a.dY = dY; a.lddy = lddy; a.dW = dW; a.db = db; a.slab = workspace;
