@@ -290,6 +290,36 @@ int mgv_edge_dot_fwd(int H, int64_t E, const float* s, const float* t, int ld, c
                      const int64_t* dst, int sigmoid, float* out, void* stream);
 int mgv_edge_dot_bwd(int H, int64_t E, const float* s, const float* t, int ld, const int64_t* src,
                      const int64_t* dst, int sigmoid, const float* gout, float* ds, float* dt, void* stream);
+/* ---- the decoder over ALL node pairs (digae_layer.py:26-33 forward_all, returned by DirectedGAE.forward, digae_model.py:118-122;
+ * csrc/pair_scores.hip).  One arithmetic for the four entries: exact fp32, every pair the chain acc = fmaf(s[i][k], t[j][k], acc) over
+ * k = 0 .. H-1 in ascending order from acc = 0 (v_mfma_f32_16x16x4_f32; the listed-pair entry restates it with scalar fmaf), then
+ * the sigmoid of mgv_edge_dot_fwd when `sigmoid` is set — a score is the same bits whichever entry reports it.  H in {16, 32, 64, 128}
+ * (any other: MGV_EUNSUPPORTED before anything is launched).  s [M][lds], t [N][ldt]: row strides in floats of their own (on the models
+ * the two halves of st = hs_decompose(hs), ld = 2H), multiples of 4 and >= H, base pointers 16-byte aligned.
+ * fwd (digae_layer.py:31-33, digae_model.py:118-122): out[i][j] = <s_i, t_j>, any M, N >= 0 (0: nothing is launched), ldo >= N; columns of
+ * a row past N are not written.  Index arithmetic is 64-bit: M N may pass 2^31. */
+int mgv_pair_scores_fwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid, float* out,
+                        int64_t ldo, void* stream);
+/* backward of the above (autograd through digae_layer.py:31-33): ds[M][ldds] = G t, dt[N][lddt] = G^T s with G = gout * p (1 - p), p = the
+ * saved forward output `out` (G = gout and `out` unused without the sigmoid); gout [M][ldg >= N].  ds / dt are WRITTEN (no zero fill), either
+ * may be NULL.  Every output row belongs to one workgroup, which walks the other dimension in tile order: one fmaf chain per entry, no
+ * float atomics, bit-identical from call to call. */
+int mgv_pair_scores_bwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid, const float* out,
+                        int64_t ldo, const float* gout, int64_t ldg, float* ds, int ldds, float* dt, int lddt, void* stream);
+/* out[e] = the score of pair (src[e], dst[e]) (digae_layer.py:26-29 in the arithmetic of forward_all :31-33, digae_model.py:118-122): equal
+ * to out[src[e]][dst[e]] of mgv_pair_scores_fwd bit for bit; int64 lists like mgv_edge_dot_fwd */
+int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, const float* t, int ldt, const int64_t* src, const int64_t* dst,
+                       int sigmoid, float* out, void* stream);
+/* the streaming consumer of forward_all (digae_layer.py:31-33, digae_model.py:118-122) that never writes an N x N array: per row u its k
+ * best candidates and the number of candidates the decoder calls an edge.  Candidates of u: the nodes v of u's own graph,
+ * graph_ptr[g] <= v < graph_ptr[g+1] (graph_ptr [G+1] int32 on the device, NULL = one graph of all N), without v = u when skip_self.
+ * 1 <= k <= 32.  idx[N][k] int32: batch-wide node ids ordered by raw dot product descending, ties by ascending id; -1 past the end when the
+ * graph has fewer than k candidates.  score[N][k]: the reported score (sigmoid of the dot product when `sigmoid`), -inf where idx is -1.
+ * n_above[N] int32: candidates whose reported score is > threshold (the `>` of pred_bin, trainer.py:240-244).  A NaN score is never
+ * selected or counted.  Refused with MGV_EINVAL before anything is launched: k outside [1, 32], a graph_ptr that does not start at 0
+ * and end at N (its two ends are read back: the only blocking step, skipped for NULL). */
+int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k, int sigmoid,
+                  float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream);
 /* sums[0] += sum_pos -log(sigma+1e-15), sums[1] += sum_neg -log(1-sigma+1e-15); counts += {TP,FP,TN,FN}
  * (trainer.py:240-244); pred_bin[Epos+Eneg] optional */
 int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,

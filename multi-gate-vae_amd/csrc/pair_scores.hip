@@ -1,0 +1,373 @@
+// All-pairs side of the inner-product decoder (digae_layer.py:26-33 forward_all, digae_model.py:118-122): dense scores with their
+// backward, scores of listed pairs, and the streaming top-k / count consumer that never writes an N x N array.
+//
+// ONE arithmetic for every entry: exact fp32 on v_mfma_f32_16x16x4_f32 with k in plain ascending order 0 .. H-1 (k-step kk feeds
+// k = 4 kk + q from lane quarter q; no in-block permutation as in mma_kblock), i.e. for every pair the chain
+//     acc = 0;  for k = 0 .. H-1: acc = fmaf(s[i][k], t[j][k], acc)
+// which k_pair_at restates with scalar fmaf.  The dense tile code (tile_scores) is shared by the dense forward and the top-k kernel,
+// so a score reported by one is the other's bit for bit; these are decisions at a threshold and ranks, like k_edge_dot's.
+#include "mgv_common.h"
+#include "../../include/mgvae_hip.h"
+
+#include <limits.h>
+
+namespace mgv {
+
+constexpr int kPairTile = 64;          // output tile: 64 x 64, wave w owns rows 16 w .. 16 w + 15 and all 64 columns
+constexpr int kPairChunk = 16;         // column tiles one workgroup of the dense forward walks with its s fragments in registers
+constexpr int kTopkMax = 32;
+
+template <int H>
+struct PairCfg {
+    static_assert(H == 16 || H == 32 || H == 64 || H == 128, "H must be 16, 32, 64 or 128");
+    static constexpr int KS = H / 4;                      // MFMA k-steps
+    static constexpr int LDT = H + 4;                     // forward t tile [column][k]: lane (r, q) reads bank 4 r + q (+ const)
+    static constexpr int VPT = H / 16;                    // float4s a thread moves per 64-row operand tile
+    static constexpr int LDB = H % 64 == 0 ? H + 16 : 48; // backward operand tile [walked row][k]: lane (r, q) reads bank 16 q + r
+};
+
+// LDS traffic of ONE wave in program order: the lanes of a wave exchange data through LDS without a workgroup barrier
+__device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// the wave's 16 rows of s as A fragments: lane (r = lane & 15, q = lane >> 4) holds s[row0 + r][4 kk + q]; rows past M are zeros
+template <int H>
+__device__ __forceinline__ void load_row_frags(float (&a)[H / 4], const float* s, int lds, int64_t row, bool ok, int q) {
+    const float* p = s + (ok ? row : 0) * (int64_t)lds + q;
+#pragma unroll
+    for (int kk = 0; kk < H / 4; ++kk) a[kk] = ok ? p[4 * kk] : 0.f;
+}
+
+// rows c0 .. c0 + 63 of a row-major operand (zeros past n) as H / 16 float4s per thread, and their place in an LDS tile of stride LD
+template <int H>
+__device__ __forceinline__ void tile_load(float4 (&v)[H / 16], const float* x, int ldx, int64_t c0, int64_t n) {
+#pragma unroll
+    for (int i = 0; i < H / 16; ++i) {
+        const int e = threadIdx.x + kThreads * i, jj = e / (H / 4), c4 = e % (H / 4);
+        v[i] = c0 + jj < n ? ld4(x + (c0 + jj) * (int64_t)ldx + 4 * c4) : zero4();
+    }
+}
+template <int H, int LD>
+__device__ __forceinline__ void tile_store(float* tl, const float4 (&v)[H / 16]) {
+#pragma unroll
+    for (int i = 0; i < H / 16; ++i) {
+        const int e = threadIdx.x + kThreads * i, jj = e / (H / 4), c4 = e % (H / 4);
+        st4(tl + jj * LD + 4 * c4, v[i]);
+    }
+}
+
+// acc[c] = the wave's 16 rows x columns 16 c .. 16 c + 15 of the tile; lane holds column (lane & 15), rows 4 (lane >> 4) + reg
+template <int H>
+__device__ __forceinline__ void tile_scores(f32x4 (&acc)[4], const float (&a)[H / 4], const float* tl, int r, int q) {
+    constexpr int LDT = PairCfg<H>::LDT;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < H / 4; ++kk) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = mfma16(a[kk], tl[(16 * c + r) * LDT + 4 * kk + q], acc[c]);
+    }
+}
+
+// ---------------------------------------------------------------------------------- dense forward
+// grid (row tiles, chunks of kPairChunk column tiles): no cap, every tile has its workgroup position
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_pair_fwd(int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt,
+                                                       int sigmoid, float* out, int64_t ldo) {
+    constexpr int LDT = PairCfg<H>::LDT;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t row0 = (int64_t)blockIdx.x * kPairTile + 16 * w;
+    float a[H / 4];
+    load_row_frags<H>(a, s, lds, row0 + r, row0 + r < M, q);
+    const int64_t nct = (N + kPairTile - 1) / kPairTile;
+    const int64_t ct0 = (int64_t)blockIdx.y * kPairChunk, ct1 = ct0 + kPairChunk < nct ? ct0 + kPairChunk : nct;
+    float4 nxt[H / 16];
+    tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
+    for (int64_t ct = ct0; ct < ct1; ++ct) {
+        __syncthreads();                                   // every wave is done with the previous tile
+        tile_store<H, LDT>(tl, nxt);
+        __syncthreads();
+        if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);   // in flight under the MFMAs
+        f32x4 acc[4];
+        tile_scores<H>(acc, a, tl, r, q);
+        const int64_t col0 = ct * kPairTile;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int64_t col = col0 + 16 * c + r;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int64_t row = row0 + 4 * q + g;
+                if (row < M && col < N) out[row * ldo + col] = sigmoid ? sigmoidf_(acc[c][g]) : acc[c][g];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------- listed pairs
+// the same chain with scalar fmaf: one thread per pair
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_pair_at(int64_t E, const float* s, int lds, const float* t, int ldt, const int64_t* src,
+                                                      const int64_t* dst, int sigmoid, float* out) {
+    for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < E; e += (int64_t)gridDim.x * kThreads) {
+        const float* a = s + src[e] * (int64_t)lds;
+        const float* b = t + dst[e] * (int64_t)ldt;
+        float acc = 0.f;
+#pragma unroll
+        for (int k4 = 0; k4 < H / 4; ++k4) {
+            const float4 x = ld4(a + 4 * k4), y = ld4(b + 4 * k4);
+            acc = fmaf(x.x, y.x, acc);
+            acc = fmaf(x.y, y.y, acc);
+            acc = fmaf(x.z, y.z, acc);
+            acc = fmaf(x.w, y.w, acc);
+        }
+        out[e] = sigmoid ? sigmoidf_(acc) : acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------- dense backward
+// d[a][k] = sum_b G(a, b) x[b][k]: one workgroup per 64 rows a, which walks b in tile order; every entry is ONE fmaf chain over
+// b = 0 .. 64 ceil(B / 64) - 1 (zeros past B), so nothing meets in atomics and two runs give the same bits.
+// TRANS = false: ds (a = row i of the score matrix, b = column j, x = t); TRANS = true: dt (a = column j, b = row i, x = s).
+template <int H, bool TRANS>
+__global__ __launch_bounds__(kThreads) void k_pair_bwd(int64_t A, int64_t B, const float* x, int ldx, int sigmoid, const float* p,
+                                                       int64_t ldp, const float* g, int64_t ldg, float* d, int ldd) {
+    constexpr int LDB = PairCfg<H>::LDB, HC = H / 16;
+    __shared__ __attribute__((aligned(16))) float xl[kPairTile * LDB];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t a0 = (int64_t)blockIdx.x * kPairTile + 16 * w, arow = a0 + r;
+    f32x4 acc[HC];
+#pragma unroll
+    for (int c = 0; c < HC; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int64_t b0 = 0; b0 < B; b0 += kPairTile) {
+        float gf[16];
+#pragma unroll
+        for (int st = 0; st < 16; ++st) {
+            const int64_t b = b0 + 4 * st + q;
+            float v = 0.f;
+            if (arow < A && b < B) {
+                v = g[TRANS ? b * ldg + arow : arow * ldg + b];
+                if (sigmoid) { const float pp = p[TRANS ? b * ldp + arow : arow * ldp + b]; v *= pp * (1.0f - pp); }
+            }
+            gf[st] = v;
+        }
+        float4 xv[H / 16];
+        tile_load<H>(xv, x, ldx, b0, B);
+        __syncthreads();
+        tile_store<H, LDB>(xl, xv);
+        __syncthreads();
+#pragma unroll
+        for (int st = 0; st < 16; ++st) {
+#pragma unroll
+            for (int c = 0; c < HC; ++c) acc[c] = mfma16(gf[st], xl[(4 * st + q) * LDB + 16 * c + r], acc[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < HC; ++c) {
+#pragma unroll
+        for (int gI = 0; gI < 4; ++gI) {
+            const int64_t row = a0 + 4 * q + gI;
+            if (row < A) d[row * (int64_t)ldd + 16 * c + r] = acc[c][gI];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------- streaming top-k and counts
+// order of the lists: raw dot product descending, ties by ascending node id
+__device__ __forceinline__ bool pair_better(float v, int i, float kv, int ki) { return v > kv || (v == kv && i < ki); }
+
+// One workgroup per 64 rows u; it walks the column tiles that meet the rows' graphs with the dense kernel's tile loop.  Each wave
+// leaves its 16 x 16 score blocks in LDS, where 4 lanes per row scan them in ascending column order against the row's k-th best and
+// insert into the row's sorted list (LDS).  A row only ever sees the columns of its own graph.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
+                                                        int G, int k, int sigmoid, float threshold, int skip_self, int32_t* idx,
+                                                        float* score, int32_t* n_above) {
+    constexpr int LDT = PairCfg<H>::LDT, LDS_SC = 17;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ float sc[kPairTile * LDS_SC];
+    __shared__ float lv[kPairTile * kTopkMax];
+    __shared__ int li[kPairTile * kTopkMax];
+    __shared__ int rlo[kPairTile], rhi[kPairTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    if (threadIdx.x < kPairTile) {
+        const int64_t u = u0 + threadIdx.x;
+        int64_t lo = 0, hi = 0;
+        if (u < N) {
+            if (gp == nullptr) { hi = N; }
+            else {
+                int a = 0, b = G;                          // first graph whose end lies behind u
+                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
+                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
+                hi = hi < lo ? lo : (hi > N ? N : hi);
+            }
+        }
+        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+    }
+    // the wave's rows: lane (row = lane >> 2, sub = lane & 3) in the scan, list rows initialised by their own wave
+    const int srow = 16 * w + (lane >> 2), sub = lane & 3;
+    for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
+    __syncthreads();
+    int64_t clo = N, chi = 0;
+    for (int i = 0; i < kPairTile; ++i) {
+        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
+    }
+    const int64_t su = u0 + srow;                          // the row this lane scans for
+    const int mylo = rlo[srow], myhi = rhi[srow];
+    const int64_t row0 = u0 + 16 * w;
+    float a[H / 4];
+    load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
+    int cnt = 0;
+    if (clo < chi) {
+        const int64_t ct0 = clo / kPairTile, ct1 = (chi + kPairTile - 1) / kPairTile;
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                wave_lds_fence();                          // the previous block's reads are done
+#pragma unroll
+                for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * LDS_SC + r] = acc[c][g];
+                wave_lds_fence();
+                const int64_t cb = ct * kPairTile + 16 * c;
+                for (int st = 0; st < 4; ++st) {
+                    const int64_t col = cb + 4 * st + sub;
+                    const float v = sc[srow * LDS_SC + 4 * st + sub];
+                    const bool valid = col >= mylo && col < myhi && !(skip_self && col == su) && v == v;
+                    const float rep = sigmoid ? sigmoidf_(v) : v;
+                    cnt += (valid && rep > threshold) ? 1 : 0;
+                    const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
+                    if (__ballot(pass) == 0ull) continue;
+                    for (int turn = 0; turn < 4; ++turn) {  // the row's four lanes insert one after the other, lowest column first
+                        if (pass && sub == turn) {
+                            float* L = lv + srow * kTopkMax;
+                            int* I = li + srow * kTopkMax;
+                            if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
+                                int pos = k - 1;
+                                while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
+                                    L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
+                                }
+                                L[pos] = v; I[pos] = (int)col;
+                            }
+                        }
+                        wave_lds_fence();
+                    }
+                }
+            }
+        }
+    }
+    wave_lds_fence();
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    if (su < N) {
+        if (sub == 0) n_above[su] = cnt;
+        for (int j = sub; j < k; j += 4) {
+            const int id = li[srow * kTopkMax + j];
+            const float v = lv[srow * kTopkMax + j];
+            idx[su * k + j] = id == INT_MAX ? -1 : id;
+            score[su * k + j] = id == INT_MAX ? -INFINITY : (sigmoid ? sigmoidf_(v) : v);
+        }
+    }
+}
+
+inline bool pair_h_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
+inline bool pair_rows_ok(const float* x, int ld, int H) { return x != nullptr && ld >= H && ld % 4 == 0 && ((uintptr_t)x & 15) == 0; }
+
+}  // namespace mgv
+
+#define MGV_PAIR_DISPATCH_H(H, EXPR)                                            \
+    switch (H) {                                                                \
+        case 16: { constexpr int HH = 16; EXPR; } break;                        \
+        case 32: { constexpr int HH = 32; EXPR; } break;                        \
+        case 64: { constexpr int HH = 64; EXPR; } break;                        \
+        default: { constexpr int HH = 128; EXPR; } break;                       \
+    }
+
+extern "C" int mgv_pair_scores_fwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid,
+                                   float* out, int64_t ldo, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(M >= 0 && N >= 0);
+    if (M == 0 || N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H) && out != nullptr && ldo >= N);
+    const int64_t nrt = (M + mgv::kPairTile - 1) / mgv::kPairTile, nct = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    const int64_t chunks = (nct + mgv::kPairChunk - 1) / mgv::kPairChunk;
+    if (nrt > 0x7fffffffLL || chunks > 65535) return MGV_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_fwd<HH>), dim3((unsigned)nrt, (unsigned)chunks), dim3(mgv::kThreads), 0, st,
+                                              M, N, s, lds, t, ldt, sigmoid, out, ldo));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_scores_bwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid,
+                                   const float* out, int64_t ldo, const float* gout, int64_t ldg, float* ds, int ldds, float* dt,
+                                   int lddt, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(M >= 0 && N >= 0);
+    MGV_CHECK_ARG(ds == nullptr || ldds >= H);
+    MGV_CHECK_ARG(dt == nullptr || lddt >= H);
+    const bool want_ds = ds != nullptr && M > 0, want_dt = dt != nullptr && N > 0;
+    if (!want_ds && !want_dt) return MGV_OK;
+    if (M > 0 && N > 0) {
+        MGV_CHECK_ARG(gout != nullptr && ldg >= N && (!sigmoid || (out != nullptr && ldo >= N)));
+        MGV_CHECK_ARG(!want_ds || mgv::pair_rows_ok(t, ldt, H));
+        MGV_CHECK_ARG(!want_dt || mgv::pair_rows_ok(s, lds, H));
+    }
+    const int64_t bs = (M + mgv::kPairTile - 1) / mgv::kPairTile, bt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    if (bs > 0x7fffffffLL || bt > 0x7fffffffLL) return MGV_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    if (want_ds) {      // an empty walked dimension leaves zeros
+        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_bwd<HH, false>), dim3((unsigned)bs), dim3(mgv::kThreads), 0, st,
+                                                  M, N, t, ldt, sigmoid, out, ldo, gout, ldg, ds, ldds));
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    if (want_dt) {
+        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_bwd<HH, true>), dim3((unsigned)bt), dim3(mgv::kThreads), 0, st,
+                                                  N, M, s, lds, sigmoid, out, ldo, gout, ldg, dt, lddt));
+    }
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, const float* t, int ldt, const int64_t* src,
+                                  const int64_t* dst, int sigmoid, float* out, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(E >= 0);
+    if (E == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H) && src != nullptr && dst != nullptr && out != nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = mgv::grid_for((E + mgv::kThreads - 1) / mgv::kThreads, 8);
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_at<HH>), dim3(grid), dim3(mgv::kThreads), 0, st, E, s, lds, t, ldt, src, dst,
+                                              sigmoid, out));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
+                             int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // node ids and idx offsets are int32 on the host side
+    MGV_CHECK_ARG(graph_ptr == nullptr || G >= 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (graph_ptr != nullptr) {
+        // the table must start at 0 and end at N: its two ends are read back (the only blocking step of this entry; NULL skips it)
+        int32_t ends[2] = {0, 0};
+        hipError_t e = hipMemcpyAsync(&ends[0], graph_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], graph_ptr + G, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return (int)e;
+        MGV_CHECK_ARG(ends[0] == 0 && (int64_t)ends[1] == N);
+    }
+    if (N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H) && idx != nullptr && score != nullptr && n_above != nullptr);
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_topk<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
+                                              graph_ptr, G, k, sigmoid, threshold, skip_self, idx, score, n_above));
+    MGV_LAUNCH_RET();
+}

@@ -123,6 +123,29 @@ class FunctionalModel(nn.Module):
                 neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan)
             return ops.link_record(st, None, pos_edge_index, neg_edge_index)
 
+    def _decoder_halves(self, hs):
+        """(s, t): the two column halves of st = hs_decompose(hs), as views (the pair kernels take a row stride)."""
+        st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
+        H = st.shape[1] // 2
+        return st[:, :H], st[:, H:]
+
+    def predict_links(self, hs, k, graph_ptr=None, skip_self=True):
+        """(idx [N, k] int32, score [N, k], n_above [N] int32) on st = hs_decompose(hs): every gate's k most probable fan-out targets
+        inside its own graph (batch-wide ids, -1 / -inf past the end) and the number of candidates the decoder calls an edge
+        (sigma > 0.5), streamed by ops.pair_topk without an N x N array.  Added functionality: the reference can only form the dense
+        matrix (digae_layer.py:31-33)."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
+
+    def reconstruction_counts(self, hs, edge_index, graph_ptr, threshold=0.5):
+        """int64 [G, 4] per graph on the device: true positives, predicted positives over all n_g^2 ordered pairs, edges, ordered pairs
+        (ops.reconstruction_counts) — the confusion of the decoder against the FULL adjacency, where recon_loss's counters see only
+        sampled non-edges.  Precision and recall are the caller's two divisions."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
+
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the

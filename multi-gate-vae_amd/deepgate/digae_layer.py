@@ -31,9 +31,13 @@ class DirectedInnerProductDecoder(nn.Module):
         return ops.edge_dot(s, t, edge_index, sigmoid)
 
     def forward_all(self, s, t, sigmoid=True):
-        # dense N x N scores: only sensible for tiny graphs; not on the training path
-        adj = ops.dense_scores(s, t)
-        return torch.sigmoid(adj) if sigmoid else adj
+        # dense M x N scores at any size that fits the device (ops.PairScoresFn, under autograd); beyond that: topk
+        return ops.pair_scores(s, t, sigmoid)
+
+    def topk(self, s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False):
+        """The streaming form of forward_all (added functionality: the reference has only the dense matrix): per node its k best
+        links inside its own graph and the number of candidates scored above `threshold`, (idx, score, n_above) of ops.pair_topk."""
+        return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self)
 
 
 def _classes_once(x, classes, width):

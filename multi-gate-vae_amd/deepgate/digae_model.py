@@ -15,9 +15,21 @@ class DirectedGAE(torch.nn.Module):
         self.decoder = DirectedInnerProductDecoder() if decoder is None else decoder
 
     def forward(self, data):
-        """sigmoid(s t^T) over all node pairs (digae_model.py:118-122), within the size limit of ops.dense_scores."""
+        """sigmoid(s t^T) over all node pairs (digae_model.py:118-122), at any size the device can hold (ops.pair_scores)."""
         s, t = self.encoder(data.x, data.x, data.edge_index)
         return self.decoder.forward_all(s, t)
+
+    def predict_links(self, s, t, k, graph_ptr=None, skip_self=True):
+        """(idx [N, k] int32, score [N, k], n_above [N] int32): every node's k most probable successors inside its own graph and the
+        number of candidates the decoder calls an edge (score > 0.5), streamed (ops.pair_topk).  Added functionality."""
+        with torch.no_grad():
+            return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
+
+    def reconstruction_counts(self, s, t, edge_index, graph_ptr, threshold=0.5):
+        """int64 [G, 4] per graph: true positives, predicted positives over all n_g^2 ordered pairs, edges, ordered pairs
+        (ops.reconstruction_counts); precision and recall against the full adjacency are the caller's two divisions."""
+        with torch.no_grad():
+            return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
     def encode(self, *args, **kwargs):
         return self.encoder(*args, **kwargs)

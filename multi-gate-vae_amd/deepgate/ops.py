@@ -952,12 +952,141 @@ def edge_dot(s, t, edge_index, sigmoid=True):
     return EdgeDotFn.apply(s, t, edge_index, sigmoid)
 
 
+def _pair_rows(x, name):
+    """(tensor, row stride) as the pair-score launchers take an operand: fp32 rows with unit column stride, a row stride that is a
+    multiple of 4 and a 16-byte aligned base — a column half of st = hs_decompose(hs) goes in as it is, anything else is copied."""
+    x = x.detach()
+    if x.dim() != 2:
+        raise HipLibraryError('%s must be a matrix [rows, H] (got shape %s)' % (name, tuple(x.shape)))
+    if not x.is_cuda:
+        raise HipLibraryError('%s must live on the GPU (got %s); the hot path has no CPU implementation' % (name, x.device))
+    if x.dtype != F32:
+        raise HipLibraryError('%s must be %s (got %s)' % (name, F32, x.dtype))
+    rows_ok = x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
+    if x.shape[0] <= 1 or not rows_ok:
+        x = x.contiguous()
+    return x, _pair_ld(x)
+
+
+def _pair_ld(x):
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def _pair_operands(s, t):
+    sd, lds = _pair_rows(s, 's')
+    td, ldt = _pair_rows(t, 't')
+    if sd.shape[1] != td.shape[1]:
+        raise HipLibraryError('s and t must have the same width (got %d and %d)' % (sd.shape[1], td.shape[1]))
+    return sd, lds, td, ldt, sd.shape[1]
+
+
+def _dense_fits(M, N, dev):
+    """A dense M x N result the device cannot hold is refused here, by name, instead of by the allocator."""
+    need = 4 * M * N
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # blocks the caching allocator can hand out again
+    if need > free:
+        raise HipLibraryError('dense scores of %d x %d pairs need %.1f GiB, the device has %.1f GiB free: use the streaming form, '
+                              'ops.pair_topk / DirectedInnerProductDecoder.topk (top-k links and counts per row, no N x N array)'
+                              % (M, N, need / 2.0 ** 30, free / 2.0 ** 30))
+
+
+class PairScoresFn(torch.autograd.Function):
+    """out[i, j] = sigma(<s_i, t_j>) over all pairs (digae_layer.py:31-33), exact fp32 in ascending k; the backward writes ds = G t and
+    dt = G^T s without atomics (mgv_pair_scores_bwd)."""
+
+    @staticmethod
+    def forward(ctx, s, t, sigmoid):
+        sd, lds, td, ldt, H = _pair_operands(s, t)
+        M, N = sd.shape[0], td.shape[0]
+        _dense_fits(M, N, sd.device)
+        out = torch.empty((M, N), dtype=F32, device=sd.device)
+        _hip.call('mgv_pair_scores_fwd', H, M, N, ptr(sd), lds, ptr(td), ldt, int(bool(sigmoid)), ptr(out), max(N, 1))
+        ctx.save_for_backward(sd, td, out)
+        ctx.sigmoid = bool(sigmoid)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        sd, td, out = ctx.saved_tensors
+        lds, ldt = _pair_ld(sd), _pair_ld(td)
+        M, N, H = sd.shape[0], td.shape[0], sd.shape[1]
+        gout = check(gout.contiguous(), F32, 'gout')
+        ds = torch.empty((M, H), dtype=F32, device=sd.device) if ctx.needs_input_grad[0] else None
+        dt = torch.empty((N, H), dtype=F32, device=sd.device) if ctx.needs_input_grad[1] else None
+        _hip.call('mgv_pair_scores_bwd', H, M, N, ptr(sd), lds, ptr(td), ldt, int(ctx.sigmoid), ptr(out), max(N, 1), ptr(gout), max(N, 1),
+                  ptr(ds), H, ptr(dt), H)
+        return ds, dt, None
+
+
+def pair_scores(s, t, sigmoid=True):
+    """Decoder scores of all M x N pairs at any size, under autograd."""
+    return PairScoresFn.apply(s, t, sigmoid)
+
+
+def pair_scores_at(s, t, edge_index, sigmoid=True):
+    """Scores of the listed pairs in the arithmetic of pair_scores: equal to pair_scores(s, t)[src, dst] bit for bit (no grad; the
+    training path's per-edge decoder is edge_dot)."""
+    sd, lds, td, ldt, H = _pair_operands(s, t)
+    src, dst = _edge_rows(edge_index)
+    E = src.numel()
+    out = torch.empty(E, dtype=F32, device=sd.device)
+    _hip.call('mgv_pair_scores_at', H, E, ptr(sd), lds, ptr(td), ldt, ptr(src), ptr(dst), int(bool(sigmoid)), ptr(out))
+    return out
+
+
+def pair_topk(s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False):
+    """(idx [N, k] int32, score [N, k], n_above [N] int32) per row u over the nodes of u's own graph (graph_ptr [G + 1], None: one graph):
+    the k best links by raw dot product (ties: lower id first; -1 / -inf past the end) and the number of candidates whose score is
+    > threshold.  Streaming: no N x N array.  No grad; nothing is read back except the two ends of a graph_ptr, which the launcher
+    checks (None: no host synchronisation at all)."""
+    sd, lds, td, ldt, H = _pair_operands(s, t)
+    N = sd.shape[0]
+    if td.shape[0] != N:
+        raise HipLibraryError('pair_topk ranks the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
+    k = int(k)
+    dev = sd.device
+    gp, G = None, 0
+    if graph_ptr is not None:
+        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
+        G = gp.numel() - 1
+        if G < 0:
+            raise HipLibraryError('graph_ptr needs at least one entry')
+    kk = min(max(k, 1), 32)
+    idx = torch.empty((N, kk), dtype=I32, device=dev)
+    score = torch.empty((N, kk), dtype=F32, device=dev)
+    n_above = torch.empty(N, dtype=I32, device=dev)
+    _hip.call('mgv_pair_topk', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, k, int(bool(sigmoid)), float(threshold), int(bool(skip_self)),
+              ptr(idx), ptr(score), ptr(n_above))
+    return idx, score, n_above
+
+
+def reconstruction_counts(s, t, edge_index, graph_ptr, threshold=0.5):
+    """int64 [G, 4] on the device, per graph of the batch: {true positives, predicted positives over all n_g^2 ordered pairs, edges,
+    ordered pairs} of the decoder at `threshold` against the FULL adjacency (the sampled counters of ReconLossFn see E + N non-edges
+    of N^2 - E).  The true positives are pair_scores_at over the edges and the predicted positives the n_above of pair_topk: the same
+    bits on both sides of the same `>`.  Integer sums throughout; precision = [:, 0] / [:, 1] and recall = [:, 0] / [:, 2] are the
+    caller's divisions.  An edge counts for the graph of its source."""
+    dev = s.device
+    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64)
+    G = gp.numel() - 1
+    src, dst = _edge_rows(edge_index)
+    _, _, n_above = pair_topk(s, t, 1, graph_ptr=gp, sigmoid=True, threshold=threshold, skip_self=False)
+    if G <= 0:
+        return torch.zeros((0, 4), dtype=torch.int64, device=dev)
+    hit = (pair_scores_at(s, t, edge_index, sigmoid=True) > threshold).to(torch.int64)
+    gid = torch.bucketize(src, gp[1:].contiguous(), right=True).clamp_(max=G - 1)
+    tp = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, hit)                     # integer adds: exact in any order
+    edges = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, torch.ones_like(hit))
+    cs = torch.zeros(s.shape[0] + 1, dtype=torch.int64, device=dev)
+    cs[1:] = torch.cumsum(n_above.to(torch.int64), 0)
+    n = gp[1:] - gp[:-1]
+    return torch.stack([tp, cs[gp[1:]] - cs[gp[:-1]], edges, n * n], dim=1)
+
+
 def dense_scores(s, t):
-    """s t^T for `forward_all` (tiny graphs only): rows of t act as the weight of a Linear."""
-    M = t.shape[0]
-    if M not in (16, 32, 64, 128):
-        raise NotImplementedError('forward_all is only provided for 16/32/64/128 target rows')
-    return linear(s, t.contiguous(), None)
+    """s t^T for `forward_all` at any size (raw dot products)."""
+    return pair_scores(s, t, sigmoid=False)
 
 
 class ReconLossFn(torch.autograd.Function):

@@ -5,6 +5,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --data_dir DIR [--checkpoint exp/e/stage_3.pth] --out emb.npz
     python examples/feature_extract.py --type aig --synthetic 4 --out emb.npz
     python examples/feature_extract.py --type aig --synthetic 4 --link_metrics      # + ROC-AUC / AP of the decoder per batch
+    python examples/feature_extract.py --type aig --synthetic 4 --predict_links 8   # + every gate's 8 most probable fan-out targets
 """
 import argparse
 import os
@@ -31,6 +32,9 @@ def main(argv=None):
     ap.add_argument('--out', default='embeddings.npz')
     ap.add_argument('--link_metrics', action='store_true', help='also print ROC-AUC / average precision of the decoder: every batch\'s '
                     'edges ranked against sampled non-edges (Model.link_metrics)')
+    ap.add_argument('--predict_links', type=int, default=0, metavar='K', help='also store every node\'s K most probable successors inside '
+                    'its graph (name/pred_dst, ids local to the graph, -1 past the end; name/pred_score) and print the mean precision and '
+                    'recall of the decoder against the FULL adjacency (Model.predict_links / reconstruction_counts; 1 <= K <= 32)')
     a = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
@@ -45,7 +49,7 @@ def main(argv=None):
         train, val = deepgate.NpzParser(a.data_dir, os.path.join(a.data_dir, 'graphs.npz'), os.path.join(a.data_dir, 'labels.npz'),
                                         a.type, random_shuffle=False, trainval_split=1.0).get_dataset()
         graphs = train + val
-    out, t0, records = {}, time.time(), []
+    out, t0, records, counts = {}, time.time(), [], []
     with torch.no_grad():
         for b0 in range(0, len(graphs), a.batch_size):
             chunk = graphs[b0:b0 + a.batch_size]
@@ -54,8 +58,16 @@ def main(argv=None):
             if a.link_metrics:
                 records.append(model.link_metrics(hs, batch.edge_index, plan=getattr(batch, '_mgv_plan', None)))
             ptr = batch.graph_ptr.tolist()
+            if a.predict_links:
+                idx, score, _ = model.predict_links(hs, a.predict_links, graph_ptr=batch.graph_ptr)
+                counts.append(model.reconstruction_counts(hs, batch.edge_index, batch.graph_ptr))
+                idx, score = idx.cpu().numpy(), score.cpu().numpy()
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if a.predict_links:
+                    loc = idx[ptr[k]:ptr[k + 1]]
+                    out[name + '/pred_dst'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
+                    out[name + '/pred_score'] = score[ptr[k]:ptr[k + 1]]
                 out[name + '/hs'] = hs[ptr[k]:ptr[k + 1]].cpu().numpy()
                 out[name + '/hf'] = hf[ptr[k]:ptr[k + 1]].cpu().numpy()
     torch.cuda.synchronize()
@@ -65,6 +77,11 @@ def main(argv=None):
         pairs = deepgate.ops.read_link_records(records)          # one host read for all batches
         print('[INFO] link prediction over %d batches: AUC %.4f, AP %.4f' % (len(pairs), sum(x for x, _ in pairs) / len(pairs),
                                                                              sum(y for _, y in pairs) / len(pairs)))
+    if a.predict_links:
+        c = torch.cat(counts).double().cpu()                     # [graphs, 4]: TP, predicted positives, edges, ordered pairs
+        prec, rec = c[:, 0] / c[:, 1].clamp(min=1), c[:, 0] / c[:, 2].clamp(min=1)
+        print('[INFO] full-adjacency reconstruction over %d graphs (all n^2 ordered pairs, threshold 0.5): precision %.4f, recall %.4f'
+              % (c.shape[0], float(prec.mean()), float(rec.mean())))
 
 
 if __name__ == '__main__':
