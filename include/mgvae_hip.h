@@ -212,7 +212,20 @@ int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const int32_t* l
                        float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
                        const float* bhh, const float* gh, const float* h_prev, void* stream);
 /* backward sweep, levels in reverse.  ghf[N][H] = dL/dhf from the losses; ghs[N][H] is ADDED to;
- * scratch: dzb[N][2H], alpha[E], dsc[E] (in-CSR edge order).  WvcT[T][2H][3H]. */
+ * scratch: dzb[N][2H], alpha[E], dsc[E] (in-CSR edge order).  WvcT[T][2H][3H].
+ * Written / added to / scratch (both backward entries; tests/test_hip_sweep_reference.py holds them to it):
+ *   hf (forward)   every updated row is WRITTEN; no other row is touched (fp32 entry, round 1: the caller zero-fills hf; bf16x3 entry,
+ *                  round 1: mgv_sweep_zero_inactive writes the other rows; rounds >= 2: the caller copies h_prev into hf)
+ *   ghs            fp32: ADDED to, every row (the caller zero-fills).  bf16x3: WRITTEN, every row (may arrive uninitialised); the rows
+ *                  of never-updated nodes with more than skip_inactive_longer_than consumers are written by mgv_sweep_pull_heavy
+ *   d_attn_u, dWvc, dbvc, dbih, dbhh   ADDED to (fp32: float atomics per tile; bf16x3: one add per entry after fixed-order slab sums)
+ *   d_gh, g_hprev  rows of updated nodes WRITTEN, no other row touched (the caller zero-fills both)
+ *   dzb, alpha, dsc   scratch, max(E, 1) / N * 2H floats, may arrive UNINITIALISED: the row / entries of an updated node are written
+ *                  before any of its sources reads them; those of a never-updated node (gslot 255) are neither written nor read
+ *   scratch, heavy_ws, partial_ws (bf16x3)   may arrive UNINITIALISED: the slab part of scratch is zeroed by the entry itself,
+ *                  every other word is written before it is read
+ * H outside {16, 32, 64} (bf16x3: {32, 64}) is MGV_EUNSUPPORTED from all four entries before anything else is looked at, also for a
+ * sweep without a tile; T > 6 on the bf16x3 entries is MGV_EINVAL (the fp32 entries have no slot cap: ops.FuncSweepFn routes it there). */
 int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                        const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
                        const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src,
@@ -268,8 +281,9 @@ int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t
 /* ---- stand-alone TFMlpAggr (arch/tfmlp.py:31-46: an edge-list call outside the levelised sweep).  Attention pooling over a CSR by
  * destination: zbar[i][W] = sum_j alpha_ij x[j], alpha = softmax over i's sources of u . x[j] (PyG softmax: exp(s - max) / (sum + 1e-16));
  * the module's message is W_v zbar + b_v [deg > 0] (mgv_linear_*).  W = row width (2 * dim_hidden) in {32, 64, 128};
- * mstat / inv [N]: the softmax statistics the backward re-uses.  Backward: dx [N][W] and du [W] are ADDED to with float atomics
- * (the caller zeroes them; this entry is not on the train step). */
+ * mstat / inv [N]: the softmax statistics the backward re-uses (an empty list: zbar = 0, mstat = 0, inv = 1 / 1e-16); all three are
+ * WRITTEN for every node.  Backward: dx [rows of x][W] and du [W] are ADDED to with float atomics
+ * (the caller zeroes them; this entry is not on the train step).  Any other W is MGV_EUNSUPPORTED before anything else is looked at. */
 int mgv_attn_pool_fwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,
                       float* zbar, float* mstat, float* inv, void* stream);
 int mgv_attn_pool_bwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,

@@ -85,6 +85,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_pool_bwd(int64_t N, const int
 
 extern "C" int mgv_attn_pool_fwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,
                                  float* zbar, float* mstat, float* inv, void* stream) {
+    if (W != 32 && W != 64 && W != 128) return MGV_EUNSUPPORTED;      // before W / 4 divides anything: refused before anything is launched
     MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv);
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -97,6 +98,7 @@ extern "C" int mgv_attn_pool_fwd(int W, int64_t N, const int32_t* in_ptr, const 
 extern "C" int mgv_attn_pool_bwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,
                                  const float* zbar, const float* mstat, const float* inv, const float* dzbar, float* dx, float* du,
                                  void* stream) {
+    if (W != 32 && W != 64 && W != 128) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv && dzbar && dx && du);
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);

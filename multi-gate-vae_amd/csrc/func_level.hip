@@ -470,6 +470,8 @@ extern "C" int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const
                                   const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
                                   float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
                                   const float* bhh, const float* gh, const float* h_prev, void* stream) {
+    // the width first: an empty sweep never reaches the level loop's switch, and the backward divides by H / 4 behind its loop
+    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && bvc && bih && bhh && in_ptr);
     MGV_CHECK_ARG((gh == nullptr) == (h_prev == nullptr));
     mgv::LevelArgs a{};
@@ -503,6 +505,7 @@ extern "C" int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const
                                   const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
                                   float* dWvc, float* dbvc, float* dbih, float* dbhh, const float* gh, const float* h_prev,
                                   float* d_gh, float* g_hprev, void* stream) {
+    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && WvcT && bvc && bih && bhh);
     MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);
     MGV_CHECK_ARG(gh == nullptr ? (!h_prev && !d_gh && !g_hprev) : (h_prev && d_gh && g_hprev));

@@ -667,6 +667,7 @@ extern "C" int mgv_func_sweep_fwd_x3(int H, int64_t N, int T, int num_levels, co
                                      const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
                                      const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh,
                                      const float* gh, const float* h_prev, void* stream) {
+    if (H != 32 && H != 64) return MGV_EUNSUPPORTED;      // the width first, also for a sweep without a tile
     MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && wpack_bf16 && bvc && bih && bhh && in_ptr);
     MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
     mgv::LevelX3Args a{};
@@ -707,6 +708,8 @@ extern "C" int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, co
                                      const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host,
                                      const int32_t* heavy_lvl_seg_ptr_host, float* heavy_ws, int skip_active_longer_than,
                                      const float* gh, const float* h_prev, float* d_gh, float* g_hprev, void* stream) {
+    // the width first: the heavy pre-pass in front of a level is launched for H = 64 whenever H != 32, and H / 4 divides behind the loops
+    if (H != 32 && H != 64) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && n_active >= 0 && level_tile_ptr_host && hs && hf &&
                   attn_u && wpack_bf16 && bvc && bih && bhh);
     MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);

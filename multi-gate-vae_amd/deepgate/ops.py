@@ -797,9 +797,13 @@ def _sweep_bwd_prep(plan, T, H, dev):
     return scratch, stp, hv, ha
 
 
-def _sweep_x3(H):
-    """The bf16x3 level kernels serve this width (else the exact-fp32 ones: H = 16, MGV_PRECISION=f32, MGV_SWEEP_X3=0)."""
-    return use_x3(H) and os.environ.get('MGV_SWEEP_X3', '1') != '0'
+SWEEP_X3_MAX_SLOTS = 6          # csrc/func_level_x3_common.h kMaxSlots: the bf16x3 level kernels keep every slot's attention vector in LDS
+
+
+def _sweep_x3(H, T=1):
+    """The bf16x3 level kernels serve this width and slot count (else the exact-fp32 ones, which have no slot cap: H = 16,
+    T > SWEEP_X3_MAX_SLOTS, MGV_PRECISION=f32, MGV_SWEEP_X3=0)."""
+    return use_x3(H) and T <= SWEEP_X3_MAX_SLOTS and os.environ.get('MGV_SWEEP_X3', '1') != '0'
 
 
 GROUPED_ROUND = True            # rounds >= 2: W_hh h_prev + b_hh of every updated gate as one grouped Linear (RoundGhFn); False: per gate type on the plain kernels
@@ -848,7 +852,7 @@ class FuncSweepFn(torch.autograd.Function):
             ghd = check(gh.detach().contiguous(), F32, 'gh')
             assert ghd.shape == (N, 3 * H) and hp.shape == (N, H)
         ltp = (_hip.ctypes.c_int32 * len(plan.level_tile_ptr))(*plan.level_tile_ptr)
-        wpack = sweep_wpack(par[1]) if _sweep_x3(H) else None
+        wpack = sweep_wpack(par[1]) if _sweep_x3(H, T) else None
         if hp is not None:
             hf = hp.clone()                  # never-updated rows keep their state; every updated row is rewritten by its level
         elif wpack is not None:
