@@ -175,6 +175,10 @@ class GraphPlan:
             hit = cache[reverse] = (class_id, (idx | (class_id[idx.long()] << 24)).to(torch.int32).contiguous())
         return hit[1]
 
+    def tagged_fits(self, n_classes):
+        """Whether `tagged_idx` entries can hold every node id (24 bits) and every row of a table of `n_classes` rows (8 bits)."""
+        return self.N < (1 << 24) and n_classes <= 256
+
     def count_self_loops(self):
         """Edges (v, v): the negative sampler draws E - self loops + N pairs (sampling.negative_sampling_device).  One host read-back,
         kept on the plan."""
@@ -204,7 +208,7 @@ class GraphPlan:
                 return self                  # the quotient stages replace the first-stage table and its tagged lists
         if xcls is not None and self.N > 0:
             first = self.first_stage_classes(xcls)
-            if first is not None and first[1] <= 256 and self.N < (1 << 24):
+            if first is not None and self.tagged_fits(first[1]):
                 self.tagged_idx(True, first[0])
         return self
 

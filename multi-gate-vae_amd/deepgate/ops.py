@@ -3,6 +3,8 @@
 backward kernels into the reference's Python operator surface.  PyTorch supplies device memory,
 streams and the autograd tape; all arithmetic on [N,*] data happens in libmgvae_hip.so.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _hip
@@ -91,10 +93,7 @@ def _heavy_args(heavy, H, device):
     if heavy is None or heavy[0] == 0:
         return 0, None, None
     n, nodes = heavy
-    hw = _WS.get(('heavy', str(device)))
-    if hw is None or hw.numel() < 2 * n * H:
-        hw = _WS[('heavy', str(device))] = torch.empty(2 * n * H, dtype=F32, device=device)
-    return n, ptr(nodes), ptr(hw)
+    return n, ptr(nodes), ptr(workspace(2 * n * H, device, tag='heavy'))     # (its own buffer: the bwd2 slab is live in the same launch)
 
 
 def struct_stage_fwd(h_in, nbr_ptr, nbr_idx, xcls, xtab, Wc, bc, Whh, bhh, ln_w, ln_b, out=None, wpack=None, heavy=None, table_own=None, n_rows=None,
@@ -131,18 +130,15 @@ def struct_stage_fwd(h_in, nbr_ptr, nbr_idx, xcls, xtab, Wc, bc, Whh, bhh, ln_w,
 # The bf16x3 half-round backward at H = 64 is struct_stage_bwd2_x3.hip (register-resident recompute weights, transposed products,
 # slab-reduced deterministic parameter gradients); the first kernel (struct_stage_x3.hip) serves H = 32 only (tools/bench_stage.py
 # still times both through the C ABI).
-TABLE_MODE = True                 # half round 2 of an encoder reads the (degree, class) table directly
 QUOTIENT = os.environ.get('MGV_QUOTIENT', '1') != '0'         # early half rounds on one row per colour (GraphPlan.quotient)
 _WS = {}
 
 
-
-
-
-def workspace(nfloats, device, dtype=F32):
+def workspace(nfloats, device, dtype=F32, tag=None):
     """Scratch for the deterministic cross-workgroup sums (per-workgroup partial rows, csrc/mgv_slab.h): one growing buffer
-    per (device, stream, dtype); launches on a stream are ordered, so consecutive users may share it."""
-    key = (str(device), _hip.stream().value if torch.device(device).type == 'cuda' else 0, dtype)
+    per (device, stream, dtype, tag); launches on a stream are ordered, so consecutive users may share it.  Scratch that one
+    launch uses next to the untagged buffer (heavy-row sums) asks for a buffer of its own by `tag`."""
+    key = (str(device), _hip.stream().value if torch.device(device).type == 'cuda' else 0, dtype, tag)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nfloats:
         buf = _WS[key] = torch.empty(max(int(nfloats), 1), dtype=dtype, device=device)
@@ -173,37 +169,26 @@ def struct_stage_bwd(h_in, nbr_ptr, nbr_idx, xcls, xtab, Wc, bc, Whh, bhh, ln_w,
     if table_own is not None:
         N = table_own.numel()
     check(gy_direct, F32, 'gy_direct'); check(gy_agg, F32, 'gy_agg')
-    if use_x3(H) and H == 64:
-        g_direct = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
-        g_agg = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
+    x3, dev = use_x3(H), h_in.device
+    assert x3 or table_own is None, 'own rows through an index need the bf16x3 kernels'
+    assert (x3 and H == 64) or table_own is None or not tagged, 'table mode needs the H = 64 bf16x3 backward'
+    g_direct = torch.empty(N, H, dtype=F32, device=dev) if need_input_grad else None
+    g_agg = torch.empty(N, H, dtype=F32, device=dev) if need_input_grad else None
+    if x3:
         wpack = stage_wpack(Wc, Whh) if wpack is None else wpack
-        ws = _stage_ws(H, N, h_in.device)
-        _hip.call('mgv_struct_stage_bwd2_x3', H, N, ptr(h_in), ptr(nbr_ptr), ptr(nbr_idx), ptr(xcls), ptr(xtab),
-                  xtab.shape[0], ptr(wpack), ptr(bc), ptr(bhh), ptr(ln_w), ptr(ln_b), LN_EPS, ptr(gy_direct),
-                  ptr(gy_agg), ptr(g_direct), ptr(g_agg), ptr(grads['dWc']), ptr(grads['dbc']), ptr(grads['dWhh']),
-                  ptr(grads['dbhh']), ptr(grads['dxtab']), ptr(grads.get('dln_w')), ptr(grads.get('dln_b')),
-                  ptr(ws), ws.numel(), *_heavy_args(heavy, H, h_in.device), ptr(table_own), int(bool(tagged)), ptr(stats))
-        return g_direct, g_agg
-    assert table_own is None or not tagged, 'table mode needs the H = 64 bf16x3 backward'
-    if use_x3(H):
-        g_direct = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
-        g_agg = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
-        wpack = stage_wpack(Wc, Whh) if wpack is None else wpack
-        _hip.call('mgv_struct_stage_bwd_x3', H, N, ptr(h_in), ptr(nbr_ptr), ptr(nbr_idx), ptr(xcls), ptr(xtab),
-                  xtab.shape[0], ptr(wpack), ptr(bc), ptr(bhh), ptr(ln_w), ptr(ln_b), LN_EPS, ptr(gy_direct),
-                  ptr(gy_agg), ptr(g_direct), ptr(g_agg), ptr(grads['dWc']), ptr(grads['dbc']), ptr(grads['dWhh']),
-                  ptr(grads['dbhh']), ptr(grads['dxtab']), ptr(grads.get('dln_w')), ptr(grads.get('dln_b')), *_heavy_args(heavy, H, h_in.device), ptr(table_own), 0)
-        return g_direct, g_agg
-    assert table_own is None, 'own rows through an index need the bf16x3 kernels'
-    WcT = Wc.t().contiguous()
-    WhhT = Whh.t().contiguous()
-    g_direct = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
-    g_agg = torch.empty(N, H, dtype=F32, device=h_in.device) if need_input_grad else None
-    _hip.call('mgv_struct_stage_bwd', H, N, ptr(h_in), ptr(nbr_ptr), ptr(nbr_idx), ptr(xcls), ptr(xtab),
-              xtab.shape[0], ptr(Wc), ptr(WcT), ptr(bc), ptr(Whh), ptr(WhhT), ptr(bhh), ptr(ln_w), ptr(ln_b),
-              LN_EPS, ptr(gy_direct), ptr(gy_agg), ptr(g_direct), ptr(g_agg), ptr(grads['dWc']), ptr(grads['dbc']),
-              ptr(grads['dWhh']), ptr(grads['dbhh']), ptr(grads['dxtab']), ptr(grads.get('dln_w')),
-              ptr(grads.get('dln_b')))
+        weights = (ptr(wpack), ptr(bc), ptr(bhh))
+    else:
+        weights = (ptr(Wc), ptr(Wc.t().contiguous()), ptr(bc), ptr(Whh), ptr(Whh.t().contiguous()), ptr(bhh))
+    head = (H, N, ptr(h_in), ptr(nbr_ptr), ptr(nbr_idx), ptr(xcls), ptr(xtab), xtab.shape[0], *weights, ptr(ln_w), ptr(ln_b), LN_EPS,
+            ptr(gy_direct), ptr(gy_agg), ptr(g_direct), ptr(g_agg), ptr(grads['dWc']), ptr(grads['dbc']), ptr(grads['dWhh']),
+            ptr(grads['dbhh']), ptr(grads['dxtab']), ptr(grads.get('dln_w')), ptr(grads.get('dln_b')))
+    if x3 and H == 64:
+        ws = _stage_ws(H, N, dev)
+        _hip.call('mgv_struct_stage_bwd2_x3', *head, ptr(ws), ws.numel(), *_heavy_args(heavy, H, dev), ptr(table_own), int(bool(tagged)), ptr(stats))
+    elif x3:
+        _hip.call('mgv_struct_stage_bwd_x3', *head, *_heavy_args(heavy, H, dev), ptr(table_own), 0)
+    else:
+        _hip.call('mgv_struct_stage_bwd', *head)
     return g_direct, g_agg
 
 
@@ -219,10 +204,60 @@ def _seg_sums(H, tables, items, direct, agg=None, nbr_ptr=None, nbr_idx=None):
     return buf[:tables['C']]
 
 
+# One half round of StructEncoderFn, as half_round_schedule lays it out:
+#   rev, rows            direction (True: over the out-CSR), and how many rows the stage computes
+#   ptr, idx, xcls       the neighbour lists and class bytes of those rows;  heavy: (count, rows with long lists) or None
+#   table_own, tagged, n_rows   as struct_stage_fwd takes them
+#   src                  its input: 'ones' [rows, H] | 'prev' the previous output, read in place | 'stacked' [own rows | previous
+#                        output], own rows = previous output rows `own` (colour stages on the fp32 kernels)
+#   expand               class ids [N] by which its output table is expanded to N rows behind it, or None
+#   grad, gsrc           how the gradient reaches it on the way back: 'rows' per node, as the stage after it left it | 'pairs'
+#                        summed per (degree, class) pair (cid, per-node lists) | 'sum_levels' summed per colour over the per-node
+#                        lists (the last colour stage: (order, levels), per-node lists) | 'above' from the colour stage after it,
+#                        summed over the representatives that own a colour and the list entries that name it
+HalfRound = namedtuple('HalfRound', 'rev rows ptr idx xcls heavy table_own tagged n_rows src own expand grad gsrc',
+                       defaults=(None, True, None, 'prev', None, None, 'rows', None))
+
+
+def half_round_schedule(plan, xcls, rounds, H, x3, first, quot):
+    """The 2R half rounds of one MultiGCNEncoder as HalfRound records: forward walks them, backward walks them in reverse.
+    `first` = plan.first_stage_classes(xcls) or None, `quot` = plan.quotient(xcls, 2R) or empty, `x3`: the bf16x3 kernels serve H.
+    node_state = ones (digae_layer.py:260), so the first half round sees identical rows: one kernel row per (degree, class) pair
+    does for all nodes of the pair (`first`), and while the rows of a half round are few distinct ones it runs on one
+    representative row per colour (`quot`: stages 0..q-1, the table of the last one expanded to N rows).  The rest runs per node."""
+    N, quot = plan.N, list(quot or [])[:2 * rounds]
+    q = len(quot)
+    # table mode for the half round after the pair one: bf16x3 H = 64 kernels read the pair table through tagged entries, it is never expanded
+    table_mode = not q and first is not None and x3 and H == 64 and plan.tagged_fits(first[1])
+    out = []
+    for k in range(2 * rounds):
+        rev = k % 2 == 1
+        p, i = plan.csr(rev)
+        if k < q:
+            st = quot[k]
+            if k + 1 < q:
+                grad, gsrc = 'above', tuple(quot[k + 1][f] for f in ('own_levels', 'own_rows', 'ent_levels', 'ent_rows'))
+            else:
+                grad, gsrc = 'sum_levels', (st.get('sum_levels'), p, i)
+            # the bf16x3 kernels read the previous table in place: own rows through own32, lists name its rows
+            lists = (dict(idx=st['ent_idx'], table_own=st['own32'], tagged=False) if x3 else
+                     dict(idx=st['idx'], n_rows=st['C'], src='stacked', own=st['own']))
+            out.append(HalfRound(rev, st['C'], st['ptr'], xcls=st['xcls'], heavy=st['heavy'], expand=st['cid'] if k + 1 == q else None,
+                                 grad=grad, gsrc=gsrc, **lists))
+        elif k == 0 and first is not None:
+            cid, C, tp, ti, tx = first
+            out.append(HalfRound(rev, C, tp, ti, tx, None, src='ones', expand=None if table_mode else cid, grad='pairs', gsrc=(cid, p, i)))
+        elif k == 1 and table_mode:
+            out.append(HalfRound(rev, N, p, plan.tagged_idx(rev, first[0]), xcls, plan.heavy(rev), table_own=first[0]))
+        else:
+            out.append(HalfRound(rev, N, p, i, xcls, plan.heavy(rev), src='ones' if k == 0 else 'prev'))
+    return out
+
+
 class StructEncoderFn(torch.autograd.Function):
     """All 2R half rounds of one MultiGCNEncoder (digae_layer.py:257-277) as one autograd node.
 
-    Forward keeps the input state of every half round (2R x [N,H]); backward walks them in reverse
+    Forward keeps the input state of every half round (per-node stages: 2R x [N,H]); backward walks them in reverse
     and hands each stage's aggregate gradient to the previous stage's gather (consecutive half
     rounds use opposite CSRs), so no scatter pass exists.
     Inputs: the composed per-direction weights (forward half: *_f, reversed half: *_r) and the shared
@@ -237,169 +272,63 @@ class StructEncoderFn(torch.autograd.Function):
         lw = ln_w.detach().contiguous() if ln_w is not None else None
         lb = ln_b.detach().contiguous() if ln_b is not None else None
         packs = (stage_wpack(par[1], par[3]), stage_wpack(par[6], par[8])) if use_x3(H) else (None, None)
-        # node_state = ones (digae_layer.py:260): the first half round sees identical rows, one kernel row per
-        # (degree, feature class) pair does for all nodes of the pair
-        # quotient stages: while the rows of a half round are few distinct ones, it runs on one representative row per colour
         quot = plan.quotient(xcls, 2 * rounds) if (QUOTIENT and FIRST_STAGE_TABLE and rounds > 0 and N > 0 and Whh_f.is_cuda) else []
-        if quot:
-            return StructEncoderFn._forward_quotient(ctx, plan, xcls, rounds, par, lw, lb, packs, quot)
-        first = plan.first_stage_classes(xcls) if (FIRST_STAGE_TABLE and rounds > 0 and N > 0) else None
-        h = None if first is not None else torch.ones(N, H, dtype=F32, device=dev)
-        # table mode for the half round after the table one: bf16x3 H = 64 kernels, node ids and table rows fit a tagged 32-bit entry
-        table_mode = first is not None and use_x3(H) and H == 64 and N < (1 << 24) and first[1] <= 256 and TABLE_MODE
-        states, stats = [], []
+        first = plan.first_stage_classes(xcls) if (not quot and FIRST_STAGE_TABLE and rounds > 0 and N > 0) else None
+        sched = half_round_schedule(plan, xcls, rounds, H, use_x3(H), first, quot)
         keep_stats = lw is not None and use_x3(H) and H == 64      # LayerNorm statistics kept for the bwd2 kernel
-        for _ in range(rounds):
-            for rev in (False, True):
-                p, i = plan.csr(rev)
-                w = par[5:] if rev else par[:5]
-                states.append(h)
-                stats.append(torch.empty((first[1] if h is None else N), 2, dtype=F32, device=dev) if keep_stats else None)
-                if h is None:
-                    cid, C, tp, ti, tx = first
-                    table = struct_stage_fwd(torch.ones(C, H, dtype=F32, device=dev), tp, ti, tx, w[0], w[1], w[2], w[3], w[4],
-                                             lw, lb, wpack=packs[0], stats_out=stats[-1])
-                    if table_mode:
-                        h = ('table', table)     # never expanded to N rows: the next half round reads the table through tagged entries
-                    else:
-                        h = torch.empty(N, H, dtype=F32, device=dev)
-                        _hip.call('mgv_class_expand', H, N, ptr(table), ptr(cid), ptr(h))
-                elif isinstance(h, tuple):
-                    h = struct_stage_fwd(h[1], p, plan.tagged_idx(rev, first[0]), xcls, w[0], w[1], w[2], w[3], w[4], lw, lb, wpack=packs[int(rev)],
-                                         heavy=plan.heavy(rev), table_own=first[0], stats_out=stats[-1])
-                else:
-                    h = struct_stage_fwd(h, p, i, xcls, w[0], w[1], w[2], w[3], w[4], lw, lb, wpack=packs[int(rev)], heavy=plan.heavy(rev),
-                                         stats_out=stats[-1])
-        ctx.plan, ctx.xcls, ctx.rounds, ctx.packs, ctx.first = plan, xcls, rounds, packs, first
-        ctx.par, ctx.lw, ctx.lb, ctx.states, ctx.stats = par, lw, lb, states, stats
-        ctx.quot = None
-        return h
-
-    @staticmethod
-    def _forward_quotient(ctx, plan, xcls, rounds, par, lw, lb, packs, quot):
-        """Half rounds 1..len(quot) on one row per colour (inputs: the previous stage's table, stacked behind the representatives'
-        own rows), the table of the last one expanded to N rows, the remaining half rounds as usual."""
-        N, H, dev = plan.N, par[3].shape[1], par[3].device
         states, stats = [], []
-        keep_stats = lw is not None and use_x3(H) and H == 64
-        table = torch.ones(1, H, dtype=F32, device=dev)
-        h = None
-        for k in range(2 * rounds):
-            rev = k % 2 == 1
-            w = par[5:] if rev else par[:5]
-            if k < len(quot):
-                st = quot[k]
-                stats.append(torch.empty(st['C'], 2, dtype=F32, device=dev) if keep_stats else None)
-                if use_x3(H):
-                    # the bf16x3 kernels read the previous table in place: own rows through st['own32'], lists name its rows
-                    states.append(table)
-                    table = struct_stage_fwd(table, st['ptr'], st['ent_idx'], st['xcls'], w[0], w[1], w[2], w[3], w[4], lw, lb, wpack=packs[int(rev)],
-                                             heavy=st['heavy'], table_own=st['own32'], tagged=False, stats_out=stats[-1])
-                else:
-                    h_cat = torch.cat([table.index_select(0, st['own']), table])
-                    states.append(h_cat)
-                    table = struct_stage_fwd(h_cat, st['ptr'], st['idx'], st['xcls'], w[0], w[1], w[2], w[3], w[4], lw, lb, wpack=packs[int(rev)],
-                                             heavy=st['heavy'], n_rows=st['C'], stats_out=stats[-1])
-                if k + 1 == len(quot) or k + 1 == 2 * rounds:
-                    h = torch.empty(N, H, dtype=F32, device=dev)
-                    _hip.call('mgv_class_expand', H, N, ptr(table), ptr(st['cid']), ptr(h))
-            else:
-                p, i = plan.csr(rev)
-                states.append(h)
-                stats.append(torch.empty(N, 2, dtype=F32, device=dev) if keep_stats else None)
-                h = struct_stage_fwd(h, p, i, xcls, w[0], w[1], w[2], w[3], w[4], lw, lb, wpack=packs[int(rev)], heavy=plan.heavy(rev),
-                                     stats_out=stats[-1])
-        ctx.plan, ctx.xcls, ctx.rounds, ctx.packs, ctx.first = plan, xcls, rounds, packs, None
+        h = torch.ones(1, H, dtype=F32, device=dev) if quot else None      # the table the first colour stage reads
+        for r in sched:
+            if r.src == 'ones':
+                h = torch.ones(r.rows, H, dtype=F32, device=dev)
+            elif r.src == 'stacked':
+                h = torch.cat([h.index_select(0, r.own), h])
+            states.append(None if r.grad == 'pairs' else h)      # (a few rows of ones: backward makes them again)
+            stats.append(torch.empty(r.rows, 2, dtype=F32, device=dev) if keep_stats else None)
+            h = struct_stage_fwd(h, r.ptr, r.idx, r.xcls, *(par[5:] if r.rev else par[:5]), lw, lb, wpack=packs[int(r.rev)], heavy=r.heavy,
+                                 table_own=r.table_own, n_rows=r.n_rows, stats_out=stats[-1], tagged=r.tagged)
+            if r.expand is not None:
+                table, h = h, torch.empty(N, H, dtype=F32, device=dev)
+                _hip.call('mgv_class_expand', H, N, ptr(table), ptr(r.expand), ptr(h))
+        if not sched:
+            h = torch.ones(N, H, dtype=F32, device=dev)
+        ctx.plan, ctx.packs, ctx.sched = plan, packs, sched
         ctx.par, ctx.lw, ctx.lb, ctx.states, ctx.stats = par, lw, lb, states, stats
-        ctx.quot = quot
         return h
-
-    @staticmethod
-    def _backward_quotient(ctx, gy):
-        plan, xcls, par, lw, lb, quot = ctx.plan, ctx.xcls, ctx.par, ctx.lw, ctx.lb, ctx.quot
-        H, dev = gy.shape[1], gy.device
-        acc = {}
-        for tag, w in (('f', par[:5]), ('r', par[5:])):
-            acc[tag] = {'dxtab': torch.zeros_like(w[0]), 'dWc': torch.zeros_like(w[1]), 'dbc': torch.zeros_like(w[2]),
-                        'dWhh': torch.zeros_like(w[3]), 'dbhh': torch.zeros_like(w[4])}
-        dlw = torch.zeros_like(lw) if lw is not None else None
-        dlb = torch.zeros_like(lb) if lb is not None else None
-        g_direct, g_agg = gy, None
-        gsum = None                                  # per-colour gradient sums entering the quotient stage below
-        for k in range(2 * ctx.rounds - 1, -1, -1):
-            rev = k % 2 == 1
-            w = par[5:] if rev else par[:5]
-            g = dict(acc['r' if rev else 'f'])
-            g['dln_w'], g['dln_b'] = dlw, dlb
-            if k >= len(quot):
-                p, i = plan.csr(rev)
-                g_direct, g_agg = struct_stage_bwd(ctx.states[k], p, i, xcls, w[0], w[1], w[2], w[3], w[4], lw, lb, g_direct, g_agg, g,
-                                                   need_input_grad=(k > 0), wpack=ctx.packs[int(rev)], heavy=plan.heavy(rev), stats=ctx.stats[k])
-                continue
-            st = quot[k]
-            if gsum is None:
-                # the last quotient stage: per-colour sums of the per-node gradient (g_direct + the pull of g_agg over this stage's
-                # lists), colour runs cut into segments, partial rows summed level by level (mgv_seg_sum: list order, no atomics)
-                p, i = plan.csr(rev)
-                order, levels = st['sum_levels']
-                gsum = _seg_sums(H, levels, order, g_direct, g_agg, p, i)
-            if use_x3(H):
-                gd_c, ga_c = struct_stage_bwd(ctx.states[k], st['ptr'], st['ent_idx'], st['xcls'], w[0], w[1], w[2], w[3], w[4], lw, lb, gsum, None, g,
-                                              need_input_grad=(k > 0), wpack=ctx.packs[int(rev)], heavy=st['heavy'], table_own=st['own32'], tagged=False,
-                                              stats=ctx.stats[k])
-            else:
-                gd_c, ga_c = struct_stage_bwd(ctx.states[k], st['ptr'], st['idx'], st['xcls'], w[0], w[1], w[2], w[3], w[4], lw, lb, gsum, None, g,
-                                              need_input_grad=(k > 0), wpack=ctx.packs[int(rev)], heavy=st['heavy'], n_rows=st['C'], stats=ctx.stats[k])
-            if k > 0:
-                # colour sums for stage k-1: a colour there collects the own-row gradients of the representatives that own it and the
-                # aggregate gradients of those that list it (deterministic gathers over the colour-level lists)
-                gsum = _seg_sums(H, st['own_levels'], st['own_rows'], gd_c) + _seg_sums(H, st['ent_levels'], st['ent_rows'], ga_c)
-        ctx.states = ctx.stats = None
-        f, r = acc['f'], acc['r']
-        return (None, None, None, f['dxtab'], f['dWc'], f['dbc'], f['dWhh'], f['dbhh'],
-                r['dxtab'], r['dWc'], r['dbc'], r['dWhh'], r['dbhh'], dlw, dlb)
 
     @staticmethod
     def backward(ctx, gy):
-        plan, xcls, par, lw, lb = ctx.plan, ctx.xcls, ctx.par, ctx.lw, ctx.lb
-        gy = gy.contiguous()
-        if ctx.quot:
-            return StructEncoderFn._backward_quotient(ctx, gy)
-        acc = {}
-        for tag, w in (('f', par[:5]), ('r', par[5:])):
-            acc[tag] = {'dxtab': torch.zeros_like(w[0]), 'dWc': torch.zeros_like(w[1]), 'dbc': torch.zeros_like(w[2]),
-                        'dWhh': torch.zeros_like(w[3]), 'dbhh': torch.zeros_like(w[4])}
+        plan, par, lw, lb = ctx.plan, ctx.par, ctx.lw, ctx.lb
+        H, dev = gy.shape[1], gy.device
         dlw = torch.zeros_like(lw) if lw is not None else None
         dlb = torch.zeros_like(lb) if lb is not None else None
-        g_direct, g_agg = gy, None
-        k = len(ctx.states) - 1
-        for _ in range(ctx.rounds):
-            for rev in (True, False):
-                p, i = plan.csr(rev)
-                w = par[5:] if rev else par[:5]
-                g = dict(acc['r' if rev else 'f'])
-                g['dln_w'], g['dln_b'] = dlw, dlb
-                if k == 0 and ctx.first is not None:
-                    # parameter gradients are linear in the incoming gradient: sum it per (degree, class) pair,
-                    # then one backward row per pair
-                    cid, C, tp, ti, tx = ctx.first
-                    H = g_direct.shape[1]
-                    gsum = torch.zeros(C, H, dtype=F32, device=g_direct.device)
-                    ws = workspace(_hip.call_value('mgv_class_pull_sum_ws_floats', H, plan.N, C), g_direct.device)
-                    _hip.call('mgv_class_pull_sum', H, plan.N, ptr(g_direct), ptr(g_agg), ptr(p), ptr(i), ptr(cid), C, ptr(gsum), ptr(ws), ws.numel())
-                    struct_stage_bwd(torch.ones(C, H, dtype=F32, device=g_direct.device), tp, ti, tx, w[0], w[1], w[2], w[3], w[4],
-                                     lw, lb, gsum, None, g, need_input_grad=False, wpack=ctx.packs[0], stats=ctx.stats[k])
-                elif isinstance(ctx.states[k], tuple):
-                    g_direct, g_agg = struct_stage_bwd(ctx.states[k][1], p, plan.tagged_idx(rev, ctx.first[0]), xcls, w[0], w[1], w[2], w[3], w[4],
-                                                       lw, lb, g_direct, g_agg, g, need_input_grad=(k > 0), wpack=ctx.packs[int(rev)],
-                                                       heavy=plan.heavy(rev), table_own=ctx.first[0], stats=ctx.stats[k])
-                else:
-                    g_direct, g_agg = struct_stage_bwd(ctx.states[k], p, i, xcls, w[0], w[1], w[2], w[3], w[4], lw, lb,
-                                                       g_direct, g_agg, g, need_input_grad=(k > 0), wpack=ctx.packs[int(rev)],
-                                                       heavy=plan.heavy(rev), stats=ctx.stats[k])
-                k -= 1
+        acc = [dict(zip(('dxtab', 'dWc', 'dbc', 'dWhh', 'dbhh', 'dln_w', 'dln_b'), _zeros_like_params(*w) + [dlw, dlb])) for w in (par[:5], par[5:])]
+        g_direct, g_agg = gy.contiguous(), None
+        for k in range(len(ctx.sched) - 1, -1, -1):
+            r, h_in = ctx.sched[k], ctx.states[k]
+            if r.grad == 'pairs':
+                # parameter gradients are linear in the incoming gradient: sum it per (degree, class) pair,
+                # then one backward row per pair
+                cid, p, i = r.gsrc
+                gsum = torch.zeros(r.rows, H, dtype=F32, device=dev)
+                ws = workspace(_hip.call_value('mgv_class_pull_sum_ws_floats', H, plan.N, r.rows), dev)
+                _hip.call('mgv_class_pull_sum', H, plan.N, ptr(g_direct), ptr(g_agg), ptr(p), ptr(i), ptr(cid), r.rows, ptr(gsum), ptr(ws), ws.numel())
+                g_direct, g_agg, h_in = gsum, None, torch.ones(r.rows, H, dtype=F32, device=dev)
+            elif r.grad == 'sum_levels':
+                # the last colour stage: per-colour sums of the per-node gradient (g_direct + the pull of g_agg over this stage's
+                # lists), colour runs cut into segments, partial rows summed level by level (mgv_seg_sum: list order, no atomics)
+                (order, levels), p, i = r.gsrc
+                g_direct, g_agg = _seg_sums(H, levels, order, g_direct, g_agg, p, i), None
+            elif r.grad == 'above':
+                # a colour collects the own-row gradients of the representatives above that own it and the aggregate gradients
+                # of those that list it (deterministic gathers over the colour-level lists)
+                own_levels, own_rows, ent_levels, ent_rows = r.gsrc
+                g_direct, g_agg = _seg_sums(H, own_levels, own_rows, g_direct) + _seg_sums(H, ent_levels, ent_rows, g_agg), None
+            g_direct, g_agg = struct_stage_bwd(h_in, r.ptr, r.idx, r.xcls, *(par[5:] if r.rev else par[:5]), lw, lb, g_direct, g_agg, acc[int(r.rev)],
+                                               need_input_grad=(k > 0), wpack=ctx.packs[int(r.rev)], heavy=r.heavy, table_own=r.table_own,
+                                               n_rows=r.n_rows, stats=ctx.stats[k], tagged=r.tagged)
         ctx.states = ctx.stats = None
-        f, r = acc['f'], acc['r']
+        f, r = acc
         return (None, None, None, f['dxtab'], f['dWc'], f['dbc'], f['dWhh'], f['dbhh'],
                 r['dxtab'], r['dWc'], r['dbc'], r['dWhh'], r['dbhh'], dlw, dlb)
 
@@ -789,10 +718,7 @@ def _sweep_bwd_prep(plan, T, H, dev):
         i32a = _hip.ctypes.c_int32
         kp = (i32a * len(hav['lvl_k_ptr']))(*hav['lvl_k_ptr'])
         sp_ = (i32a * len(hav['lvl_seg_ptr']))(*hav['lvl_seg_ptr'])
-        need = (hav['K'] + hav['S']) * 2 * H          # its own buffer: it must outlive the launcher call's other scratch users
-        hws = _WS.get(('heavy_active', str(dev)))
-        if hws is None or hws.numel() < need:
-            hws = _WS[('heavy_active', str(dev))] = torch.empty(need, dtype=F32, device=dev)
+        hws = workspace((hav['K'] + hav['S']) * 2 * H, dev, tag='heavy_active')      # its own buffer: it must outlive the launcher call's other scratch users
         ha = (hav['K'], ptr(hav['nodes']), ptr(hav['node_seg_ptr']), ptr(hav['seg_e0']), ptr(hav['seg_e1']), kp, sp_, ptr(hws), plan.HEAVY_ROW)
     return scratch, stp, hv, ha
 
