@@ -334,6 +334,23 @@ int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, const float* t
  * and end at N (its two ends are read back: the only blocking step, skipped for NULL). */
 int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k, int sigmoid,
                   float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream);
+/* the reconstructed graph of forward_all (digae_layer.py:31-33, digae_model.py:118-122) as per-row lists, without an N x N array: the
+ * candidates of row u (as in mgv_pair_topk: u's own graph, without v = u when skip_self) whose reported score is > threshold, the very
+ * decision behind n_above.  A NaN score is never selected.  Two passes around the caller's exclusive scan:
+ * count (digae_layer.py:31-33, digae_model.py:118-122): n_sel[N] int32 is written for every row and equals n_above of mgv_pair_topk for
+ * the same arguments.  Refused before anything is launched: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); a bad row stride or
+ * alignment, N > 2^31 - 1, a graph_ptr that does not start at 0 and end at N (read back as in mgv_pair_topk, NULL skips it): MGV_EINVAL.
+ * N = 0 launches nothing. */
+int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                          float threshold, int skip_self, int32_t* n_sel, void* stream);
+/* fill (digae_layer.py:31-33, digae_model.py:118-122): row u's selected columns as batch-wide int32 node ids in ascending order at
+ * col[row_ptr[u] ..], with score[cap] (or NULL) the reported score beside each.  row_ptr [N+1] int64 on the device (a batch can select more
+ * than 2^31 pairs), normally the exclusive scan of n_sel; whatever it holds, a row writes only inside [row_ptr[u], min(row_ptr[u+1], cap)),
+ * drops what it has no room for and touches nothing outside [0, cap).  No atomics: positions come from a ballot and a prefix popcount per
+ * 16-column block and a cursor the row's lanes carry through the walk, so two calls give the same bytes.  Refusals as for count, and
+ * cap < 0: MGV_EINVAL. */
+int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                         float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
 /* sums[0] += sum_pos -log(sigma+1e-15), sums[1] += sum_neg -log(1-sigma+1e-15); counts += {TP,FP,TN,FN}
  * (trainer.py:240-244); pred_bin[Epos+Eneg] optional */
 int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,

@@ -277,6 +277,112 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
     }
 }
 
+// ---------------------------------------------------------------------------------- thresholded links as per-row lists
+// The tile walk of k_pair_topk without its lists: one workgroup per 64 rows u, the rows' s fragments in registers, the t tiles through
+// LDS with the next one prefetched.  Nothing leaves the accumulators: lane (r, q) holds column 16 c + r of rows 4 q + g, so the 16
+// lanes of quarter q are one row's 16-column block in ascending column order, and the decision `reported score > threshold` (the
+// expression behind k_pair_topk's n_above) is taken where the score lies.
+//   FILL = false: every lane counts its own columns; the 16 lanes of a quarter add up at the end -> n_sel[u].
+//   FILL = true : a ballot per (c, g) gives the block's 16 decisions to all of the row's lanes; a lane's slot is the row's cursor plus
+//                 the popcount of the lower columns, and the cursor (the same number in the row's 16 lanes) moves on by the block's
+//                 popcount through the whole walk.  Ascending columns, no atomics, the same bytes from call to call.  A row writes
+//                 only slots in [row_ptr[u], min(row_ptr[u+1], cap)) that are >= 0; what has no room is dropped.
+template <int H, bool FILL>
+__global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
+                                                          int G, int sigmoid, float threshold, int skip_self, int32_t* n_sel,
+                                                          const int64_t* row_ptr, int64_t cap, int32_t* col_out, float* score_out) {
+    constexpr int LDT = PairCfg<H>::LDT;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    if (threadIdx.x < kPairTile) {
+        const int64_t u = u0 + threadIdx.x;
+        int64_t lo = 0, hi = 0;
+        if (u < N) {
+            if (gp == nullptr) { hi = N; }
+            else {
+                int a = 0, b = G;                          // first graph whose end lies behind u
+                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
+                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
+                hi = hi < lo ? lo : (hi > N ? N : hi);
+            }
+        }
+        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+    }
+    __syncthreads();
+    int64_t clo = N, chi = 0;
+    for (int i = 0; i < kPairTile; ++i) {
+        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
+    }
+    const int64_t row0 = u0 + 16 * w;
+    // the lane's four rows 4 q + g: candidate range, slots, cursor
+    int mylo[4], myhi[4], cnt[4];
+    int64_t base[4];
+    uint64_t room[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int lr = 16 * w + 4 * q + g;
+        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; cnt[g] = 0;
+        base[g] = 0; room[g] = 0;
+        if (FILL && u0 + lr < N) {
+            const int64_t b = row_ptr[u0 + lr], e0 = row_ptr[u0 + lr + 1], e = e0 < cap ? e0 : cap;
+            base[g] = b;
+            room[g] = e > b ? (uint64_t)e - (uint64_t)b : 0ull;     // exact for any b < e
+        }
+    }
+    float a[H / 4];
+    load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
+    if (clo < chi) {
+        const int64_t ct0 = clo / kPairTile, ct1 = (chi + kPairTile - 1) / kPairTile;
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t col = ct * kPairTile + 16 * c + r;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float v = acc[c][g];
+                    const bool valid = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
+                    const float rep = sigmoid ? sigmoidf_(v) : v;
+                    const bool pass = valid && rep > threshold;
+                    if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
+                    const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
+                    const uint64_t i = (uint64_t)(unsigned)cnt[g] + (uint64_t)__popc(bits & ((1u << r) - 1u));
+                    cnt[g] += __popc(bits);
+                    if (pass && i < room[g]) {              // i < room: base + i < min(row_ptr[u+1], cap), no overflow
+                        const int64_t pos = base[g] + (int64_t)i;
+                        if (pos >= 0) {
+                            col_out[pos] = (int32_t)col;
+                            if (score_out != nullptr) score_out[pos] = rep;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!FILL) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            int n = cnt[g];
+            n += __shfl_xor(n, 1, 64);
+            n += __shfl_xor(n, 2, 64);
+            n += __shfl_xor(n, 4, 64);
+            n += __shfl_xor(n, 8, 64);
+            const int64_t u = row0 + 4 * q + g;
+            if (r == 0 && u < N) n_sel[u] = n;
+        }
+    }
+}
+
 inline bool pair_h_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
 inline bool pair_rows_ok(const float* x, int ld, int H) { return x != nullptr && ld >= H && ld % 4 == 0 && ((uintptr_t)x & 15) == 0; }
 
@@ -369,5 +475,58 @@ extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const fl
     const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
     MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_topk<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
                                               graph_ptr, G, k, sigmoid, threshold, skip_self, idx, score, n_above));
+    MGV_LAUNCH_RET();
+}
+
+// the arguments the two selection entries share, checked in the order of mgv_pair_topk; *launch = false: nothing to do
+static int pair_select_args(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                            hipStream_t st, bool* launch) {
+    *launch = false;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL);                           // node ids are int32
+    MGV_CHECK_ARG(graph_ptr == nullptr || G >= 0);
+    if (graph_ptr != nullptr) {
+        // the table must start at 0 and end at N: its two ends are read back (the only blocking step; NULL skips it)
+        int32_t ends[2] = {0, 0};
+        hipError_t e = hipMemcpyAsync(&ends[0], graph_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], graph_ptr + G, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return (int)e;
+        MGV_CHECK_ARG(ends[0] == 0 && (int64_t)ends[1] == N);
+    }
+    if (N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H));
+    *launch = true;
+    return MGV_OK;
+}
+
+extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                     int sigmoid, float threshold, int skip_self, int32_t* n_sel, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(n_sel != nullptr);
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, false>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t,
+                                              ldt, graph_ptr, G, sigmoid, threshold, skip_self, n_sel, (const int64_t*)nullptr, (int64_t)0,
+                                              (int32_t*)nullptr, (float*)nullptr));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                    int sigmoid, float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col,
+                                    float* score, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(cap >= 0);
+    bool launch;
+    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
+    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t,
+                                              ldt, graph_ptr, G, sigmoid, threshold, skip_self, (int32_t*)nullptr, row_ptr, cap, col, score));
     MGV_LAUNCH_RET();
 }

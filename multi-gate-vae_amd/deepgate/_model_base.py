@@ -146,6 +146,16 @@ class FunctionalModel(nn.Module):
             s, t = self._decoder_halves(hs)
             return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
+    def reconstruct_edges(self, hs, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
+        """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None) on st = hs_decompose(hs): the graph the decoder
+        reconstructs, every pair inside a graph with sigma > threshold, as (source, target) rows listed per source in ascending target
+        order (by='dst': per target in ascending source order, the in-neighbour lists); row_ptr delimits the lists
+        (ops.reconstruct_edges, streamed by ops.pair_select).  E' = reconstruction_counts(...)[:, 1].sum().  Added functionality."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
+                                         with_scores=with_scores, max_edges=max_edges)
+
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the

@@ -39,6 +39,12 @@ class DirectedInnerProductDecoder(nn.Module):
         links inside its own graph and the number of candidates scored above `threshold`, (idx, score, n_above) of ops.pair_topk."""
         return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self)
 
+    def select(self, s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
+        """The decoded graph itself (added functionality): per node the list of ALL links inside its own graph scored above `threshold`,
+        by source or (by='dst') by target, (row_ptr, col, score or None) of ops.pair_select; no N x N array and no cap per node."""
+        return ops.pair_select(s, t, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self, by=by,
+                               with_scores=with_scores, max_edges=max_edges)
+
 
 def _classes_once(x, classes, width):
     """Integer one-hot rows -> (rows, ids) once per encoder call (feature_classes runs a torch.unique with a host read-back); float

@@ -31,6 +31,14 @@ class DirectedGAE(torch.nn.Module):
         with torch.no_grad():
             return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
+    def reconstruct_edges(self, s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
+        """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None): every pair inside a graph that the decoder calls an
+        edge (score > threshold) as (source, target) rows, listed per source or (by='dst') per target (ops.reconstruct_edges).  Added
+        functionality."""
+        with torch.no_grad():
+            return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
+                                         with_scores=with_scores, max_edges=max_edges)
+
     def encode(self, *args, **kwargs):
         return self.encoder(*args, **kwargs)
 

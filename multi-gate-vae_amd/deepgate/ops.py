@@ -991,6 +991,75 @@ def pair_topk(s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=Fa
     return idx, score, n_above
 
 
+_PAIR_WIDTHS = (16, 32, 64, 128)
+
+
+def _select_room(total, with_scores, max_edges, free):
+    """The two refusals of pair_select between its count and its fill (nothing is allocated before them): more links than the caller
+    allows, or lists (int32 ids, float32 scores beside them when asked for) the device cannot hold — by name, like _dense_fits."""
+    hint = 'raise the threshold, or take the k best links per node with ops.pair_topk / DirectedInnerProductDecoder.topk'
+    if max_edges is not None and total > int(max_edges):
+        raise HipLibraryError('pair_select: %d links are above the threshold, max_edges allows %d: %s' % (total, int(max_edges), hint))
+    need = (8 if with_scores else 4) * total
+    if free is not None and need > free:
+        raise HipLibraryError('pair_select: the lists of %d links above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
+                              % (total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
+
+
+def pair_select(s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
+    """(row_ptr int64 [N + 1], col int32 [E'], score float32 [E'] or None): the reconstructed graph as per-node lists — for every row u
+    the nodes v of u's own graph (graph_ptr [G + 1], None: one graph; without v = u when skip_self) whose score is > threshold, as
+    batch-wide ids in ascending order at col[row_ptr[u] : row_ptr[u + 1]].  The decision is the one behind pair_topk's n_above, on the
+    dense entry's bits.  by='src': row u lists its targets v (<s_u, t_v>); by='dst': the operands change places and row v lists its
+    sources u, the in-neighbour lists — every product commutes and k keeps its order, so the scores are the dense entries, transposed.
+    Count, exclusive scan on the device, ONE read-back of the total (the result must be allocated; the only synchronisation besides the
+    two ends of a graph_ptr), fill; no atomics, the same bytes from call to call, nothing of size N^2.  A total above `max_edges` or
+    beyond the free memory raises HipLibraryError before the fill.  No grad."""
+    if by not in ('src', 'dst'):
+        raise HipLibraryError("pair_select: by must be 'src' (row u lists its targets) or 'dst' (row v lists its sources), got %r" % (by,))
+    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1] and s.shape[1] not in _PAIR_WIDTHS:
+        raise HipLibraryError('pair_select: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
+                              % (list(_PAIR_WIDTHS), s.shape[1]))
+    if by == 'dst':
+        s, t = t, s
+    sd, lds, td, ldt, H = _pair_operands(s, t)
+    N = sd.shape[0]
+    if td.shape[0] != N:
+        raise HipLibraryError('pair_select lists the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
+    dev = sd.device
+    gp, G = None, 0
+    if graph_ptr is not None:
+        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
+        G = gp.numel() - 1
+        if G < 0:
+            raise HipLibraryError('graph_ptr needs at least one entry')
+    common = (H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), float(threshold), int(bool(skip_self)))
+    n_sel = torch.empty(N, dtype=I32, device=dev)
+    _hip.call('mgv_pair_select_count', *common, ptr(n_sel))
+    row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
+    total = int(row_ptr[-1])                                      # the read-back
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # as _dense_fits
+    _select_room(total, with_scores, max_edges, free)
+    col = torch.empty(total, dtype=I32, device=dev)
+    score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
+    _hip.call('mgv_pair_select_fill', *common, ptr(row_ptr), total, ptr(col), ptr(score))
+    return row_ptr, col, score
+
+
+def reconstruct_edges(s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
+    """(edge_index int64 [2, E'], row_ptr, score or None): pair_select's lists (sigmoid scores) as (source, target) rows in list order,
+    whichever side they are listed by.  E' is reconstruction_counts(...)[:, 1].sum() by construction (skip_self off)."""
+    row_ptr, col, score = pair_select(s, t, graph_ptr=graph_ptr, sigmoid=True, threshold=threshold, skip_self=skip_self, by=by,
+                                      with_scores=with_scores, max_edges=max_edges)
+    N = row_ptr.numel() - 1
+    rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=col.device), row_ptr[1:] - row_ptr[:-1],
+                                   output_size=col.numel())
+    col = col.to(torch.int64)
+    return torch.stack([rows, col] if by == 'src' else [col, rows]), row_ptr, score
+
+
 def reconstruction_counts(s, t, edge_index, graph_ptr, threshold=0.5):
     """int64 [G, 4] on the device, per graph of the batch: {true positives, predicted positives over all n_g^2 ordered pairs, edges,
     ordered pairs} of the decoder at `threshold` against the FULL adjacency (the sampled counters of ReconLossFn see E + N non-edges

@@ -6,6 +6,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --out emb.npz
     python examples/feature_extract.py --type aig --synthetic 4 --link_metrics      # + ROC-AUC / AP of the decoder per batch
     python examples/feature_extract.py --type aig --synthetic 4 --predict_links 8   # + every gate's 8 most probable fan-out targets
+    python examples/feature_extract.py --type aig --synthetic 4 --reconstruct 0.5   # + the decoded edge list of every graph
 """
 import argparse
 import os
@@ -35,6 +36,10 @@ def main(argv=None):
     ap.add_argument('--predict_links', type=int, default=0, metavar='K', help='also store every node\'s K most probable successors inside '
                     'its graph (name/pred_dst, ids local to the graph, -1 past the end; name/pred_score) and print the mean precision and '
                     'recall of the decoder against the FULL adjacency (Model.predict_links / reconstruction_counts; 1 <= K <= 32)')
+    ap.add_argument('--reconstruct', type=float, default=None, metavar='THR', help='also store the graph the decoder reconstructs: every '
+                    'pair inside a graph scored above THR (name/rec_edge_index [2, E\'], ids local to the graph, listed per source in '
+                    'ascending target order) with its precision and recall against the true edges (name/rec_precision, name/rec_recall; '
+                    'Model.reconstruct_edges / reconstruction_counts)')
     a = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
@@ -62,8 +67,16 @@ def main(argv=None):
                 idx, score, _ = model.predict_links(hs, a.predict_links, graph_ptr=batch.graph_ptr)
                 counts.append(model.reconstruction_counts(hs, batch.edge_index, batch.graph_ptr))
                 idx, score = idx.cpu().numpy(), score.cpu().numpy()
+            if a.reconstruct is not None:
+                rec_ei, rec_ptr, _ = model.reconstruct_edges(hs, graph_ptr=batch.graph_ptr, threshold=a.reconstruct)
+                rc = model.reconstruction_counts(hs, batch.edge_index, batch.graph_ptr, threshold=a.reconstruct).double().cpu()
+                rec_ei, eptr = rec_ei.cpu().numpy(), rec_ptr[batch.graph_ptr.to(rec_ptr.device).long()].tolist()      # the graphs' places in the list
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if a.reconstruct is not None:
+                    out[name + '/rec_edge_index'] = (rec_ei[:, eptr[k]:eptr[k + 1]] - ptr[k]).astype(np.int32)
+                    out[name + '/rec_precision'] = np.float64(rc[k, 0] / max(float(rc[k, 1]), 1.0))
+                    out[name + '/rec_recall'] = np.float64(rc[k, 0] / max(float(rc[k, 2]), 1.0))
                 if a.predict_links:
                     loc = idx[ptr[k]:ptr[k + 1]]
                     out[name + '/pred_dst'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
