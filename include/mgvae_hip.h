@@ -444,22 +444,30 @@ int mgv_confusion(int64_t n, const int32_t* pred_bin, const int32_t* gt_bin, uin
  * colstats: sums[c] += sum_i Y[i][c], sums[C+c] += sum_i Y[i][c]^2 (BatchNorm batch statistics) */
 /* Small sums (column statistics, loss sums, head gradients) are deterministic: every workgroup leaves its partials in its own row of
  * `workspace` (>= mgv_sum_workspace_doubles() doubles, one buffer per stream in flight) and a second launch adds the rows in a fixed
- * order — no floating-point atomics, bit-identical from call to call. */
+ * order — no floating-point atomics, bit-identical from call to call.  The size covers every served C: at most 2048 workgroup rows of
+ * at most 2 * 64 doubles (the launchers themselves insist on workgroups * row only and return MGV_EINVAL below that).
+ * Common to the per-layer entries below: C in {4, 8, 16, 32, 64} (else MGV_EINVAL); matrices are contiguous [N][C] (only mgv_colstats
+ * takes a row stride) and 16-byte aligned; N = 0 is MGV_OK with nothing written, N < 0 MGV_EINVAL.
+ * colstats: sums[2C] (double) is ADDED to; ld >= C and ld % 4 == 0, the columns C .. ld of Y are not read. */
 int mgv_sum_workspace_doubles(void);
 int mgv_colstats(int64_t N, int C, const float* Y, int ld, double* sums, double* workspace, int64_t workspace_doubles, void* stream);
-/* A = dropout_p(relu(gamma*(Y-mean)*invstd+beta)); dropout mask from a counter-based hash of (seed, element) */
+/* A = dropout_p(relu(gamma*(Y-mean)*invstd+beta)), overwritten; dropout mask from a counter-based hash of (seed, element row * C + col);
+ * p_drop in [0, 1) (else MGV_EINVAL); p_drop = 0: no mask, whatever the seed */
 int mgv_bn_act_fwd(int64_t N, int C, const float* Y, const float* mean, const float* invstd, const float* gamma,
                    const float* beta, float p_drop, uint64_t seed, float* A, void* stream);
-/* dZ = dA * mask * [bn_out > 0]; sums[c] += sum dZ (= dbeta), sums[C+c] += sum dZ*xhat (= dgamma) */
+/* dZ = dA * mask * [bn_out > 0] (overwritten); sums[2C] (double) is ADDED to: sums[c] += sum dZ (= dbeta), sums[C+c] += sum dZ*xhat (= dgamma);
+ * p_drop in [0, 1) as in the forward (else MGV_EINVAL, nothing written) */
 int mgv_bn_act_bwd(int64_t N, int C, const float* Y, const float* mean, const float* invstd, const float* gamma,
                    const float* beta, float p_drop, uint64_t seed, const float* dA, float* dZ, double* sums, double* workspace,
                    int64_t workspace_doubles, void* stream);
-/* dY = gamma*invstd*(dZ - [batch_stats](sums[c]/N + xhat*sums[C+c]/N)) */
+/* dY = gamma*invstd*(dZ - [batch_stats](sums[c]/N + xhat*sums[C+c]/N)), overwritten; batch_stats = 0 (eval mode): dY = gamma*invstd*dZ,
+ * sums is not read but must not be NULL */
 int mgv_bn_bwd_apply(int64_t N, int C, const float* Y, const float* mean, const float* invstd, const float* gamma,
                      const float* dZ, const double* sums, int batch_stats, float* dY, void* stream);
-/* prob = A w + b (mlp.py:43, last Linear), clamped to [0,1] when clamp01 != 0 (dg_ae_model_aig.py:105) */
+/* prob[N] = A w + b (mlp.py:43, last Linear), clamped to [0,1] when clamp01 != 0 (dg_ae_model_aig.py:105); overwritten */
 int mgv_readout_head_fwd(int64_t N, int C, const float* A, const float* w, const float* b, int clamp01, float* prob, void* stream);
-/* given dprob[N]: dA = dy w, dw += sum dy A, db += sum dy with dy = dprob * [clamp inactive] */
+/* given dprob[N]: dA = dy w (overwritten); dw[C] and db[1] are ADDED to: dw += sum dy A, db += sum dy; dy = dprob * [clamp inactive],
+ * the clamp is inactive for 0 <= A w + b <= 1 (both ends included) and everywhere when clamp01 = 0 */
 int mgv_readout_head_bwd(int64_t N, int C, const float* A, const float* w, const float* b, int clamp01, const float* dprob,
                          float* dA, float* dw, float* db, double* workspace, int64_t workspace_doubles, void* stream);
 /* ---- fused training-mode readout (arch/mlp.py MLP.forward with dim_in 64, dim_hidden 32, three layers = the pred_prob of
@@ -472,7 +480,11 @@ int mgv_readout_fused_grad_floats(void);
 int mgv_readout_fused_ws_doubles(int64_t N);
 /* Forward: y1 = hf W1^T + b1, y2 = a1 W2^T + b2 with a_k = dropout(relu(bn_k(y_k))) (batch statistics; running buffers rm/rv
  * updated as nn.BatchNorm1d: running = running * keep + momentum * value, keep = 1 - momentum, unbiased var), prob = clamp(a2 w3 + b3).
- * Out: y1, y2 [N][32]; stats[128] = mean1, invstd1, mean2, invstd2 (kept for the backward); sums[128] (double) scratch; prob [N]. */
+ * Out (all overwritten): y1, y2 [N][32]; stats[128] = mean1, invstd1, mean2, invstd2 (kept for the backward); sums[128] (double) scratch;
+ * prob [N].  rm / rv are updated in place; momentum, keep and eps are taken as given (keep is not derived from momentum).
+ * N >= 1: N = 0 is MGV_EINVAL here (the per-layer entries return MGV_OK).  N = 1: var = 0 and invstd = 1/sqrt(eps) in every column;
+ * the unbiased factor is N / max(N - 1, 1) = 1, so running_var = running_var * keep (torch refuses one row in training mode).
+ * p1, p2 in [0, 1); workspace_doubles below mgv_readout_fused_ws_doubles(N): MGV_EINVAL. */
 int mgv_readout_fused_fwd(int64_t N, const float* hf, const void* wpack, const float* b1, const float* g1, const float* be1,
                           float* rm1, float* rv1, const float* b2, const float* g2, const float* be2, float* rm2, float* rv2,
                           const float* w3, const float* b3, float p1, float p2, uint64_t seed1, uint64_t seed2, float momentum,
@@ -484,7 +496,8 @@ int mgv_readout_fused_bwd(int64_t N, const float* hf, const float* y1, const flo
                           const void* wpack, const float* g1, const float* be1, const float* g2, const float* be2, const float* w3,
                           const float* b3, float p1, float p2, uint64_t seed1, uint64_t seed2, int clamp01, float* dhf,
                           float* grads, double* sums, double* workspace, int64_t workspace_doubles, void* stream);
-/* nn.L1Loss, reduction mean (trainer.py:71,156): sum += sum |x - target|;  dx = *gscale/n * sign(x - target) */
+/* nn.L1Loss, reduction mean (trainer.py:71,156): sum[1] (double) += sum |x - target|;  dx = *gscale/n * sign(x - target), sign(0) = 0,
+ * overwritten; gscale is read on the device; n = 0 is MGV_OK with nothing written */
 int mgv_l1_loss_fwd(int64_t n, const float* x, const float* target, double* sum, double* workspace, int64_t workspace_doubles,
                     void* stream);
 int mgv_l1_loss_bwd(int64_t n, const float* x, const float* target, const float* gscale, float* dx, void* stream);

@@ -257,7 +257,7 @@ extern "C" int mgv_bn_act_fwd(int64_t N, int C, const float* Y, const float* mea
 extern "C" int mgv_bn_act_bwd(int64_t N, int C, const float* Y, const float* mean, const float* invstd, const float* gamma,
                               const float* beta, float p_drop, uint64_t seed, const float* dA, float* dZ, double* sums,
                               double* workspace, int64_t workspace_doubles, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && mgv::c_ok(C) && Y && mean && invstd && gamma && beta && dA && dZ && sums);
+    MGV_CHECK_ARG(N >= 0 && mgv::c_ok(C) && Y && mean && invstd && gamma && beta && dA && dZ && sums && p_drop >= 0.f && p_drop < 1.f);
     if (N == 0) return MGV_OK;
     const int rows = mgv::kThreads / (C / 4);
     const int grid = mgv::grid_for((N + rows - 1) / rows, 8);
