@@ -21,49 +21,6 @@ TILE = 64
 NO_GATE = 255
 
 
-class ColourDictionary:
-    """Dataset-wide, EXACT dictionary of colour signatures -> global colour ids, one per half round of the structural encoder.
-    A colour of half round t is (feature class, global colour of its own row after t-1, sorted global colours of its neighbours after
-    t-1); two nodes of different graphs with equal signatures have identical rows after half round t (induction over t: every node
-    starts from ones, digae_layer.py:260), so a batch may compute them once.  Signatures are compared as Python tuples / bytes —
-    no hashing of our own, no collisions.  Filled per graph, once, from the graph's own quotient stages (their representatives'
-    lists): GraphPlan.assemble_quotient then merges the graphs' colours of a batch by their global ids."""
-
-    def __init__(self, max_entries=20000000):
-        self.maps, self.next_id, self.max_entries = [], [], int(max_entries)
-
-    def globals_of(self, stages):
-        """stages: per half round a dict of HOST arrays ptr [C+1], ent [n_ent] (previous colours, the graph's own numbering),
-        own [C], xcls [C].  -> list of int64 arrays: the global id of every colour of the graph, per half round."""
-        out = []
-        gprev = np.zeros(1, dtype=np.int64)                   # before the first half round: one colour, global id 0
-        for t, st in enumerate(stages):
-            while len(self.maps) <= t:
-                self.maps.append({}); self.next_id.append(0)
-            table = self.maps[t]
-            ptr, ent, own, xcls = (np.asarray(st[k]) for k in ('ptr', 'ent', 'own', 'xcls'))
-            C = int(own.shape[0])
-            deg = np.diff(ptr)
-            entg = gprev[ent] if ent.size else np.zeros(0, dtype=np.int64)
-            rowid = np.repeat(np.arange(C), deg)
-            entg = entg[np.lexsort((entg, rowid))] if entg.size else entg      # every list sorted by global colour: a multiset
-            owng = gprev[own]
-            g = np.empty(C, dtype=np.int64)
-            full = len(table) >= self.max_entries
-            for c in range(C):
-                key = (int(xcls[c]), int(owng[c]), entg[ptr[c]:ptr[c + 1]].tobytes())
-                v = table.get(key)
-                if v is None:
-                    v = self.next_id[t]
-                    self.next_id[t] += 1
-                    if not full:
-                        table[key] = v                        # (a full table hands out fresh ids: such colours are simply not shared)
-                g[c] = v
-            out.append(g)
-            gprev = g
-        return out
-
-
 class GraphPlan:
     """in-CSR  : in_ptr[N+1], in_src[E]              sources of each node, original edge order kept
     out-CSR : out_ptr[N+1], out_dst[E], out_slot[E] destinations; out_slot = position of that edge
@@ -323,8 +280,8 @@ class GraphPlan:
         Grouping is proposed by a 64-bit key (two sums of random per-colour values over the neighbour list, folded with the own
         colour, class and degree) and then CHECKED exactly: every member against its colour's representative, list entry by list
         entry (lists sorted by colour); refinement stops at the first disagreement, so a key collision costs speed, never
-        correctness.  Cached per xcls tensor.  `force`: also below QUOTIENT_MIN_NODES (per-graph parts for assemble_quotient).
-        Every stage also keeps the pieces a batch-level assembly needs under 'raw' (references, no extra work)."""
+        correctness.  Cached per xcls tensor.  `force`: the torch composition also below QUOTIENT_MIN_NODES, and stages go on while
+        C * 1.1 <= N instead of stopping by QUOTIENT_FRACTION / QUOTIENT_GROWTH (small CPU plans of the host-logic tests)."""
         cache = getattr(self, '_quotient', None)
         if cache is None or cache[0] is not xcls:      # (the tensor itself: an address can be reused)
             cache = self._quotient = (xcls, {})
@@ -377,7 +334,7 @@ class GraphPlan:
                 starts = torch.nonzero(first).reshape(-1)
                 C = int(starts.numel())
                 if C * (1.1 if force else self.QUOTIENT_FRACTION) > N:
-                    break                    # (force: a graph's own stages go on until it is nearly fully refined; assembly applies the batch rule)
+                    break                    # (force: stages go on until the graph is nearly fully refined)
                 inv = torch.empty(N, **i64)
                 inv[by_colour] = torch.cumsum(first, 0) - 1
                 members = torch.diff(starts, append=torch.tensor([N], **i64))
@@ -412,9 +369,7 @@ class GraphPlan:
                 # mgv_seg_sum (a colour like "AND gate" is named by thousands of entries: balanced, and summed in a fixed order)
                 own_o, own_levels = self.class_sum_levels(own, Cp)
                 ent_o, ent_levels = self.class_sum_levels(ent, Cp)
-                raw = dict(rptr=rptr, ent=ent, own=own, row=row, heavy=heavy, own_sorted=(own_o, own_levels['counts']),
-                           ent_sorted=(ent_o, ent_levels['counts']), cid_sorted=(by_colour, members))
-                stages.append(dict(C=C, raw=raw, cid=inv.to(torch.int32).contiguous(), rev=rev, ptr=rptr.to(torch.int32).contiguous(),
+                stages.append(dict(C=C, cid=inv.to(torch.int32).contiguous(), rev=rev, ptr=rptr.to(torch.int32).contiguous(),
                                    idx=(ent + C).to(torch.int32).contiguous() if n_ent else torch.zeros(1, dtype=torch.int32, device=dev),
                                    ent_idx=ent.to(torch.int32).contiguous() if n_ent else torch.zeros(1, dtype=torch.int32, device=dev),
                                    own=own, own32=own.to(torch.int32).contiguous(), xcls=xcls[rep].contiguous(),
@@ -606,173 +561,6 @@ class GraphPlan:
                     own=own32.long(), own32=own32, xcls=xrep, heavy=(int(n_heavy), heavy),
                     own_rows=own_o, own_levels=self._class_sum_levels_dev(own_counts, Cp),
                     ent_rows=row.index_select(0, ent_o) if n_ent else ent, ent_levels=self._class_sum_levels_dev(ent_counts, Cp))
-
-    def assemble_quotient(self, parts, node_off, max_stages):
-        """Quotient stages of a BATCH from its graphs' own stages (`parts[g]` = GraphPlan(graph g).quotient(..., force=True), cached by
-        the loader: a dataset's graphs come back every epoch in other batches, their colour refinement need not).  Graphs share
-        nothing, so the disjoint union of their colourings is a valid colouring of the batch (colours are never merged ACROSS graphs:
-        a few more rows than the batch-level refinement finds, the same exactness — the check ran per graph).  Pure index
-        arithmetic: concatenation with offsets (node ids by `node_off`, colour ids by the running sums of the graphs' colour counts;
-        every graph's stage-1 lists name the ONE shared all-ones row) and the segment tables of mgv_seg_sum rebuilt from the
-        concatenated, already colour-sorted orders (class_sum_levels(presorted=...): no sort).  Stages are cut where a graph has
-        none left, or where the batch's colours exceed N / QUOTIENT_FRACTION; nothing below QUOTIENT_MIN_NODES.  Installs the result
-        as this plan's quotient cache for `max_stages` and returns it."""
-        N, dev = self.N, self.device
-        i64 = dict(dtype=torch.int64, device=dev)
-        counts = sorted({int(c) for c in (max_stages if isinstance(max_stages, (tuple, list, set)) else [max_stages]) if int(c) > 0})
-        S = min([len(p) for p in parts] + [max(counts + [0])])
-        G = len(parts)
-        stages = []
-        if N >= self.QUOTIENT_MIN_NODES and self.E > 0:
-            prev_off = [0] * G               # offset of graph g's previous-stage colours (stage 1: the single shared row)
-            Cp = 1
-            for t in range(S):
-                st = [p[t] for p in parts]
-                Cs = [s_['C'] for s_ in st]
-                C = sum(Cs)
-                if C * self.QUOTIENT_FRACTION > N:
-                    break
-                coff = [0] * G
-                for g in range(1, G):
-                    coff[g] = coff[g - 1] + Cs[g - 1]
-                n_ents = [int(s_['raw']['ent'].numel()) for s_ in st]
-                eoff = [0] * G
-                for g in range(1, G):
-                    eoff[g] = eoff[g - 1] + n_ents[g - 1]
-                n_ent = sum(n_ents)
-                n_nodes = [int(node_off[g + 1]) - int(node_off[g]) for g in range(G)]
-
-                def spread(offs, lens, total):
-                    # the per-graph offsets, one per element of the concatenation (ONE launch, no read-back: the size is known here)
-                    return torch.repeat_interleave(torch.tensor(offs, **i64), torch.tensor(lens, **i64), output_size=total)
-
-                def catoff(ts, off_vec):
-                    flat = (torch.cat(ts) if len(ts) > 1 else ts[0]).long()
-                    return flat + off_vec if off_vec is not None else flat
-                by_node_c = spread(coff, n_nodes, N)
-                by_rep_c, by_rep_e = spread(coff, Cs, C), spread(eoff, Cs, C)
-                by_rep_p = spread(prev_off, Cs, C) if t > 0 else None
-                by_ent_c = spread(coff, n_ents, n_ent)
-                by_ent_p = spread(prev_off, n_ents, n_ent) if t > 0 else None
-                cid = catoff([s_['cid'] for s_ in st], by_node_c)
-                rptr = torch.cat([catoff([s_['raw']['rptr'][:-1] for s_ in st], by_rep_e), torch.tensor([n_ent], **i64)])
-                ent = catoff([s_['raw']['ent'] for s_ in st], by_ent_p)
-                own = catoff([s_['raw']['own'] for s_ in st], by_rep_p)
-                row = catoff([s_['raw']['row'] for s_ in st], by_ent_c)
-                n_heavy = [int(s_['raw']['heavy'].numel()) for s_ in st]
-                heavy = catoff([s_['raw']['heavy'] for s_ in st], spread(coff, n_heavy, sum(n_heavy)) if sum(n_heavy) else None).to(torch.int32)
-                if t == 0:
-                    # one previous colour for everybody: every representative / entry belongs to group 0, in index order
-                    own_pre = (torch.arange(C, dtype=torch.int32, device=dev), torch.tensor([C], **i64))
-                    ent_o = torch.arange(n_ent, dtype=torch.int32, device=dev)
-                    ent_pre = (ent_o, torch.tensor([n_ent], **i64))
-                else:
-                    own_pre = (catoff([s_['raw']['own_sorted'][0] for s_ in st], by_rep_c), torch.cat([s_['raw']['own_sorted'][1] for s_ in st]))
-                    ent_o = catoff([s_['raw']['ent_sorted'][0] for s_ in st], spread(eoff, n_ents, n_ent))
-                    ent_pre = (ent_o, torch.cat([s_['raw']['ent_sorted'][1] for s_ in st]))
-                own_o, own_levels = self.class_sum_levels(None, Cp, presorted=own_pre)
-                ent_o, ent_levels = self.class_sum_levels(None, Cp, presorted=ent_pre)
-                zero1 = torch.zeros(1, dtype=torch.int32, device=dev)
-                cid_sorted = (catoff([s_['raw']['cid_sorted'][0] for s_ in st], spread([int(v) for v in node_off[:G]], n_nodes, N)), torch.cat([s_['raw']['cid_sorted'][1] for s_ in st]))
-                stages.append(dict(C=C, cid=cid.to(torch.int32).contiguous(), rev=st[0]['rev'], ptr=rptr.to(torch.int32).contiguous(),
-                                   idx=(ent + C).to(torch.int32).contiguous() if n_ent else zero1,
-                                   ent_idx=ent.to(torch.int32).contiguous() if n_ent else zero1,
-                                   own=own, own32=own.to(torch.int32).contiguous(), xcls=torch.cat([s_['xcls'] for s_ in st]).contiguous(),
-                                   heavy=(int(heavy.numel()), heavy.contiguous()), own_rows=own_o, own_levels=own_levels,
-                                   ent_rows=row[ent_o.long()].to(torch.int32).contiguous() if n_ent else zero1, ent_levels=ent_levels,
-                                   _cid_sorted=cid_sorted))
-                prev_off, Cp = coff, C
-        out = {}
-        for c in counts:
-            lst = list(stages[:c])
-            if lst:
-                last = dict(lst[-1])
-                last['sum_levels'] = self.class_sum_levels(last['cid'], last['C'], presorted=last['_cid_sorted'])
-                lst[-1] = last
-            out[c] = lst
-        xc = getattr(self, 'xcls', None)
-        cache = getattr(self, '_quotient', None)
-        if cache is None or cache[0] is not xc:
-            cache = self._quotient = (xc, {})
-        cache[1].update(out)
-        return out
-
-    def assemble_quotient_merged(self, parts, gcols, node_off, max_stages):
-        """Like assemble_quotient, but colours are MERGED across the batch's graphs through their dataset-wide global ids
-        (`gcols[g][t]` [C_g] int64 from ColourDictionary.globals_of): the result is the batch-level colour refinement itself (same
-        partition as GraphPlan.quotient finds), at the price of one `unique` + one argsort over the graphs' colours per half round
-        (not over the nodes), two sorts for the segment tables and one sort of the nodes for the last stage's sums."""
-        N, dev = self.N, self.device
-        i64 = dict(dtype=torch.int64, device=dev)
-        counts = sorted({int(c) for c in (max_stages if isinstance(max_stages, (tuple, list, set)) else [max_stages]) if int(c) > 0})
-        S = min([len(p) for p in parts] + [max(counts + [0])])
-        G = len(parts)
-        stages = []
-        if N >= self.QUOTIENT_MIN_NODES and self.E > 0:
-            n_nodes = [int(node_off[g + 1]) - int(node_off[g]) for g in range(G)]
-            inv_prev, prev_off, Cp = None, [0] * G, 1
-            zero1 = torch.zeros(1, dtype=torch.int32, device=dev)
-
-            def spread(offs, lens, total):
-                return torch.repeat_interleave(torch.tensor(offs, **i64), torch.tensor(lens, **i64), output_size=total)
-            for t in range(S):
-                st = [p[t] for p in parts]
-                Cs = [s_['C'] for s_ in st]
-                Ctot = sum(Cs)
-                coff = [0] * G
-                for g in range(1, G):
-                    coff[g] = coff[g - 1] + Cs[g - 1]
-                n_ents = [int(s_['raw']['ent'].numel()) for s_ in st]
-                eoff = [0] * G
-                for g in range(1, G):
-                    eoff[g] = eoff[g - 1] + n_ents[g - 1]
-                uniq, inv = torch.unique(torch.cat([gcols[g][t] for g in range(G)]), return_inverse=True)
-                C = int(uniq.numel())
-                if C * self.QUOTIENT_FRACTION > N:
-                    break
-                # the first colour (in concatenation order) of every merged colour represents it
-                order = torch.sort(inv, stable=True).indices
-                members = torch.bincount(inv, minlength=C)
-                rep = order[torch.cumsum(members, 0) - members]
-                cid = inv[torch.cat([s_['cid'] for s_ in st]).long() + spread(coff, n_nodes, N)]
-                start_cc = torch.cat([s_['raw']['rptr'][:-1] for s_ in st]) + spread(eoff, Cs, Ctot)
-                len_cc = torch.cat([s_['raw']['rptr'][1:] - s_['raw']['rptr'][:-1] for s_ in st])
-                ent_cc = torch.cat([s_['raw']['ent'] for s_ in st])
-                own_cc = torch.cat([s_['raw']['own'] for s_ in st])
-                if t > 0:                    # previous colours: the graph's numbering -> concatenation index -> merged id of stage t-1
-                    ent_cc = inv_prev[ent_cc + spread(prev_off, n_ents, sum(n_ents))]
-                    own_cc = inv_prev[own_cc + spread(prev_off, Cs, Ctot)]
-                dr = len_cc[rep]
-                rptr = torch.zeros(C + 1, **i64)
-                rptr[1:] = torch.cumsum(dr, 0)
-                n_ent = int(rptr[-1].item())
-                row = torch.repeat_interleave(torch.arange(C, **i64), dr, output_size=n_ent)
-                ent = ent_cc[start_cc[rep][row] + (torch.arange(n_ent, **i64) - rptr[row])] if n_ent else torch.zeros(0, **i64)
-                own = own_cc[rep]
-                heavy = torch.nonzero(dr > self.HEAVY_ROW).reshape(-1).to(torch.int32)
-                own_o, own_levels = self.class_sum_levels(own, Cp)
-                ent_o, ent_levels = self.class_sum_levels(ent, Cp)
-                stages.append(dict(C=C, cid=cid.to(torch.int32).contiguous(), rev=st[0]['rev'], ptr=rptr.to(torch.int32).contiguous(),
-                                   idx=(ent + C).to(torch.int32).contiguous() if n_ent else zero1,
-                                   ent_idx=ent.to(torch.int32).contiguous() if n_ent else zero1,
-                                   own=own, own32=own.to(torch.int32).contiguous(), xcls=torch.cat([s_['xcls'] for s_ in st])[rep].contiguous(),
-                                   heavy=(int(heavy.numel()), heavy.contiguous()), own_rows=own_o, own_levels=own_levels,
-                                   ent_rows=row[ent_o.long()].to(torch.int32).contiguous() if n_ent else zero1, ent_levels=ent_levels))
-                inv_prev, prev_off, Cp = inv, coff, C
-        out = {}
-        for c in counts:
-            lst = list(stages[:c])
-            if lst:
-                last = dict(lst[-1])
-                last['sum_levels'] = self.class_sum_levels(last['cid'], last['C'])
-                lst[-1] = last
-            out[c] = lst
-        xc = getattr(self, 'xcls', None)
-        cache = getattr(self, '_quotient', None)
-        if cache is None or cache[0] is not xc:
-            cache = self._quotient = (xc, {})
-        cache[1].update(out)
-        return out
 
     def class_sum_levels(self, cid, C, seg=64, presorted=None):
         """Segment tables of mgv_seg_sum for per-colour row sums: (order [N] int32 = nodes sorted by colour, tables) with

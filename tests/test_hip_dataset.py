@@ -123,12 +123,11 @@ def test_npz_dataset_through_train_entry_and_first_batch_against_the_oracle(tmp_
         assert abs(a - b) <= 1e-4 * max(1.0, abs(b)), (k, a, b)
 
 
-@pytest.mark.parametrize('mode', ['merged', 'separate'])
-def test_prefetched_batches_assemble_their_quotient_stages_from_per_graph_caches(mode):
-    """deepgate/prefetch.py: a fresh batch's quotient stages (the early half rounds of the structural encoder on one row per colour)
-    are put together from its graphs' own cached stages (GraphPlan.assemble_quotient) instead of a colour refinement per batch.
-    Two batches over the same graphs in another order: the cache is filled by the first, the stages engage in both, and a train
-    step on such a batch gives the losses (1e-6) and parameter gradients (4e-4 of scale; attention logits 1e-3) of the per-node path."""
+def test_prefetched_batches_arrive_with_their_quotient_stages_built():
+    """deepgate/prefetch.py: a fresh batch arrives with its quotient stages (the early half rounds of the structural encoder on one
+    row per colour) already built on the worker's stream, with the colour counts of a plan that refines alone.  Two batches over the
+    same graphs in another order: the stages engage in both, and a train step on such a batch gives the losses (1e-6) and parameter
+    gradients (4e-4 of scale; attention logits 1e-3) of the per-node path."""
     if not torch.cuda.is_available():
         pytest.skip('needs a GPU')
     import deepgate
@@ -147,17 +146,16 @@ def test_prefetched_batches_assemble_their_quotient_stages_from_per_graph_caches
     gate_ids = [g for _, g in model.GATES]
     chunks = [graphs, graphs[2:] + graphs[:2]]
     pf = BatchPrefetcher(iter(chunks), dev, gate_ids=gate_ids, workers=2, quotient_stages=4)
-    pf.PER_GRAPH_QUOTIENT = mode
     batches = list(pf)
     pf.close()
-    assert all('_mgv_quot' in g for g in graphs)
+    from deepgate.graph_plan import GraphPlan
     for b in batches:
+        built = b._mgv_plan._quotient
+        assert built[0] is b._mgv_plan.xcls and 4 in built[1]      # built by the worker, not by the call below
         q = b._mgv_plan.quotient(b._mgv_plan.xcls, 4)
-        assert len(q) >= 2 and 'sum_levels' in q[-1], len(q)
-        if mode == 'merged':                # the batch-level colour refinement itself: same colour counts as a plan that refines alone
-            from deepgate.graph_plan import GraphPlan
-            alone = GraphPlan(b.edge_index, b.x.shape[0]).quotient(b._mgv_plan.xcls, 4)
-            assert [s_['C'] for s_ in q] == [s_['C'] for s_ in alone[:len(q)]]
+        assert q is built[1][4] and len(q) >= 2 and 'sum_levels' in q[-1], len(q)
+        alone = GraphPlan(b.edge_index, b.x.shape[0]).quotient(b._mgv_plan.xcls, 4)
+        assert [s_['C'] for s_ in q] == [s_['C'] for s_ in alone]
 
     def grads(batch):
         tr.optimizer.zero_grad()

@@ -273,23 +273,40 @@ def test_prefetcher_collates_like_collate_and_keeps_order():
     assert not hasattr(skipped, 'neg_edge_index') and not hasattr(skipped, '_mgv_plan')
 
 
-@pytest.mark.parametrize('ctype', ['aig', 'xmg'])
-def test_quotient_colours_equal_brute_force_refinement(ctype):
-    """GraphPlan.quotient (host logic of the structural encoder's quotient stages): the colours of half round t equal colour
-    refinement done literally — (feature class, previous colour, sorted tuple of the neighbours' previous colours) over the in-CSR for odd t,
-    the out-CSR for even t — and a representative's list names its neighbours' previous colours."""
-    from deepgate import synthetic as syn
-    from deepgate.graph_plan import GraphPlan
-    a = syn.collate([syn.make_graph(ctype, 200 + 30 * 40, 40, 5 + i, n_inputs=200) for i in range(2)])
-    N, ei = a['num_nodes'], a['edge_index']
-    plan = GraphPlan(torch.from_numpy(ei), N)
+def _run_seg_tables(levels, items_value):
+    """Run mgv_seg_sum's tables the way the kernel does (out[out_row[s]] = sum of the segment's items) on one number per item: the
+    buffer of `rows` sums.  Every segment holds <= 64 items, every level consumes all its items, every row is written exactly once."""
+    buf = [None] * levels['rows']
+    for li, (n_seg, sp, out_row, src_row) in enumerate(levels['levels']):
+        sp = sp.tolist()
+        rows = out_row.tolist() if out_row is not None else list(range(n_seg))
+        assert len(sp) == n_seg + 1 and sp[0] == 0 and all(0 <= b - a_ <= 64 for a_, b in zip(sp[:-1], sp[1:]))
+        src = items_value if li == 0 else buf[src_row:]
+        assert sp[-1] == len([v for v in src if v is not None])
+        for s_, r in enumerate(rows):
+            assert buf[r] is None
+            buf[r] = sum(src[m] for m in range(sp[s_], sp[s_ + 1]))
+    assert all(v is not None for v in buf)
+    return buf
+
+
+def _batch_quotient(graphs, fraction):
+    """(collated arrays, xcls, GraphPlan.quotient(xcls, 3)) of a small CPU batch, with the thresholds lowered so that three half rounds
+    can qualify."""
+    a = syn.collate(graphs)
     xcls = torch.from_numpy(a['x'][:, 1].astype('uint8'))
     old = GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES
-    GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = 1.5, 1      # small graphs: let three half rounds qualify
+    GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = fraction, 1
     try:
-        q = plan.quotient(xcls, 3)
+        q = GraphPlan(torch.from_numpy(a['edge_index']), a['num_nodes']).quotient(xcls, 3)
     finally:
         GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = old
+    return a, xcls, q
+
+
+def _check_stages_against_brute_force(a, xcls, q):
+    """Every stage of `q` against colour refinement done literally, and its tables against what they are read as."""
+    N, ei = a['num_nodes'], a['edge_index']
     assert len(q) >= 2
     col = [0] * N
     for t, s in enumerate(q, start=1):
@@ -302,39 +319,61 @@ def test_quotient_colours_equal_brute_force_refinement(ctype):
         for kk in keys:
             ids.setdefault(kk, len(ids))
         cid = s['cid'].tolist()
-        assert len(set(zip((ids[kk] for kk in keys), cid))) == len(ids) == s['C'], t          # the same partition
-        # representatives' lists: entries = C + previous colour (in the numbering of stage t-1: q[t-2]['cid'], or 0)
+        C = s['C']
+        assert len(set(zip((ids[kk] for kk in keys), cid))) == len(ids) == C, t          # the same partition
+        # in the numbering of stage t-1 (q[t-2]['cid'], or the one start colour): all members of a colour share (previous colour, class)
         prev_cid = q[t - 2]['cid'].tolist() if t > 1 else [0] * N
-        first = {}
+        Cp = q[t - 2]['C'] if t > 1 else 1
+        shared, first = {}, {}
         for i, c in enumerate(cid):
             first.setdefault(c, i)
-        ptr, idx, own = s['ptr'].tolist(), s['idx'].tolist(), s['own'].tolist()
-        for c in range(s['C']):
+            assert shared.setdefault(c, (prev_cid[i], int(xcls[i]))) == (prev_cid[i], int(xcls[i])), (t, c)
+        ptr, idx, ent, own, xc = s['ptr'].tolist(), s['idx'].tolist(), s['ent_idx'].tolist(), s['own'].tolist(), s['xcls'].tolist()
+        assert s['own32'].dtype == torch.int32 and s['own32'].tolist() == own
+        # a representative's list: its neighbours' previous colours as a multiset (ent_idx), and the same as rows C + colour (idx)
+        for c in range(C):
             r = first[c]
-            assert own[c] == prev_cid[r]
-            src_nodes = [u for u, v in zip(src.tolist(), dst.tolist()) if v == r]
-            assert sorted(idx[ptr[c]:ptr[c + 1]]) == sorted(s['C'] + prev_cid[u] for u in src_nodes), (t, c)
+            assert own[c] == prev_cid[r] and xc[c] == int(xcls[r])
+            want = sorted(prev_cid[u] for u, v in zip(src.tolist(), dst.tolist()) if v == r)
+            assert sorted(ent[ptr[c]:ptr[c + 1]]) == want and sorted(idx[ptr[c]:ptr[c + 1]]) == [C + w for w in want], (t, c)
+        # colour-level sums for stage t-1: per previous colour, the representatives that own it / the entries that name it
+        assert s['own_levels']['C'] == Cp and sorted(s['own_rows'].tolist()) == list(range(C))
+        assert _run_seg_tables(s['own_levels'], [1] * C)[:Cp] == np.bincount(np.asarray(own), minlength=Cp).tolist()
+        n_ent = ptr[-1]
+        if n_ent:
+            # ent_rows[k] = the colour whose list holds the k-th entry in previous-colour order: a permutation of the entries' owners
+            assert sorted(s['ent_rows'].tolist()) == np.repeat(np.arange(C), np.diff(ptr)).tolist()
+            assert s['ent_levels']['C'] == Cp
+            assert _run_seg_tables(s['ent_levels'], [1] * n_ent)[:Cp] == np.bincount(np.asarray(ent[:n_ent]), minlength=Cp).tolist()
         col = [ids[kk] for kk in keys]
-    # segment tables of the per-colour sums: runs of <= 64 members of one colour, in colour order, down to one row per colour
+    # segment tables of the per-colour sums: runs of <= 64 members of one colour, in colour order, down to one row per colour:
+    # on one number per node every colour's final row must be its member count
     order, levels = q[-1]['sum_levels']
-    cid = q[-1]['cid']
+    cid, C = q[-1]['cid'], q[-1]['C']
     assert sorted(order.tolist()) == list(range(N)) and bool((cid[order.long()][1:] >= cid[order.long()][:-1]).all())
-    # run the tables the way mgv_seg_sum does (out[out_row[s]] = sum of the segment's items) on one number per node: every colour's
-    # final row must be its member count, every segment <= 64 items, every row of the buffer written exactly once
-    C = q[-1]['C']
     assert levels['C'] == C and levels['rows'] >= C
-    buf = [None] * levels['rows']
-    for li, (n_seg, sp, out_row, src_row) in enumerate(levels['levels']):
-        sp = sp.tolist()
-        rows = out_row.tolist() if out_row is not None else list(range(n_seg))
-        assert len(sp) == n_seg + 1 and sp[0] == 0 and all(0 <= b - a_ <= 64 for a_, b in zip(sp[:-1], sp[1:]))
-        src = [1] * N if li == 0 else buf[src_row:]
-        assert sp[-1] == (N if li == 0 else len([v for v in src if v is not None]))
-        for s_, r in enumerate(rows):
-            assert buf[r] is None
-            buf[r] = sum(src[m] for m in range(sp[s_], sp[s_ + 1]))
-    assert all(v is not None for v in buf)
-    assert buf[:C] == torch.bincount(cid.long(), minlength=C).tolist()
+    assert _run_seg_tables(levels, [1] * N)[:C] == torch.bincount(cid.long(), minlength=C).tolist()
+
+
+@pytest.mark.parametrize('ctype', ['aig', 'xmg'])
+def test_quotient_colours_equal_brute_force_refinement(ctype):
+    """GraphPlan.quotient (host logic of the structural encoder's quotient stages): the colours of half round t equal colour
+    refinement done literally — (feature class, previous colour, sorted tuple of the neighbours' previous colours) over the in-CSR for odd t,
+    the out-CSR for even t — a representative's list names its neighbours' previous colours, xcls / own / own32 are its members'
+    class and previous colour, and the segment tables (own / ent / final sums) add up."""
+    _check_stages_against_brute_force(*_batch_quotient([syn.make_graph(ctype, 200 + 30 * 40, 40, 5 + i, n_inputs=200) for i in range(2)], 1.5))
+
+
+def test_second_copy_of_a_graph_adds_no_colour_to_the_batch():
+    """Colours are shared ACROSS the graphs of a batch: with a second copy of graph 0 every stage has as many colours as the three
+    distinct graphs alone (the copy's nodes carry their originals' signatures), and the stages still equal brute force."""
+    graphs = [syn.make_graph('xmg', 120 + 25 * 30, 30, 70 + i, n_inputs=120) for i in range(3)]
+    a4, xcls4, q4 = _batch_quotient(graphs + [syn.make_graph('xmg', 120 + 25 * 30, 30, 70, n_inputs=120)], 1.3)
+    # the stopping rules compare C * fraction with N: scaled by the node counts, the three graphs alone stop where the four do
+    n3 = sum(int(g['num_nodes']) for g in graphs)
+    _, _, q3 = _batch_quotient(graphs, 1.3 * n3 / a4['num_nodes'])
+    assert [s['C'] for s in q4] == [s['C'] for s in q3]
+    _check_stages_against_brute_force(a4, xcls4, q4)
 
 
 def test_quotient_stages_only_from_the_break_even_batch_size():
@@ -412,154 +451,6 @@ def test_packed_sweep_rows_name_the_first_sources_and_consumers_of_every_updated
         assert np.all(r[26:] == -1)
         for e in cons:                                       # the pair really is that edge seen from the consumer
             assert isrc[osl[e]] == v
-
-
-def _run_seg_tables(levels, items_value):
-    """Run mgv_seg_sum's tables on one number per item: the buffer of `rows` sums (every row written exactly once)."""
-    buf = [None] * levels['rows']
-    for li, (n_seg, sp, out_row, src_row) in enumerate(levels['levels']):
-        sp = sp.tolist()
-        rows = out_row.tolist() if out_row is not None else list(range(n_seg))
-        assert len(sp) == n_seg + 1 and sp[0] == 0 and all(0 <= b - a_ <= 64 for a_, b in zip(sp[:-1], sp[1:]))
-        src = items_value if li == 0 else buf[src_row:]
-        for s_, r in enumerate(rows):
-            assert buf[r] is None
-            buf[r] = sum(src[m] for m in range(sp[s_], sp[s_ + 1]))
-    assert all(v is not None for v in buf)
-    return buf
-
-
-def test_batch_quotient_assembled_from_per_graph_stages():
-    """GraphPlan.assemble_quotient: a batch's quotient stages put together from its graphs' own (cached) stages by index arithmetic.
-    Per graph the colours equal brute-force colour refinement; colours are never shared between graphs; a representative's list
-    names its neighbours' previous colours in the BATCH numbering; the segment tables (own / ent / final sums) add up."""
-    graphs = [syn.make_graph('xmg', 120 + 25 * 30, 30, 50 + i, n_inputs=120) for i in range(3)]
-    graphs.append(syn.make_graph('xmg', 120 + 25 * 30, 30, 50, n_inputs=120))          # a copy of graph 0: still its own colours
-    a = syn.collate(graphs)
-    N, ei = a['num_nodes'], a['edge_index']
-    node_off = a['graph_ptr'].tolist()
-    old = GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES
-    GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = 1.3, 1
-    try:
-        parts = []
-        for g in graphs:
-            xc = torch.from_numpy(g['x'][:, 1].astype('uint8'))
-            parts.append(GraphPlan(torch.from_numpy(g['edge_index']), g['num_nodes']).quotient(xc, 3, force=True))
-        plan = GraphPlan(torch.from_numpy(ei), N)
-        plan.xcls = torch.from_numpy(a['x'][:, 1].astype('uint8'))
-        out = plan.assemble_quotient(parts, node_off, [2, 3])
-        assert plan.quotient(plan.xcls, 3) is out[3] and plan.quotient(plan.xcls, 2) is out[2]      # installed as the plan's cache
-    finally:
-        GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = old
-    q = out[3]
-    assert len(q) >= 2 and len(out[2]) == 2 and 'sum_levels' in out[2][-1] and 'sum_levels' in q[-1]
-    xcls = plan.xcls
-    gid = np.repeat(np.arange(len(graphs)), np.diff(node_off))
-    col = [0] * N
-    for t, s in enumerate(q, start=1):
-        src, dst = (ei[1], ei[0]) if t % 2 == 0 else (ei[0], ei[1])
-        nb = [[] for _ in range(N)]
-        for u, v in zip(src.tolist(), dst.tolist()):
-            nb[v].append(col[u])
-        keys = [(int(gid[i]), int(xcls[i]), col[i], tuple(sorted(nb[i]))) for i in range(N)]      # the graph id is part of the colour
-        ids = {}
-        for kk in keys:
-            ids.setdefault(kk, len(ids))
-        cid = s['cid'].tolist()
-        assert len(set(zip((ids[kk] for kk in keys), cid))) == len(ids) == s['C'], t
-        prev_cid = q[t - 2]['cid'].tolist() if t > 1 else [0] * N
-        Cp = q[t - 2]['C'] if t > 1 else 1
-        first = {}
-        for i, c in enumerate(cid):
-            first.setdefault(c, i)
-        ptr, idx, ent, own, xc = s['ptr'].tolist(), s['idx'].tolist(), s['ent_idx'].tolist(), s['own'].tolist(), s['xcls'].tolist()
-        for c in range(s['C']):
-            members = [i for i in range(N) if cid[i] == c]
-            assert len({(prev_cid[i], int(xcls[i])) for i in members}) == 1 and xc[c] == int(xcls[members[0]]) and own[c] == prev_cid[members[0]]
-            r = members[0]
-            want = sorted(prev_cid[u] for u, v in zip(src.tolist(), dst.tolist()) if v == r)
-            assert sorted(ent[ptr[c]:ptr[c + 1]]) == want and sorted(idx[ptr[c]:ptr[c + 1]]) == [s['C'] + w for w in want], (t, c)
-        # colour-level sums for stage t-1: per previous colour, the representatives that own it / the entries that name it
-        buf = _run_seg_tables(s['own_levels'], [1] * s['C'])
-        assert s['own_levels']['C'] == Cp and sorted(s['own_rows'].tolist()) == list(range(s['C']))
-        assert buf[:Cp] == np.bincount(np.asarray(own), minlength=Cp).tolist()
-        n_ent = ptr[-1]
-        if n_ent:
-            rows_of_entries = s['ent_rows'].tolist()
-            owner = np.repeat(np.arange(s['C']), np.diff(ptr))
-            # ent_rows[k] = the colour whose list holds the k-th entry in previous-colour order: a permutation of the entries' owners
-            assert sorted(rows_of_entries) == sorted(owner.tolist())
-            buf = _run_seg_tables(s['ent_levels'], [1] * n_ent)
-            assert buf[:Cp] == np.bincount(np.asarray(ent[:n_ent]), minlength=Cp).tolist()
-        col = [ids[kk] for kk in keys]
-    for lst in (out[2], out[3]):
-        order, levels = lst[-1]['sum_levels']
-        cidl = lst[-1]['cid']
-        assert sorted(order.tolist()) == list(range(N)) and bool((cidl[order.long()][1:] >= cidl[order.long()][:-1]).all())
-        assert _run_seg_tables(levels, [1] * N)[:lst[-1]['C']] == torch.bincount(cidl.long(), minlength=lst[-1]['C']).tolist()
-
-
-def test_batch_quotient_merged_through_the_dataset_wide_colour_dictionary():
-    """GraphPlan.assemble_quotient_merged + ColourDictionary: the graphs' own colours merged by their dataset-wide global ids give
-    exactly the batch-level colour refinement (the partition brute force finds on the whole batch, colours shared ACROSS graphs —
-    a copy of a graph adds no colour), the representatives' lists name merged previous colours, the segment tables add up."""
-    from deepgate.graph_plan import ColourDictionary
-    graphs = [syn.make_graph('xmg', 120 + 25 * 30, 30, 70 + i, n_inputs=120) for i in range(3)]
-    graphs.append(syn.make_graph('xmg', 120 + 25 * 30, 30, 70, n_inputs=120))          # a copy of graph 0
-    a = syn.collate(graphs)
-    N, ei = a['num_nodes'], a['edge_index']
-    node_off = a['graph_ptr'].tolist()
-    old = GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES
-    GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = 1.3, 1
-    try:
-        cd = ColourDictionary()
-        parts, gcols = [], []
-        for g in graphs:
-            xc = torch.from_numpy(g['x'][:, 1].astype('uint8'))
-            st = GraphPlan(torch.from_numpy(g['edge_index']), g['num_nodes']).quotient(xc, 3, force=True)
-            parts.append(st)
-            host = [dict(ptr=s_['raw']['rptr'].numpy(), ent=s_['raw']['ent'].numpy(), own=s_['raw']['own'].numpy(), xcls=s_['xcls'].numpy()) for s_ in st]
-            gcols.append([torch.from_numpy(v) for v in cd.globals_of(host)])
-        assert all(torch.equal(x, y) for x, y in zip(gcols[0], gcols[3]))               # the copy: the same global colours
-        plan = GraphPlan(torch.from_numpy(ei), N)
-        plan.xcls = torch.from_numpy(a['x'][:, 1].astype('uint8'))
-        out = plan.assemble_quotient_merged(parts, gcols, node_off, [2, 3])
-        assert plan.quotient(plan.xcls, 3) is out[3]
-        ref = GraphPlan(torch.from_numpy(ei), N).quotient(plan.xcls, 3)                # the batch-level refinement
-    finally:
-        GraphPlan.QUOTIENT_FRACTION, GraphPlan.QUOTIENT_MIN_NODES = old
-    q = out[3]
-    assert len(q) >= 2 and len(q) == len(ref) and [s['C'] for s in q] == [s['C'] for s in ref]
-    xcls = plan.xcls
-    col = [0] * N
-    for t, s in enumerate(q, start=1):
-        src, dst = (ei[1], ei[0]) if t % 2 == 0 else (ei[0], ei[1])
-        nb = [[] for _ in range(N)]
-        for u, v in zip(src.tolist(), dst.tolist()):
-            nb[v].append(col[u])
-        keys = [(int(xcls[i]), col[i], tuple(sorted(nb[i]))) for i in range(N)]        # no graph id: colours are shared
-        ids = {}
-        for kk in keys:
-            ids.setdefault(kk, len(ids))
-        cid = s['cid'].tolist()
-        assert len(set(zip((ids[kk] for kk in keys), cid))) == len(ids) == s['C'], t
-        assert len(set(zip(cid, ref[t - 1]['cid'].tolist()))) == s['C']                 # the same partition as GraphPlan.quotient
-        prev_cid = q[t - 2]['cid'].tolist() if t > 1 else [0] * N
-        Cp = q[t - 2]['C'] if t > 1 else 1
-        ptr, ent, own, xc = s['ptr'].tolist(), s['ent_idx'].tolist(), s['own'].tolist(), s['xcls'].tolist()
-        first = {}
-        for i, c in enumerate(cid):
-            first.setdefault(c, i)
-        for c in range(s['C']):
-            r = first[c]
-            assert xc[c] == int(xcls[r]) and own[c] == prev_cid[r]
-            assert sorted(ent[ptr[c]:ptr[c + 1]]) == sorted(prev_cid[u] for u, v in zip(src.tolist(), dst.tolist()) if v == r), (t, c)
-        assert _run_seg_tables(s['own_levels'], [1] * s['C'])[:Cp] == np.bincount(np.asarray(own), minlength=Cp).tolist()
-        if ptr[-1]:
-            assert _run_seg_tables(s['ent_levels'], [1] * ptr[-1])[:Cp] == np.bincount(np.asarray(ent[:ptr[-1]]), minlength=Cp).tolist()
-        col = [ids[kk] for kk in keys]
-    order, levels = q[-1]['sum_levels']
-    assert _run_seg_tables(levels, [1] * N)[:q[-1]['C']] == torch.bincount(q[-1]['cid'].long(), minlength=q[-1]['C']).tolist()
 
 
 def test_self_loop_count_and_key_bits():
