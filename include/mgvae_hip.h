@@ -86,7 +86,9 @@ int mgv_struct_stage_rows_bwd(int H, int64_t N, const float* h_in, const int32_t
  * previous stage's colour table, a representative's own row is its previous colour's, its list names previous colours).
  * ln_stats_out (forward) / ln_stats (bwd2) [N][2], NULL = off: {mean, rstd} of every row's pre-LayerNorm state, kept by the forward
  * so that the backward's recompute needs two cross-lane row sums instead of four and no four-way combination of the column waves'
- * partial statistics (-3 % per backward launch); ignored when ln_w is NULL. */
+ * partial statistics (-3 % per backward launch); ignored when ln_w is NULL.
+ * mgv_struct_stage_bwd_x3 (the first backward) serves H = 32 only: with valid arguments it returns MGV_EUNSUPPORTED at H = 64, whose
+ * backward is mgv_struct_stage_bwd2_x3 below. */
 int mgv_struct_stage_fwd_x3(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                             const uint8_t* xcls, const float* xtab, int C, const void* wpack_bf16, const float* bc,
                             const float* bhh, const float* ln_w, const float* ln_b, float ln_eps, float* h_out,

@@ -12,11 +12,9 @@
 //     rows, all of a row's loads in flight together.  8 waves per workgroup, two rows per 16-lane group.
 #include "func_level_x3_common.h"
 
-#ifndef MGV_LVL_FWD_KU
-#define MGV_LVL_FWD_KU 4        // k-steps whose weight fragments the forward requests together (1: four dependent L2 trips per tile; 4: one, 100 VGPRs)
-#endif
-
 namespace mgv {
+
+constexpr int kLvlFwdKU = 4;    // k-steps whose weight fragments the forward requests together (1: four dependent L2 trips per tile; 4: one, 100 VGPRs)
 
 template <int H, bool HID = false>
 __global__ __launch_bounds__(kLT, 4) void k_level_fwd_x3(LevelX3Args a) {
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(kLT, 4) void k_level_fwd_x3(LevelX3Args a) {
     lds_barrier();
     STAMP(3);
     f32x4 ar[S::RTW], az[S::RTW], an[S::RTW];
-    lvl_gemm_x3<H, MGV_LVL_FWD_KU>(a.wpack + (int64_t)g * 4 * 6 * H * H, z_hi, z_lo, ar, az, an);
+    lvl_gemm_x3<H, kLvlFwdKU>(a.wpack + (int64_t)g * 4 * 6 * H * H, z_hi, z_lo, ar, az, an);
     STAMP(4);
     lds_barrier();                   // s_o overlays the planes
     {
@@ -163,16 +161,6 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
     STAMP(1);
     const float4 us = ld4(sv.u + 4 * lr), uf = ld4(sv.u + H + 4 * lr);
     // ---- 0/1. pull dL/dhf and dL/dhs of the tile's nodes from their consumers, recompute their attention
-#ifndef MGV_LVL_EARLY_Z
-#define MGV_LVL_EARLY_Z 1
-#endif
-#ifndef MGV_LVL_EARLY_GHS
-#define MGV_LVL_EARLY_GHS 1     // dL/dhs rows leave in the pull phase (8 registers less across the MFMA phases: 22 -> 10 spilled, backward sweep 7.24 -> 6.78 ms)
-#endif
-#if !MGV_LVL_EARLY_GHS
-    float4 gs_keep[2] = {zero4(), zero4()};      // dL/dhs rows, stored at the end
-#endif
-    static_assert(RPG <= 2, "two kept rows");
 #pragma unroll 1
     for (int i = 0; i < RPG; ++i) {
         const int row = grp + i * GROUPS;
@@ -210,21 +198,16 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
         }
         float4 dh = zero4();
         if (node >= 0) dh = add4(gf, f4(own));
-#if MGV_LVL_EARLY_GHS
+        // dL/dhs rows leave here, in the pull phase, not at the tile's end (8 registers less across the MFMA phases: 22 -> 10 spilled, backward sweep 7.24 -> 6.78 ms)
         if (row < count) st4(a.ghs + (int64_t)node * H + 4 * lr, gs);
-#else
-        if (i == 0) gs_keep[0] = gs; else gs_keep[1] = gs;
-#endif
         float m, inv;
         float4 zs, zf;
         attn_reduce<H>(a, L, sp, us, uf, lr, m, inv, zs, zf);
         store_zbar<H>(z_hi, z_lo, row, lr, zs, zf);
-#if MGV_LVL_EARLY_Z
         if (row < count) {               // the zbar row for the deferred weight gradient leaves here, in fp32 as formed (not re-read from the planes)
             st4(a.zrows + (int64_t)(start + row) * 2 * H + 4 * lr, zs);
             st4(a.zrows + (int64_t)(start + row) * 2 * H + H + 4 * lr, zf);
         }
-#endif
         st4(s_dh + row * LDO + 4 * lr, dh);
         if (lr == 0) { sv.sa[row] = sp.y > sp.x ? 1.0f : 0.0f; sv.m[row] = m; sv.inv[row] = inv; }
     }
@@ -324,12 +307,9 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
             }
         STAMP(7);
     }
-#ifndef MGV_LVL_EARLY_DG
-#define MGV_LVL_EARLY_DG 1        // with the early dL/dhs store and the re-read attention vector: 22 -> 2 spilled registers, backward sweep 7.4 -> 6.85 ms
-#endif
-#if MGV_LVL_EARLY_DG
-    // (behind the passes, not at the end of the tile: the 24 gate-gradient registers are free during the attention backward)
-    // gate gradients of the tile's rows, for the weight-gradient kernel
+    // gate gradients of the tile's rows, for the weight-gradient kernel (behind the passes, not at the end of the tile: the 24
+    // gate-gradient registers are free during the attention backward; with the early dL/dhs store and the re-read attention vector:
+    // 22 -> 2 spilled registers, backward sweep 7.4 -> 6.85 ms)
     {
         const int col = wc * 16 + r;
 #pragma unroll
@@ -343,7 +323,6 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
                 }
             }
     }
-#endif
     // ---- 5. d(zbar) tile to LDS (fp32, row layout for the attention backward); it overlays the dG planes
     lds_barrier();
 #pragma unroll
@@ -371,12 +350,6 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
         for (int i = 0; i < RPG; ++i) {
             const int row = grp + i * GROUPS;
             const float4 dzs = ld4(s_dz + row * LDZF + 4 * lr), dzf = ld4(s_dz + row * LDZF + H + 4 * lr);
-#if !MGV_LVL_EARLY_Z
-            const bf16x4 zsh = *reinterpret_cast<const bf16x4*>(z_hi + row * LDZP + 4 * lr), zsl = *reinterpret_cast<const bf16x4*>(z_lo + row * LDZP + 4 * lr);
-            const bf16x4 zfh = *reinterpret_cast<const bf16x4*>(z_hi + row * LDZP + H + 4 * lr), zfl = *reinterpret_cast<const bf16x4*>(z_lo + row * LDZP + H + 4 * lr);
-            const float4 zs = make_float4((float)zsh[0] + (float)zsl[0], (float)zsh[1] + (float)zsl[1], (float)zsh[2] + (float)zsl[2], (float)zsh[3] + (float)zsl[3]);
-            const float4 zf = make_float4((float)zfh[0] + (float)zfl[0], (float)zfh[1] + (float)zfl[1], (float)zfh[2] + (float)zfl[2], (float)zfh[3] + (float)zfl[3]);
-#endif
             if (row < count) attn_bwd_row<H>(a, L[i], sp[i], us6, uf6, dzs, dzf, sv.m[row], sv.inv[row], lr, al[i], ds[i], gus, guf);
             if (i == 0) { STAMP(12); } else { STAMP(14); }
             if (i + 1 < RPG) {
@@ -385,16 +358,8 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
             }
             if (row < count) {
                 const int64_t node = ix.node[row];
-                const int64_t pos = start + row;
                 st4(a.dzb + node * 2 * H + 4 * lr, dzs);
                 st4(a.dzb + node * 2 * H + H + 4 * lr, dzf);
-#if !MGV_LVL_EARLY_Z
-                st4(a.zrows + pos * 2 * H + 4 * lr, zs);
-                st4(a.zrows + pos * 2 * H + H + 4 * lr, zf);
-#endif
-#if !MGV_LVL_EARLY_GHS
-                st4(a.ghs + node * H + 4 * lr, gs_keep[i]);
-#endif
                 const int deg = sp[i].y - sp[i].x;
                 if (lr == 0) {
 #pragma unroll
@@ -406,22 +371,6 @@ __global__ __launch_bounds__(kLT, 4) void k_level_bwd_x3(LevelX3Args a) {
         }
     }
     STAMP(10);
-#if !MGV_LVL_EARLY_DG
-    // gate gradients of the tile's rows, for the weight-gradient kernel
-    {
-        const int col = wc * 16 + r;
-#pragma unroll
-        for (int i = 0; i < S::RTW; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int row = (wr * S::RTW + i) * 16 + q * 4 + e;
-                if (row < count) {
-                    float* dg = a.dgrows + (int64_t)(start + row) * 3 * H + col;
-                    dg[0] = ar[i][e]; dg[H] = az[i][e]; dg[2 * H] = an[i][e];
-                }
-            }
-    }
-#endif
     // d(attention vector): the lane groups of a wave that share a column quad meet by shuffles (fixed tree), the eight waves through
     // an LDS stage over the (now dead) zbar planes, summed in wave order — no LDS float atomics, bit-reproducible
     {

@@ -569,27 +569,60 @@ int launch_bwd(const StageArgs& a, hipStream_t st) {
     MGV_LAUNCH_RET();
 }
 
+// ---- the one place that validates and fills the arguments of the four entries.  The caller has put the feature term into `a`: xcls, xtab
+// and C (class table), or xrow and C = 1 (general node features).  An entry runs: these checks (MGV_EINVAL), then N == 0 (MGV_OK), then
+// nbr_idx, then the width (stage_run).
+static int stage_args(StageArgs& a, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx, const float* Wc,
+                      const float* bc, const float* Whh, const float* bhh, const float* ln_w, const float* ln_b, float ln_eps) {
+    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && (a.xrow || (a.xcls && a.xtab)) && Wc && bc && Whh && bhh);
+    MGV_CHECK_ARG(a.C >= 1 && a.C <= kMaxCls);
+    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
+    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx;
+    a.Wc = Wc; a.bc = bc; a.Whh = Whh; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
+    return MGV_OK;
+}
+
+// the backward's own checks and fields; dx is dxtab, or d_xrow with general node features
+static int stage_bwd_args(StageArgs& a, const float* WcT, const float* WhhT, const float* gy_direct, const float* gy_agg, float* g_direct_out,
+                          float* g_agg_out, float* dWc, float* dbc, float* dWhh, float* dbhh, float* dx, float* dln_w, float* dln_b) {
+    MGV_CHECK_ARG(WcT && WhhT && gy_direct && dWc && dbc && dWhh && dbhh && dx);
+    MGV_CHECK_ARG(a.lnw == nullptr || (dln_w && dln_b));
+    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
+    a.WcT = WcT; a.WhhT = WhhT; a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out; a.g_agg_out = g_agg_out;
+    a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dlnw = dln_w; a.dlnb = dln_b;
+    if (a.xrow) a.d_xrow = dx; else a.dxtab = dx;
+    return MGV_OK;
+}
+
+static int stage_run(int H, const StageArgs& a, bool bwd, void* stream) {
+    if (a.N == 0) return MGV_OK;
+    MGV_CHECK_ARG(a.idx != nullptr);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!bwd) switch (H) {
+        case 16: return launch_fwd<16>(a, st);
+        case 32: return launch_fwd<32>(a, st);
+        case 64: return launch_fwd<64>(a, st);
+        default: return MGV_EUNSUPPORTED;
+    }
+    switch (H) {
+        case 16: return launch_bwd<16>(a, st);
+        case 32: return launch_bwd<32>(a, st);
+        case 64: return launch_bwd<64>(a, st);
+        default: return MGV_EUNSUPPORTED;
+    }
+}
+
 }  // namespace mgv
 
 extern "C" int mgv_struct_stage_fwd(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                                     const uint8_t* xcls, const float* xtab, int C, const float* Wc, const float* bc,
                                     const float* Whh, const float* bhh, const float* ln_w, const float* ln_b, float ln_eps,
                                     float* h_out, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && Wc && bc && Whh && bhh && h_out);
-    MGV_CHECK_ARG(C >= 1 && C <= mgv::kMaxCls);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
     mgv::StageArgs a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
-    a.Wc = Wc; a.bc = bc; a.Whh = Whh; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps; a.h_out = h_out;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 16: return mgv::launch_fwd<16>(a, st);
-        case 32: return mgv::launch_fwd<32>(a, st);
-        case 64: return mgv::launch_fwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    a.xcls = xcls; a.xtab = xtab; a.C = C; a.h_out = h_out;
+    if (int rc = mgv::stage_args(a, N, h_in, nbr_ptr, nbr_idx, Wc, bc, Whh, bhh, ln_w, ln_b, ln_eps)) return rc;
+    MGV_CHECK_ARG(h_out != nullptr);
+    return mgv::stage_run(H, a, false, stream);
 }
 
 extern "C" int mgv_struct_stage_bwd(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
@@ -598,27 +631,11 @@ extern "C" int mgv_struct_stage_bwd(int H, int64_t N, const float* h_in, const i
                                     const float* ln_w, const float* ln_b, float ln_eps, const float* gy_direct,
                                     const float* gy_agg, float* g_direct_out, float* g_agg_out, float* dWc, float* dbc,
                                     float* dWhh, float* dbhh, float* dxtab, float* dln_w, float* dln_b, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && Wc && WcT && bc && Whh && WhhT && bhh && gy_direct);
-    MGV_CHECK_ARG(dWc && dbc && dWhh && dbhh && dxtab);
-    MGV_CHECK_ARG(C >= 1 && C <= mgv::kMaxCls);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    MGV_CHECK_ARG(ln_w == nullptr || (dln_w && dln_b));
-    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
     mgv::StageArgs a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
-    a.Wc = Wc; a.bc = bc; a.Whh = Whh; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
-    a.WcT = WcT; a.WhhT = WhhT; a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out;
-    a.g_agg_out = g_agg_out; a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dxtab = dxtab;
-    a.dlnw = dln_w; a.dlnb = dln_b;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 16: return mgv::launch_bwd<16>(a, st);
-        case 32: return mgv::launch_bwd<32>(a, st);
-        case 64: return mgv::launch_bwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    a.xcls = xcls; a.xtab = xtab; a.C = C;
+    if (int rc = mgv::stage_args(a, N, h_in, nbr_ptr, nbr_idx, Wc, bc, Whh, bhh, ln_w, ln_b, ln_eps)) return rc;
+    if (int rc = mgv::stage_bwd_args(a, WcT, WhhT, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, dxtab, dln_w, dln_b)) return rc;
+    return mgv::stage_run(H, a, true, stream);
 }
 
 // ---- general node features: the same half round with the GRU's feature term per NODE (xrow [N][3H] = W_ih[:, H:] x_i + b_ih, formed by
@@ -626,20 +643,11 @@ extern "C" int mgv_struct_stage_bwd(int H, int64_t N, const float* h_in, const i
 extern "C" int mgv_struct_stage_rows_fwd(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                                          const float* xrow, const float* Wc, const float* bc, const float* Whh, const float* bhh,
                                          const float* ln_w, const float* ln_b, float ln_eps, float* h_out, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xrow && Wc && bc && Whh && bhh && h_out);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
     mgv::StageArgs a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.C = 1; a.xrow = xrow;
-    a.Wc = Wc; a.bc = bc; a.Whh = Whh; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps; a.h_out = h_out;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 16: return mgv::launch_fwd<16>(a, st);
-        case 32: return mgv::launch_fwd<32>(a, st);
-        case 64: return mgv::launch_fwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    a.xrow = xrow; a.C = 1; a.h_out = h_out;
+    if (int rc = mgv::stage_args(a, N, h_in, nbr_ptr, nbr_idx, Wc, bc, Whh, bhh, ln_w, ln_b, ln_eps)) return rc;
+    MGV_CHECK_ARG(h_out != nullptr);
+    return mgv::stage_run(H, a, false, stream);
 }
 
 extern "C" int mgv_struct_stage_rows_bwd(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
@@ -648,24 +656,9 @@ extern "C" int mgv_struct_stage_rows_bwd(int H, int64_t N, const float* h_in, co
                                          const float* gy_direct, const float* gy_agg, float* g_direct_out, float* g_agg_out,
                                          float* dWc, float* dbc, float* dWhh, float* dbhh, float* d_xrow, float* dln_w, float* dln_b,
                                          void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xrow && Wc && WcT && bc && Whh && WhhT && bhh && gy_direct);
-    MGV_CHECK_ARG(dWc && dbc && dWhh && dbhh && d_xrow);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    MGV_CHECK_ARG(ln_w == nullptr || (dln_w && dln_b));
-    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
     mgv::StageArgs a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.C = 1; a.xrow = xrow; a.d_xrow = d_xrow;
-    a.Wc = Wc; a.bc = bc; a.Whh = Whh; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
-    a.WcT = WcT; a.WhhT = WhhT; a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out;
-    a.g_agg_out = g_agg_out; a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dxtab = nullptr;
-    a.dlnw = dln_w; a.dlnb = dln_b;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 16: return mgv::launch_bwd<16>(a, st);
-        case 32: return mgv::launch_bwd<32>(a, st);
-        case 64: return mgv::launch_bwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    a.xrow = xrow; a.C = 1;
+    if (int rc = mgv::stage_args(a, N, h_in, nbr_ptr, nbr_idx, Wc, bc, Whh, bhh, ln_w, ln_b, ln_eps)) return rc;
+    if (int rc = mgv::stage_bwd_args(a, WcT, WhhT, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, d_xrow, dln_w, dln_b)) return rc;
+    return mgv::stage_run(H, a, true, stream);
 }

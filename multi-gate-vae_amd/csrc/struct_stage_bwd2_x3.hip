@@ -18,24 +18,15 @@
 //     bit-identical from run to run.
 //   * weight gradients keep all three products of bf16x3: on one bf16 product per term (hi x hi) a launch is 6.7 % shorter but the
 //     gradients are off by 2.5e-3 of their scale against the 1e-3 bar (measured in round 4, NOTEBOOK R4.4b), so that form is not kept.
+//   * timing ablations of this kernel (builds without its MFMAs, phase arithmetic, row gathers, output stores or per-tile weight reloads,
+//     wrong by design) priced its phases in round 3: profiles/r03_struct_bwd_ablation.txt, NOTEBOOK r3 §4.1; they are no longer in this source.
 #include <cstddef>
 #include <type_traits>
 #include "struct_stage_x3_common.h"
-#ifndef MGV_BWD2_D
-#define MGV_BWD2_D 3            // neighbour slots per row and gather round (2 x 3 x 2 row loads in flight per lane; 2: 1-2 % slower, same box)
-#endif
-#ifndef MGV_ABL
-#define MGV_ABL 0            // timing ablations of diagnostic builds (results are wrong): 1 no MFMA, 2 light VALU in P2/P3, 4 no row gathers, 8 no output stores, 16 dgrad weights loaded once, 32 (with 1) no LDS fragment reads
-#endif
 
 namespace mgv {
 
-#if (MGV_ABL & 33) == 33
-#define mma_x3(c, ah, al, bh, bl) ((void)0)                  // and no LDS fragment reads either
-#elif MGV_ABL & 1
-#define mma_x3(c, ah, al, bh, bl) asm volatile("" :: "v"(ah), "v"(al), "v"(bh), "v"(bl))
-#endif
-
+constexpr int kBwd2D = 3;       // neighbour slots per row and gather round (2 x 3 x 2 row loads in flight per lane; 2: 1-2 % slower, same box)
 
 struct B2 {
     static constexpr int H = 64;
@@ -195,11 +186,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd2_x3(B2Args args
                     if (node < a.N) st_r[rr] = a.ln_stats[node * 2 + lr];
                 }
             }
-#if MGV_ABL & 4
-            for (int rr = 0; rr < 2; ++rr) { acc[rr] = make_float4(0.1f * lr, 0.2f, 0.3f, 0.4f); own[rr] = acc[rr]; dy[rr] = acc[rr]; deg[rr] = 2.f; cls[rr] = 1; }
-#else
-            tile_rows<H, 2, true, MGV_BWD2_D>(a, base, grp, 32, lr, idx_lds(idx_base, b).ptr, idx_lds(idx_base, b).idx, *idx_lds(idx_base, b).dmax(), acc, own, dy, deg, cls);
-#endif
+            tile_rows<H, 2, true, kBwd2D>(a, base, grp, 32, lr, idx_lds(idx_base, b).ptr, idx_lds(idx_base, b).idx, *idx_lds(idx_base, b).dmax(), acc, own, dy, deg, cls);
             // (0) the previous tile's P4 (last reader of the planes and of xe) is over in every wave; placed here, behind the
             //     gather, it waits where the waves wait for memory anyway
             __syncthreads();
@@ -311,10 +298,6 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd2_x3(B2Args args
             const f32x4 rx0 = s_ex[(w * 6 + il * 3 + 0) * 64 + lane], rx1 = s_ex[(w * 6 + il * 3 + 1) * 64 + lane], rx2 = s_ex[(w * 6 + il * 3 + 2) * 64 + lane];
             const f32x4 sr = rx0 + oa[0][il], sz = rx1 + oa[1][il];
             const f32x4 pn = m ? rx2 : oa[2][il], hn = m ? oa[2][il] : rx2;
-#if MGV_ABL & 2
-            vr[il] = rx0 + oa[0][il]; vz[il] = rx1 + oa[1][il]; vn[il] = rx2 + oa[2][il]; vg[il] = vr[il]; vd[il] = vz[il]; mw[il] = (float)row;
-            continue;
-#endif
             const float deg = sv.deg[row];
             const float* xt = sv.xtab + sv.cls[row] * 3 * H + c0;
             const bf16x4 hh = *reinterpret_cast<const bf16x4*>(hin_hi + row * LDP + c0);
@@ -365,19 +348,6 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd2_x3(B2Args args
         for (int il = 0; il < 2; ++il) {
             LANE_IDS
             const int row = 16 * (2 * m + il) + r;
-#if MGV_ABL & 2
-            {
-                __bf16* dst = s_dg + row * LDP + c0;
-                const bf16x4 h0 = bf16x4{(__bf16)vr[il][0], (__bf16)vr[il][1], (__bf16)vr[il][2], (__bf16)vr[il][3]};
-                const bf16x4 h1 = bf16x4{(__bf16)vz[il][0], (__bf16)vz[il][1], (__bf16)vz[il][2], (__bf16)vz[il][3]};
-                const bf16x4 h2 = bf16x4{(__bf16)vn[il][0], (__bf16)vn[il][1], (__bf16)vn[il][2], (__bf16)vn[il][3]};
-                st_bf4(dst, h0); st_bf4(dst + PE, h1); st_bf4(dst + 2 * PE, h2); st_bf4(dst + 3 * PE, h0);
-                st_bf4(dst + 4 * PE, h1); st_bf4(dst + 5 * PE, h2); st_bf4(dst + 6 * PE, h0); st_bf4(dst + 7 * PE, h1);
-                dhz[il] = vd[il] + mw[il];
-                if (m == 0) s_dhz[(wc * 2 + il) * 64 + lane] = dhz[il];
-                continue;
-            }
-#endif
             const float4 dy = ld4(s_dy + row * LDF + c0);
             const float dy_[4] = {dy.x, dy.y, dy.z, dy.w};
             const bf16x4 hh = *reinterpret_cast<const bf16x4*>(hin_hi + row * LDP + c0);
@@ -471,9 +441,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd2_x3(B2Args args
             const int it0 = 2 * (wc >> 1), jt0 = 2 * (wc & 1), ig = wc & 1;
             bf16x8 wd_hi[3], wd_lo[3];
             int oz = 0;
-#if !(MGV_ABL & 16)
             asm volatile("" : "+s"(oz));                    // opaque per tile: keeps the (loop-invariant) loads inside the loop
-#endif
             const __bf16* wd_p = a.wpack + wd_off + oz;
             if (need_dgrad) {
 #pragma unroll
@@ -537,11 +505,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd2_x3(B2Args args
                         mma_x3(dgo[i], wd_hi[k], wd_lo[k], ldfrag(ph + off), ldfrag(ph + PE + off));
                     }
                     const int64_t node = base + i * 16 + r;
-#if MGV_ABL & 8
-                    if (node < a.N && dgo[i][0] == 1.2345e-30f) *reinterpret_cast<f32x4*>(go + node * H + c0) = dgo[i];
-#else
                     if (node < a.N) *reinterpret_cast<f32x4*>(go + node * H + c0) = dgo[i];
-#endif
                 }
             }
         }
@@ -673,33 +637,15 @@ extern "C" int mgv_struct_stage_bwd2_x3(int H, int64_t N, const float* h_in, con
                                         float* dln_b, float* workspace, int64_t workspace_floats, int heavy_n,
                                         const int32_t* heavy_nodes, float* heavy_ws, const int32_t* table_own_idx,
                                         int nbr_tagged, const float* ln_stats, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && wpack_bf16 && bc && bhh && gy_direct);
-    MGV_CHECK_ARG(dWc && dbc && dWhh && dbhh && dxtab);
-    MGV_CHECK_ARG(C >= 1 && C <= mgv::kMaxClsX3);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    MGV_CHECK_ARG(ln_w == nullptr || (dln_w && dln_b));
-    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
+    mgv::StageX3Args a{};
+    if (int rc = mgv::stage_x3_args(a, N, h_in, nbr_ptr, nbr_idx, xcls, xtab, C, wpack_bf16, bc, bhh, ln_w, ln_b, ln_eps, table_own_idx, nbr_tagged, const_cast<float*>(ln_stats))) return rc;
+    if (int rc = mgv::stage_x3_bwd_args(a, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, dxtab, dln_w, dln_b)) return rc;
     if (H != 64) return MGV_EUNSUPPORTED;
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
-    mgv::StageX3Args a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
-    a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bc = bc; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
-    a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out; a.g_agg_out = g_agg_out;
-    a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dxtab = dxtab; a.dlnw = dln_w; a.dlnb = dln_b;
-    a.gmask = -1;
-    MGV_CHECK_ARG(table_own_idx == nullptr || !nbr_tagged || N < (1 << 24));
-    if (table_own_idx) { a.own_idx = table_own_idx; if (nbr_tagged) { a.hshift = 24; a.gmask = 0xffffff; } }
-    a.ln_stats = ln_w ? const_cast<float*>(ln_stats) : nullptr;
+    if (int rc = mgv::stage_x3_lists(N, heavy_n, heavy_nodes, heavy_ws, table_own_idx, nbr_tagged)) return rc;
     MGV_SET_STAMPS2(a);
-    a.xcd = 1;           // XCD-contiguous tile order and the L2 row prefetch: both measured, no switch left
-    a.prefetch = (table_own_idx && !nbr_tagged) ? 0 : 1;      // (own rows through an index into a shorter h_in: the row prefetch assumes N rows behind h_in)
-    MGV_CHECK_ARG(heavy_n >= 0 && (heavy_n == 0 || (heavy_nodes && heavy_ws)));
+    a.prefetch = (table_own_idx && !nbr_tagged) ? 0 : 1;      // the L2 row prefetch (measured) assumes N rows behind h_in: off when own rows go through an index into a shorter h_in
     mgv::launch_heavy_sums<64>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, static_cast<hipStream_t>(stream));
     return mgv::launch_bwd2_x3(a, workspace, workspace_floats, static_cast<hipStream_t>(stream));
 }
-
-#if MGV_ABL != 0
-// marker of a timing-ablation build (wrong results by design): deepgate/_hip.py refuses a library that exports it
-extern "C" int mgv_diag_ablation_build(void) { return MGV_ABL; }
-#endif

@@ -6,13 +6,14 @@
 // Weights arrive pre-split by the host in one bf16 pack of eight [3H*H] blocks:
 //   0 Wc_hi  1 Wc_lo  2 Whh_hi  3 Whh_lo   ([3H][H], k contiguous: forward B operands)
 //   4 WcT_hi 5 WcT_lo 6 WhhT_hi 7 WhhT_lo  ([H][3H], k contiguous: dgrad B operands)
+//
+// Timing ablations of the forward kernel (builds without its MFMAs, GRU epilogue, row gathers or output stores, wrong by design) priced its
+// parts in round 3: row gathers expose 0.37 ms of 1.26 ms (NOTEBOOK r3 §4.3); they are no longer in this source.
 #include "struct_stage_x3_common.h"
 
-#ifndef MGV_FWD_D
-#define MGV_FWD_D 3            // neighbour slots per row and gather round of the H = 64 forward
-#endif
-
 namespace mgv {
+
+constexpr int kFwdD = 3;        // neighbour slots per row and gather round of the H = 64 forward
 
 // gate pre-activations of one tile from the split planes; weights streamed from L2
 template <int H>
@@ -69,14 +70,6 @@ __device__ __forceinline__ void stage_gemm_x3(const __bf16* wpack, const __bf16*
 // loaded once per kernel and stay in registers: the dense phase touches LDS only.
 constexpr int kThreadsF = 256;
 
-#ifndef MGV_ABLF
-#define MGV_ABLF 0           // timing ablations of diagnostic builds of the FORWARD kernel (results are wrong): 1 no MFMA, 2 light epilogue, 4 no row gathers, 8 no output stores
-#endif
-#if MGV_ABLF & 1
-#define FWD_MMA(c, ah, al, bh, bl) asm volatile("" :: "v"(ah), "v"(al), "v"(bh), "v"(bl))
-#else
-#define FWD_MMA(c, ah, al, bh, bl) mma_x3(c, ah, al, bh, bl)
-#endif
 template <int H>
 __global__ __launch_bounds__(kThreadsF, 2) void k_struct_stage_fwd_x3(StageX3Args a) {
     using S = WaveSplit<H>;                 // 4 waves: column tiles first, then row tiles (mgv_common.h)
@@ -139,11 +132,7 @@ __global__ __launch_bounds__(kThreadsF, 2) void k_struct_stage_fwd_x3(StageX3Arg
             float4 acc[RPG], own[RPG], dy[RPG];
             float deg[RPG];
             int cls[RPG];
-#if MGV_ABLF & 4
-            for (int rr = 0; rr < RPG; ++rr) { acc[rr] = make_float4(0.1f * lr, 0.2f, 0.3f, 0.4f); own[rr] = acc[rr]; deg[rr] = 2.f; cls[rr] = 1; }
-#else
-            tile_rows<H, RPG, false, (H == 64 ? MGV_FWD_D : 4)>(a, base, grp, S::GROUPS, lr, idx_lds(idx_base, b).ptr, idx_lds(idx_base, b).idx, *idx_lds(idx_base, b).dmax(), acc, own, dy, deg, cls);
-#endif
+            tile_rows<H, RPG, false, (H == 64 ? kFwdD : 4)>(a, base, grp, S::GROUPS, lr, idx_lds(idx_base, b).ptr, idx_lds(idx_base, b).idx, *idx_lds(idx_base, b).dmax(), acc, own, dy, deg, cls);
 #pragma unroll
             for (int rr = 0; rr < RPG; ++rr) {
                 const int row = grp + rr * S::GROUPS;
@@ -171,9 +160,9 @@ __global__ __launch_bounds__(kThreadsF, 2) void k_struct_stage_fwd_x3(StageX3Arg
                 const int off = ((wr * S::RTW + i) * 16 + r) * LDP + 32 * ks + 8 * q;
                 const bf16x8 ah = ldfrag(agg_hi + off), al = ldfrag(agg_lo + off);
                 const bf16x8 hh = ldfrag(hin_hi + off), hl = ldfrag(hin_lo + off);
-                FWD_MMA(ar[i], ah, al, wch[ks][0], wcl[ks][0]); FWD_MMA(ar[i], hh, hl, wuh[ks][0], wul[ks][0]);
-                FWD_MMA(az[i], ah, al, wch[ks][1], wcl[ks][1]); FWD_MMA(az[i], hh, hl, wuh[ks][1], wul[ks][1]);
-                FWD_MMA(ani[i], ah, al, wch[ks][2], wcl[ks][2]); FWD_MMA(anh[i], hh, hl, wuh[ks][2], wul[ks][2]);
+                mma_x3(ar[i], ah, al, wch[ks][0], wcl[ks][0]); mma_x3(ar[i], hh, hl, wuh[ks][0], wul[ks][0]);
+                mma_x3(az[i], ah, al, wch[ks][1], wcl[ks][1]); mma_x3(az[i], hh, hl, wuh[ks][1], wul[ks][1]);
+                mma_x3(ani[i], ah, al, wch[ks][2], wcl[ks][2]); mma_x3(anh[i], hh, hl, wuh[ks][2], wul[ks][2]);
             }
         STAMP(2);
         __syncthreads();        // s_pre overlays the agg planes; pointers of tile t+2 are in buffer b
@@ -198,14 +187,10 @@ __global__ __launch_bounds__(kThreadsF, 2) void k_struct_stage_fwd_x3(StageX3Arg
                 const f32x4 xr = f32x4{x0[0], x1[0], x2[0], x3[0]}, xz = f32x4{x0[H], x1[H], x2[H], x3[H]}, xn = f32x4{x0[2 * H], x1[2 * H], x2[2 * H], x3[2 * H]};
                 const float* hrow = s_hin + row0 * S::LD + col;
                 const f32x4 hp = f32x4{hrow[0], hrow[S::LD], hrow[2 * S::LD], hrow[3 * S::LD]};
-#if MGV_ABLF & 2
-                const f32x4 pre = ar[i] + az[i] + ani[i] + anh[i] + hp + xr + xz + xn + deg * (bcr + bcz + bcn + bhn);
-#else
                 const f32x4 rr = sigmoid4(ar[i] + (deg * bcr + xr));
                 const f32x4 zz = sigmoid4(az[i] + (deg * bcz + xz));
                 const f32x4 nn = tanh4(ani[i] + (deg * bcn + xn) + rr * (anh[i] + bhn));
                 const f32x4 pre = nn + zz * (hp - nn);
-#endif
                 float* prow = s_pre + row0 * S::LD + col;
                 prow[0] = pre[0]; prow[S::LD] = pre[1]; prow[2 * S::LD] = pre[2]; prow[3 * S::LD] = pre[3];
             }
@@ -229,11 +214,7 @@ __global__ __launch_bounds__(kThreadsF, 2) void k_struct_stage_fwd_x3(StageX3Arg
                 const float4 g = ld4(sv.lnw + 4 * lr), bb = ld4(sv.lnb + 4 * lr);
                 v = make_float4(v.x * rstd * g.x + bb.x, v.y * rstd * g.y + bb.y, v.z * rstd * g.z + bb.z, v.w * rstd * g.w + bb.w);
             }
-#if MGV_ABLF & 8
-            if (node < a.N && v.x == 1.2345e-30f) st4(a.h_out + node * H + 4 * lr, v);
-#else
             if (node < a.N) st4(a.h_out + node * H + 4 * lr, v);
-#endif
         }
         idx_commit<kThreadsF>(idx_lds(idx_base, b).idx, ri);               // ids of tile t+2 replace this tile's
         STAMP(7);
@@ -339,18 +320,12 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
     const bool need_dgrad = a.g_direct_out != nullptr;
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
 
-    // weight-gradient accumulators, persistent over the workgroup's tiles.  WBLK (H = 64): gWc[g] holds the wave's 2x2
-    // block of ITS matrix (gWhh unused); otherwise TPW tiles of each matrix per wave.
-    constexpr bool WBLK = (H == 64 && kNW == 8 && kTPR == 2);
-    constexpr int GT = WBLK ? 4 : W::TPW;
-    f32x4 gWc[3][GT], gWhh[3][WBLK ? 1 : W::TPW];
+    // weight-gradient accumulators, persistent over the workgroup's tiles: TPW tiles of each matrix per wave
+    f32x4 gWc[3][W::TPW], gWhh[3][W::TPW];
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
+    for (int g = 0; g < 3; ++g)
 #pragma unroll
-        for (int t = 0; t < GT; ++t) gWc[g][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < (WBLK ? 1 : W::TPW); ++t) gWhh[g][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+        for (int t = 0; t < W::TPW; ++t) { gWc[g][t] = f32x4{0.f, 0.f, 0.f, 0.f}; gWhh[g][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     // bias-type gradients (dbc, dxtab, dbhh) as one more wgrad tile per pass: dG^T x [deg, onehot(cls), 1]
     f32x4 gX[4];
 #pragma unroll
@@ -369,12 +344,10 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
     rp = ptr_prefetch(a, seq.at(1), ntiles);
     __syncthreads();
     int b = 0;
-    STAMP_DECL
     constexpr int RPG = kTileRows / S::GROUPS;
     for (int it = 0; seq.at(it) < ntiles; ++it, b ^= 1) {
         const int64_t tile = seq.at(it);
         const int64_t base = tile * kTileRows;
-        STAMP_BEGIN;
         // ---- A. row phase (independent loads); operand planes row-major (GEMM A operands) and
         //        (they serve the wgrad too, read transposed)
         {
@@ -401,16 +374,13 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
             }
         }
         if (tid <= kTileRows) idx_lds(idx_base, b ^ 1).ptr[tid] = rp;
-        STAMP(0);
         __syncthreads();
-        STAMP(1);
         // ---- B. recompute gates; keep the own-row values (hi+lo) for the GRU backward
         f32x4 ar[S::RTW][S::HCW], az[S::RTW][S::HCW], ani[S::RTW][S::HCW], anh[S::RTW][S::HCW];
         stage_gemm_x3<H>(a.wpack, wc_hi, whh_hi, agg_hi, agg_lo, hin_hi, hin_lo, ar, az, ani, anh);
         idx_prefetch<kThreadsX3>(a, idx_lds(idx_base, b ^ 1).ptr, ri);          // after the weight fragments (vmcnt is in order); committed at the tile's end
         rp = ptr_prefetch(a, seq.at(it + 2), ntiles);
         tile_dmax(idx_lds(idx_base, b ^ 1).ptr, idx_lds(idx_base, b ^ 1).dmax());
-        STAMP(2);
 #pragma unroll
         for (int i = 0; i < S::RTW; ++i)
 #pragma unroll
@@ -432,9 +402,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
                     ar[i][j][e] = rr; az[i][j][e] = zz; ani[i][j][e] = nn; anh[i][j][e] = ghn;
                 }
             }
-        STAMP(3);
         __syncthreads();
-        STAMP(4);
         // ---- C. LayerNorm row statistics
         if (has_ln) {
             for (int row = grp; row < kTileRows; row += S::GROUPS) {
@@ -452,7 +420,6 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
             }
             __syncthreads();
         }
-        STAMP(5);
         // ---- D. LayerNorm + GRU backward in accumulator layout
         f32x4 dhd[S::RTW][S::HCW];
 #pragma unroll
@@ -487,7 +454,6 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
             }
             if (has_ln) { colsum_lds_x3(s_lw, s_dlnw + col); colsum_lds_x3(s_lb, s_dlnb + col); }
         }
-        STAMP(6);
         // ---- E. four gate-gradient tiles through region C (which held pre/dy until here)
         f32x4 dag[S::RTW][S::HCW];
 #pragma unroll
@@ -498,7 +464,6 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
 #pragma unroll
         for (int rnd = 0; rnd < 4 / kTPR; ++rnd) {
             __syncthreads();          // readers of region C: phase D, or the previous round
-            STAMP(14);
 #pragma unroll
             for (int t2 = 0; t2 < kTPR; ++t2) {
                 const int p = kTPR * rnd + t2;
@@ -520,9 +485,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
                         }
                     }
             }
-            STAMP(10);
             __syncthreads();
-            STAMP(11);
 #pragma unroll
             for (int t2 = 0; t2 < kTPR; ++t2) {
                 const int p = kTPR * rnd + t2;
@@ -557,23 +520,14 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
                     }
                 }
             }
-            STAMP(12);
 #pragma unroll
             for (int t2 = 0; t2 < kTPR; ++t2) {
                 const int p = kTPR * rnd + t2;
                 const int g = p < 2 ? p : 2;
                 const __bf16* ph = d_hi + t2 * 2 * kTileRows * LDP;
                 const __bf16* pl = ph + kTileRows * LDP;
-                if constexpr (WBLK) {
-                    // round 0 (r, z gates): both matrices take the tile; round 1: Wc takes the n-input tile (t2 = 0), Whh the
-                    // n-hidden tile (t2 = 1), each from its own wave group in ONE pass
-                    const bool whh = w >= 4;
-                    if (rnd == 0) wgrad_blk_x3<H>(gWc[g], ph, pl, whh ? hin_hi : agg_hi, whh ? hin_lo : agg_lo);
-                    else if (t2 == (whh ? 1 : 0)) wgrad_blk_x3<H>(gWc[2], ph, pl, whh ? hin_hi : agg_hi, whh ? hin_lo : agg_lo);
-                } else {
-                    if (p != 3) wgrad_x3<H>(gWc[g], ph, pl, agg_hi, agg_lo);
-                    if (p != 2) wgrad_x3<H>(gWhh[g], ph, pl, hin_hi, hin_lo);
-                }
+                if (p != 3) wgrad_x3<H>(gWc[g], ph, pl, agg_hi, agg_lo);
+                if (p != 2) wgrad_x3<H>(gWhh[g], ph, pl, hin_hi, hin_lo);
                 if (w < H / 16) {          // wave-uniform: gate-column tile w of the bias-type gradients
 #pragma unroll
                     for (int ks = 0; ks < kTileRows / 32; ++ks)
@@ -581,12 +535,9 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
                                ldfrag_tr2(xe_hi, XLD, 32 * ks, 0), ldfrag_tr2(xe_lo, XLD, 32 * ks, 0));
                 }
             }
-            STAMP(13);
         }
-        STAMP(7);
         // ---- F. outputs through LDS (region C as two fp32 tiles again)
         __syncthreads();
-        STAMP(8);
         if (need_dgrad) {
 #pragma unroll
             for (int i = 0; i < S::RTW; ++i)
@@ -611,17 +562,11 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
         }
         idx_commit<kThreadsX3>(idx_lds(idx_base, b ^ 1).idx, ri);
         __syncthreads();
-        STAMP(9);
     }
-    STAMP_FLUSH(a);
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-        if constexpr (WBLK) {
-            wgrad_blk_flush_x3<H>(gWc[g], (w >= 4 ? a.dWhh : a.dWc) + (int64_t)g * H * H);
-        } else {
-            wgrad_flush_x3<H>(gWc[g], a.dWc + (int64_t)g * H * H);
-            wgrad_flush_x3<H>(gWhh[g], a.dWhh + (int64_t)g * H * H);
-        }
+        wgrad_flush_x3<H>(gWc[g], a.dWc + (int64_t)g * H * H);
+        wgrad_flush_x3<H>(gWhh[g], a.dWhh + (int64_t)g * H * H);
     }
     if (w < H / 16) {
         // gX[p][e] = sum_rows dG_p[row][i] * Xe[row][j] with i = 16w + 4q + e, j = r:
@@ -676,29 +621,19 @@ extern "C" int mgv_diag_set_stamps(void* p) { g_stamps = static_cast<unsigned lo
 #define MGV_SET_STAMPS(a)
 #endif
 
-static int xcd_tiles() {
-    return 1;            // XCD-contiguous tile order (measured against round-robin in round 2; no switch left)
-}
-
 extern "C" int mgv_struct_stage_fwd_x3(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                                        const uint8_t* xcls, const float* xtab, int C, const void* wpack_bf16, const float* bc,
                                        const float* bhh, const float* ln_w, const float* ln_b, float ln_eps, float* h_out,
                                        int heavy_n, const int32_t* heavy_nodes, float* heavy_ws, const int32_t* table_own_idx,
                                        int nbr_tagged, float* ln_stats_out, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && wpack_bf16 && bc && bhh && h_out && (table_own_idx == nullptr || !nbr_tagged || N < (1 << 24)));
-    MGV_CHECK_ARG(heavy_n >= 0 && (heavy_n == 0 || (heavy_nodes && heavy_ws)));
-    MGV_CHECK_ARG(C >= 1 && C <= mgv::kMaxClsX3);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
+    mgv::StageX3Args a{};
+    if (int rc = mgv::stage_x3_args(a, N, h_in, nbr_ptr, nbr_idx, xcls, xtab, C, wpack_bf16, bc, bhh, ln_w, ln_b, ln_eps, table_own_idx, nbr_tagged, ln_stats_out)) return rc;
+    if (int rc = mgv::stage_x3_lists(N, heavy_n, heavy_nodes, heavy_ws, table_own_idx, nbr_tagged)) return rc;
+    MGV_CHECK_ARG(h_out != nullptr);
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
-    mgv::StageX3Args a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
-    a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bc = bc; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps; a.h_out = h_out;
-    a.gmask = -1;
-    if (table_own_idx) { a.own_idx = table_own_idx; if (nbr_tagged) { a.hshift = 24; a.gmask = 0xffffff; } }
-    a.ln_stats = ln_w ? ln_stats_out : nullptr;
+    a.h_out = h_out;
     MGV_SET_STAMPS(a);
-    a.xcd = xcd_tiles();
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (H) {
         case 32: mgv::launch_heavy_sums<32>(a, heavy_n, heavy_nodes, heavy_ws, false, st); return mgv::launch_fwd_x3<32>(a, st);
@@ -707,6 +642,7 @@ extern "C" int mgv_struct_stage_fwd_x3(int H, int64_t N, const float* h_in, cons
     }
 }
 
+// H = 32 only: at H = 64 the backward is mgv_struct_stage_bwd2_x3 (struct_stage_bwd2_x3.hip)
 extern "C" int mgv_struct_stage_bwd_x3(int H, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                                        const uint8_t* xcls, const float* xtab, int C, const void* wpack_bf16, const float* bc,
                                        const float* bhh, const float* ln_w, const float* ln_b, float ln_eps,
@@ -714,33 +650,14 @@ extern "C" int mgv_struct_stage_bwd_x3(int H, int64_t N, const float* h_in, cons
                                        float* dWc, float* dbc, float* dWhh, float* dbhh, float* dxtab, float* dln_w,
                                        float* dln_b, int heavy_n, const int32_t* heavy_nodes, float* heavy_ws,
                                        const int32_t* table_own_idx, int nbr_tagged, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && wpack_bf16 && bc && bhh && gy_direct && (table_own_idx == nullptr || !nbr_tagged || N < (1 << 24)));
-    MGV_CHECK_ARG(heavy_n >= 0 && (heavy_n == 0 || (heavy_nodes && heavy_ws)));
-    MGV_CHECK_ARG(dWc && dbc && dWhh && dbhh && dxtab);
-    MGV_CHECK_ARG(C >= 1 && C <= mgv::kMaxClsX3);
-    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
-    MGV_CHECK_ARG(ln_w == nullptr || (dln_w && dln_b));
-    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
+    mgv::StageX3Args a{};
+    if (int rc = mgv::stage_x3_args(a, N, h_in, nbr_ptr, nbr_idx, xcls, xtab, C, wpack_bf16, bc, bhh, ln_w, ln_b, ln_eps, table_own_idx, nbr_tagged, nullptr)) return rc;
+    if (int rc = mgv::stage_x3_lists(N, heavy_n, heavy_nodes, heavy_ws, table_own_idx, nbr_tagged)) return rc;
+    if (int rc = mgv::stage_x3_bwd_args(a, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, dxtab, dln_w, dln_b)) return rc;
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
-    mgv::StageX3Args a{};
-    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
-    a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bc = bc; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
-    a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out; a.g_agg_out = g_agg_out;
-    a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dxtab = dxtab; a.dlnw = dln_w; a.dlnb = dln_b;
-    a.gmask = -1;
-    if (table_own_idx) { a.own_idx = table_own_idx; if (nbr_tagged) { a.hshift = 24; a.gmask = 0xffffff; } }
-    MGV_SET_STAMPS(a);
-    a.xcd = xcd_tiles();
+    if (H != 32) return MGV_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 32: mgv::launch_heavy_sums<32>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, st); return mgv::launch_bwd_x3<32>(a, st);
-        case 64: mgv::launch_heavy_sums<64>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, st); return mgv::launch_bwd_x3<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    mgv::launch_heavy_sums<32>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, st);
+    return mgv::launch_bwd_x3<32>(a, st);
 }
-
-#if MGV_ABLF != 0
-// marker of a timing-ablation build (wrong results by design): deepgate/_hip.py refuses a library that exports it
-extern "C" int mgv_diag_ablation_build_fwd(void) { return MGV_ABLF; }
-#endif

@@ -9,7 +9,7 @@ namespace mgv {
 
 struct StageX3Args {
     unsigned long long* stamps;   // diagnostic build only (MGV_STAMPS): [8 waves][16 phases] cycle sums
-    int xcd;                      // 1: XCD-contiguous tile order (default), 0: round-robin (MGV_XCD_TILES=0, A/B measurements)
+    int xcd;                      // 1: XCD-contiguous tile order (what every entry passes: measured against round-robin in round 2), 0: round-robin
     int prefetch;                 // bwd2: 1: L2 prefetch of the next tile's rows (default), 0: off (MGV_ROW_PREFETCH=0, A/B measurements)
     int64_t N;
     const float* h_in;
@@ -434,5 +434,39 @@ __device__ __forceinline__ void wgrad_blk_flush_x3(const f32x4 (&acc)[4], float*
             for (int e = 0; e < 4; ++e) atomicAdd(dW + (int64_t)((it0 + i) * 16 + q * 4 + e) * H + (jt0 + j) * 16 + r, acc[i * 2 + j][e]);
 }
 
+// ---- host side: the one place that validates and fills the arguments the three bf16x3 entries share (struct_stage_x3.hip: forward and
+// first backward; struct_stage_bwd2_x3.hip).  An entry runs: these checks (MGV_EINVAL), then N == 0 (MGV_OK), then nbr_idx, then the width.
+inline int stage_x3_args(StageX3Args& a, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx, const uint8_t* xcls,
+                         const float* xtab, int C, const void* wpack_bf16, const float* bc, const float* bhh, const float* ln_w,
+                         const float* ln_b, float ln_eps, const int32_t* table_own_idx, int nbr_tagged, float* ln_stats) {
+    MGV_CHECK_ARG(N >= 0 && h_in && nbr_ptr && xcls && xtab && wpack_bf16 && bc && bhh);
+    MGV_CHECK_ARG(C >= 1 && C <= kMaxClsX3);
+    MGV_CHECK_ARG((ln_w == nullptr) == (ln_b == nullptr));
+    a.N = N; a.h_in = h_in; a.ptr = nbr_ptr; a.idx = nbr_idx; a.xcls = xcls; a.xtab = xtab; a.C = C;
+    a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bc = bc; a.bhh = bhh; a.lnw = ln_w; a.lnb = ln_b; a.eps = ln_eps;
+    a.gmask = -1;
+    if (table_own_idx) { a.own_idx = table_own_idx; if (nbr_tagged) { a.hshift = 24; a.gmask = 0xffffff; } }
+    a.ln_stats = ln_w ? ln_stats : nullptr;
+    a.xcd = 1;
+    return MGV_OK;
+}
+
+// the backward's own checks and fields (both backward entries)
+inline int stage_x3_bwd_args(StageX3Args& a, const float* gy_direct, const float* gy_agg, float* g_direct_out, float* g_agg_out, float* dWc,
+                             float* dbc, float* dWhh, float* dbhh, float* dxtab, float* dln_w, float* dln_b) {
+    MGV_CHECK_ARG(gy_direct && dWc && dbc && dWhh && dbhh && dxtab);
+    MGV_CHECK_ARG(a.lnw == nullptr || (dln_w && dln_b));
+    MGV_CHECK_ARG((g_direct_out == nullptr) == (g_agg_out == nullptr));
+    a.gy_direct = gy_direct; a.gy_agg = gy_agg; a.g_direct_out = g_direct_out; a.g_agg_out = g_agg_out;
+    a.dWc = dWc; a.dbc = dbc; a.dWhh = dWhh; a.dbhh = dbhh; a.dxtab = dxtab; a.dlnw = dln_w; a.dlnb = dln_b;
+    return MGV_OK;
+}
+
+// the heavy-row list, and the tagged form of table mode: a neighbour entry keeps 24 bits for the node
+inline int stage_x3_lists(int64_t N, int heavy_n, const int32_t* heavy_nodes, const float* heavy_ws, const int32_t* table_own_idx, int nbr_tagged) {
+    MGV_CHECK_ARG(table_own_idx == nullptr || !nbr_tagged || N < (1 << 24));
+    MGV_CHECK_ARG(heavy_n >= 0 && (heavy_n == 0 || (heavy_nodes && heavy_ws)));
+    return MGV_OK;
+}
 
 }  // namespace mgv

@@ -128,8 +128,8 @@ def struct_stage_fwd(h_in, nbr_ptr, nbr_idx, xcls, xtab, Wc, bc, Whh, bhh, ln_w,
 
 
 # The bf16x3 half-round backward at H = 64 is struct_stage_bwd2_x3.hip (register-resident recompute weights, transposed products,
-# slab-reduced deterministic parameter gradients); the first kernel (struct_stage_x3.hip) serves H = 32 only (tools/bench_stage.py
-# still times both through the C ABI).
+# slab-reduced deterministic parameter gradients); the first kernel (struct_stage_x3.hip, mgv_struct_stage_bwd_x3) serves H = 32 only
+# and refuses H = 64 with MGV_EUNSUPPORTED.
 QUOTIENT = os.environ.get('MGV_QUOTIENT', '1') != '0'         # early half rounds on one row per colour (GraphPlan.quotient)
 _WS = {}
 

@@ -3,8 +3,10 @@ float64 restatement of tests/struct_stage_ref.py (pinned on the CPU by tests/tes
 properties of the case builders used here and shows that the defects these tests are there to catch are far outside their bound):
 
   f32    struct_stage.hip, exact fp32, H = 16 / 32 / 64                    rows   its general-feature form (xrow per node, d_xrow)
-  x3     struct_stage_x3.hip: forward and the first backward, H = 32 / 64 (the H = 64 backward is reachable through the C ABI only)
-  bwd2   struct_stage_bwd2_x3.hip, the H = 64 backward (with the x3 forward)
+  x3     struct_stage_x3.hip: forward and the first backward, H = 32 (the first backward serves that width only: at H = 64 it
+         returns MGV_EUNSUPPORTED, test_refusals_are_return_codes)
+  bwd2   struct_stage_bwd2_x3.hip, the H = 64 backward, with the H = 64 forward of struct_stage_x3.hip: every case here checks that
+         forward's h_out and {mean, rstd} as well
 
 Every call here goes through the C ABI with 64 guard rows behind each output (NaN before the call, bit-identical after it),
 NaN-filled workspaces and accumulators pre-filled with random values a0; test_through_ops repeats a selection through
@@ -182,7 +184,7 @@ def _check(impl, H, size, lists='designed', mode='plain', C=6, ln=True, agg=True
     _compare(tag, got, a0, r64, _tau(MM[impl], *key))
 
 
-IMPLS = [('f32', 16), ('f32', 32), ('f32', 64), ('rows', 16), ('rows', 32), ('rows', 64), ('x3', 32), ('x3', 64), ('bwd2', 64)]
+IMPLS = [('f32', 16), ('f32', 32), ('f32', 64), ('rows', 16), ('rows', 32), ('rows', 64), ('x3', 32), ('bwd2', 64)]
 ALL_SIZES = tuple(SR.SIZES)
 SOME_SIZES = ('n1', 'n65', 't9', 't17', 't257')
 
@@ -193,7 +195,7 @@ def test_every_size_against_float64(impl, H):
     on the chunked path, the heavy ladder 64 .. 129 and a 600-entry hub, heavy rows as node 0, node N - 1 and in the partial tile)
     at every named size for the H = 64 kernels and the H = 32 bf16x3 ones, a selection for the other widths of the fp32 kernels
     (one template, the tile loop does not depend on H)."""
-    sizes = ALL_SIZES if (impl, H) in (('f32', 64), ('x3', 32), ('x3', 64), ('bwd2', 64)) else SOME_SIZES
+    sizes = ALL_SIZES if (impl, H) in (('f32', 64), ('x3', 32), ('bwd2', 64)) else SOME_SIZES
     for size in sizes:
         _check(impl, H, size)
 
@@ -224,11 +226,11 @@ def test_list_layouts_and_switches(impl, H):
             _check(impl, H, size, stats=None)
 
 
-@pytest.mark.parametrize('impl,H', [('f32', 16), ('f32', 32), ('f32', 64), ('rows', 32), ('x3', 32), ('x3', 64), ('bwd2', 64)])
+@pytest.mark.parametrize('impl,H', [('f32', 16), ('f32', 32), ('f32', 64), ('rows', 32), ('x3', 32), ('bwd2', 64)])
 def test_index_forms(impl, H):
     """h_in longer than the stage (every implementation); for the bf16x3 kernels the tagged table form (entries node | row << 24, rows
-    >= 128 negative as int32, own rows through the index; the first backward through the ABI at H = 64 only, as the product never
-    calls it tagged at H = 32) and the untagged own-index form of the quotient stages with h_in shorter and longer than N."""
+    >= 128 negative as int32, own rows through the index; at H = 64 with bwd2, at H = 32 the forward alone, as the product never
+    calls the first backward tagged) and the untagged own-index form of the quotient stages with h_in shorter and longer than N."""
     for size in ('n1', 'n65', 't9', 't17') + (('t257',) if H == 64 else ()):
         _check(impl, H, size, mode='n_rows')
         if impl in ('x3', 'bwd2'):
@@ -325,7 +327,8 @@ def test_through_ops(precision, H):
 
 def test_refusals_are_return_codes():
     """Every refusal comes back as MGV_EINVAL / MGV_EUNSUPPORTED from the argument check, with the outputs untouched; no call here
-    could launch anything (a refused call returns before its first launch)."""
+    could launch anything (a refused call returns before its first launch).  bwd_x3() is the first backward at H = 64: its rows with a
+    bad argument are refused by the argument check, and with every argument valid the width is (MGV_EUNSUPPORTED: H = 32 only)."""
     dev = _dev()
     from deepgate import _hip, ops
     from deepgate._hip import HipLibraryError
@@ -365,7 +368,7 @@ def test_refusals_are_return_codes():
     refused = [
         ('MGV_EUNSUPPORTED', lambda: fwd_x3(H=16)), ('MGV_EUNSUPPORTED', lambda: bwd_x3(H=16)), ('MGV_EUNSUPPORTED', lambda: bwd_x3(B2, H=32)),
         ('MGV_EUNSUPPORTED', lambda: bwd_x3(B2, H=16)), ('MGV_EUNSUPPORTED', lambda: f32(False, H=48)), ('MGV_EUNSUPPORTED', lambda: f32(True, H=128)),
-        ('MGV_EINVAL', lambda: bwd_x3(B2, nws=nws - 1)),
+        ('MGV_EINVAL', lambda: bwd_x3(B2, nws=nws - 1)), ('MGV_EUNSUPPORTED', lambda: bwd_x3()),
     ]
     for C in (0, 9):
         refused += [('MGV_EINVAL', lambda C=C: fwd_x3(C=C)), ('MGV_EINVAL', lambda C=C: bwd_x3(C=C)), ('MGV_EINVAL', lambda C=C: bwd_x3(B2, C=C)),

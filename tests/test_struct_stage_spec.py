@@ -283,3 +283,103 @@ def test_x3_emulation_is_split_precision(H):
         for k in ('h_out', 'g_direct', 'g_agg', 'dWc', 'dWhh'):
             assert r3[k] > r32[k], k
         assert max(r3.values()) < 2.0 ** -14
+
+
+# ------------------------------------------------------------------------------------------------ host-side refusals
+_STAGE_ENTRIES = {'fwd': 64, 'bwd': 64, 'rows_fwd': 64, 'rows_bwd': 64, 'fwd_x3': 64, 'bwd_x3': 32, 'bwd2_x3': 64}      # mgv_struct_stage_<entry>: H of its valid call
+OK, E, U, D = 0, -1, -2, 'dummy'        # MGV_OK, MGV_EINVAL, MGV_EUNSUPPORTED; D: a non-NULL pointer where the valid call has NULL
+# (overrides of the valid call, return code).  The valid call: H as above, N = 65, C = 6, every pointer non-NULL but heavy_nodes / heavy_ws /
+# table_own_idx (heavy_n = 0, nbr_tagged = 0), workspace_floats = mgv_struct_stage_bwd2_ws_floats(64, 65) (written as an offset from it).
+# Every code is what the library of the commit before the first backward lost H = 64 returned for the row (the table was run against
+# that build through MGV_LIB); the one row that differs by design is the last of bwd_x3.  The rows behind "N=0, nbr_idx=None" pin the
+# order of each entry: argument check, N == 0, nbr_idx, width (bwd2: width in front of N == 0, heavy and tagged lists behind nbr_idx).
+_STAGE_REFUSALS = {
+    'fwd': [
+        (dict(H=48), U), (dict(C=0), E), (dict(C=9), E), (dict(C=9, H=48), E), (dict(ln_w=None), E), (dict(ln_b=None), E), (dict(h_in=None), E),
+        (dict(nbr_ptr=None), E), (dict(xcls=None), E), (dict(xtab=None), E), (dict(Wc=None), E), (dict(bc=None), E), (dict(Whh=None), E),
+        (dict(bhh=None), E), (dict(h_out=None), E), (dict(N=-1), E), (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK), (dict(H=48, N=0), OK),
+        (dict(H=48, nbr_idx=None), E)
+    ],
+    'bwd': [
+        (dict(H=128), U), (dict(C=0), E), (dict(C=9), E), (dict(C=9, H=128), E), (dict(ln_w=None), E), (dict(ln_b=None), E),
+        (dict(g_direct_out=None), E), (dict(g_agg_out=None), E), (dict(h_in=None), E), (dict(nbr_ptr=None), E), (dict(xcls=None), E),
+        (dict(xtab=None), E), (dict(Wc=None), E), (dict(WcT=None), E), (dict(bc=None), E), (dict(Whh=None), E), (dict(WhhT=None), E),
+        (dict(bhh=None), E), (dict(gy_direct=None), E), (dict(dWc=None), E), (dict(dbc=None), E), (dict(dWhh=None), E), (dict(dbhh=None), E),
+        (dict(dxtab=None), E), (dict(dln_w=None), E), (dict(dln_b=None), E), (dict(N=-1), E), (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK)
+    ],
+    'rows_fwd': [
+        (dict(H=48), U), (dict(ln_w=None), E), (dict(ln_b=None), E), (dict(h_in=None), E), (dict(nbr_ptr=None), E), (dict(xrow=None), E),
+        (dict(Wc=None), E), (dict(bc=None), E), (dict(Whh=None), E), (dict(bhh=None), E), (dict(h_out=None), E), (dict(N=-1), E),
+        (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK)
+    ],
+    'rows_bwd': [
+        (dict(H=128), U), (dict(ln_w=None), E), (dict(ln_b=None), E), (dict(g_direct_out=None), E), (dict(g_agg_out=None), E), (dict(h_in=None), E),
+        (dict(nbr_ptr=None), E), (dict(xrow=None), E), (dict(Wc=None), E), (dict(WcT=None), E), (dict(bc=None), E), (dict(Whh=None), E),
+        (dict(WhhT=None), E), (dict(bhh=None), E), (dict(gy_direct=None), E), (dict(dWc=None), E), (dict(dbc=None), E), (dict(dWhh=None), E),
+        (dict(dbhh=None), E), (dict(d_xrow=None), E), (dict(dln_w=None), E), (dict(dln_b=None), E), (dict(N=-1), E), (dict(nbr_idx=None), E),
+        (dict(N=0, nbr_idx=None), OK), (dict(H=128, N=0), OK), (dict(H=128, nbr_idx=None), E)
+    ],
+    'fwd_x3': [
+        (dict(H=16), U), (dict(C=0), E), (dict(C=9), E), (dict(C=9, H=16), E), (dict(ln_w=None), E), (dict(ln_b=None), E), (dict(h_in=None), E),
+        (dict(nbr_ptr=None), E), (dict(xcls=None), E), (dict(xtab=None), E), (dict(wpack_bf16=None), E), (dict(bc=None), E), (dict(bhh=None), E),
+        (dict(h_out=None), E), (dict(N=-1), E), (dict(heavy_n=-1), E), (dict(heavy_n=1, heavy_ws=D), E), (dict(heavy_n=1, heavy_nodes=D), E),
+        (dict(N=1 << 24, table_own_idx=D, nbr_tagged=1), E), (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK), (dict(H=16, N=0), OK),
+        (dict(N=0, heavy_n=-1), E), (dict(H=16, nbr_idx=None), E)
+    ],
+    'bwd_x3': [
+        (dict(H=16), U), (dict(C=0), E), (dict(C=9), E), (dict(C=9, H=16), E), (dict(ln_w=None), E), (dict(ln_b=None), E),
+        (dict(g_direct_out=None), E), (dict(g_agg_out=None), E), (dict(h_in=None), E), (dict(nbr_ptr=None), E), (dict(xcls=None), E),
+        (dict(xtab=None), E), (dict(wpack_bf16=None), E), (dict(bc=None), E), (dict(bhh=None), E), (dict(gy_direct=None), E), (dict(dWc=None), E),
+        (dict(dbc=None), E), (dict(dWhh=None), E), (dict(dbhh=None), E), (dict(dxtab=None), E), (dict(dln_w=None), E), (dict(dln_b=None), E),
+        (dict(N=-1), E), (dict(heavy_n=-1), E), (dict(heavy_n=1, heavy_ws=D), E), (dict(heavy_n=1, heavy_nodes=D), E),
+        (dict(N=1 << 24, table_own_idx=D, nbr_tagged=1), E), (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK), (dict(H=16, N=0), OK),
+        (dict(N=0, heavy_n=-1), E), (dict(H=16, nbr_idx=None), E)
+    ],
+    'bwd2_x3': [
+        (dict(H=16), U), (dict(H=32), U), (dict(C=0), E), (dict(C=9), E), (dict(C=9, H=16), E), (dict(ln_w=None), E), (dict(ln_b=None), E),
+        (dict(g_direct_out=None), E), (dict(g_agg_out=None), E), (dict(h_in=None), E), (dict(nbr_ptr=None), E), (dict(xcls=None), E),
+        (dict(xtab=None), E), (dict(wpack_bf16=None), E), (dict(bc=None), E), (dict(bhh=None), E), (dict(gy_direct=None), E), (dict(dWc=None), E),
+        (dict(dbc=None), E), (dict(dWhh=None), E), (dict(dbhh=None), E), (dict(dxtab=None), E), (dict(dln_w=None), E), (dict(dln_b=None), E),
+        (dict(N=-1), E), (dict(heavy_n=-1), E), (dict(heavy_n=1, heavy_ws=D), E), (dict(heavy_n=1, heavy_nodes=D), E),
+        (dict(N=1 << 24, table_own_idx=D, nbr_tagged=1), E), (dict(workspace_floats=-1), E), (dict(nbr_idx=None), E), (dict(N=0, nbr_idx=None), OK),
+        (dict(H=16, N=0), U), (dict(N=0, heavy_n=-1), OK), (dict(H=16, heavy_n=-1), U), (dict(H=16, nbr_idx=None), U)
+    ],
+}
+_STAGE_REFUSALS['bwd_x3'].append((dict(H=64), U))       # every argument valid: the first backward serves H = 32 only
+
+
+def test_stage_entries_refuse_on_the_host_before_any_launch():
+    """All seven struct-stage entries over rows that return before anything is launched or any pointer is read: an unserved width, C
+    outside 1 .. 8, half a LayerNorm, half an input gradient, every checked pointer NULL in turn, N = -1, a bad heavy list, the tagged
+    form at N = 2^24, bwd2 one float short of workspace, N > 0 without nbr_idx, N = 0 without it (accepted), and which of two faults
+    wins.  The pointers are dummies, so this runs only where no device could be reached through them; the same rows with real buffers
+    that must come back untouched: tests/test_hip_struct_stage_reference.py::test_refusals_are_return_codes."""
+    if torch.cuda.is_available():
+        pytest.skip('dummy pointers: host only')
+    import ctypes
+    import re
+    from deepgate import _hip
+    lib, sigs = _hip.load(), _hip.parse_header()
+    with open(_hip.HEADER_PATH) as f:
+        header = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    dummy = ctypes.c_void_p(64)
+    N = 65
+    nws = lib.mgv_struct_stage_bwd2_ws_floats(64, N)
+    assert nws == 2 * 28800
+    n = 0
+    for entry, H in _STAGE_ENTRIES.items():
+        name = 'mgv_struct_stage_' + entry
+        decl = re.search(r'\bint\s+%s\s*\(([^;{]*?)\)\s*;' % name, header, flags=re.S).group(1)
+        names = [re.search(r'(\w+)\s*$', a).group(1) for a in decl.split(',')]
+        assert len(names) == len(sigs[name])
+        valid = dict(H=H, N=N, C=6, ln_eps=1e-5, heavy_n=0, heavy_nodes=None, heavy_ws=None, table_own_idx=None, nbr_tagged=0,
+                     workspace_floats=0, stream=None)
+        for over, code in _STAGE_REFUSALS[entry]:
+            assert set(over) <= set(names), (entry, over)
+            args = dict({k: dummy for k in names}, **{k: v for k, v in valid.items() if k in names})
+            args.update({k: dummy if v is D else v for k, v in over.items()})
+            if 'workspace_floats' in args:
+                args['workspace_floats'] += nws
+            assert getattr(lib, name)(*[args[k] for k in names]) == code, (entry, over)
+            n += 1
+    assert n == 184

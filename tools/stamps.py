@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: where does a wave of the bf16x3 struct-stage kernels spend its cycles?
 Runs the stamped build (csrc/libmgvae_diag.so, `make -C multi-gate-vae_amd/csrc diag`) of the forward
-(and backward) kernel on a config-2-shaped batch and prints per-phase shares of the summed wave time.
+kernel on a config-2-shaped batch and prints per-phase shares of the summed wave time (the H = 64 backward:
+tools/stamps_bwd2.py).
 Never quote this build's run time (its fences forbid overlaps the real kernel has)."""
 import ctypes
 import os
@@ -16,8 +17,6 @@ from deepgate import ops, synthetic as syn  # noqa: E402
 from deepgate.graph_plan import GraphPlan  # noqa: E402
 
 FWD = ['row phase', 'barrier', 'prefetch+mfma', 'barrier', 'gru epilogue', 'idx commit', 'barrier', 'layernorm+store']
-BWD = ['A row phase', 'barrier', 'B recompute mfma', 'B gate epilogue+commit', 'barrier', 'C ln stats (+barrier)', 'D ln/gru backward',
-       '(unused)', 'F barrier', 'F output stage', 'E write dG tiles', 'E barrier', 'E dgrad mfma', 'E wgrad mfma', 'E pass-entry barrier']
 
 
 def main():
@@ -53,21 +52,6 @@ def main():
         print('forward, %s CSR: shares of summed wave cycles' % ('out' if rev else 'in'))
         for k, name in enumerate(FWD):
             print('   %-18s %5.1f%%   (per wave: %s)' % (name, 100 * t[:, k].sum() / tot, ' '.join('%4.1f' % (100 * v / tot * 8) for v in t[:, k])))
-        # backward of the same half round
-        gy = torch.randn(N, H, device=dev)
-        gd, ga = torch.empty_like(h), torch.empty_like(h)
-        acc = [torch.zeros(3 * H, H, device=dev), torch.zeros(3 * H, device=dev), torch.zeros(3 * H, H, device=dev),
-               torch.zeros(3 * H, device=dev), torch.zeros(6, 3 * H, device=dev), torch.zeros(H, device=dev), torch.zeros(H, device=dev)]
-        stamps.zero_()
-        rc = lib.mgv_diag_struct_stage_bwd_x3_impl(H, ctypes.c_int64(N), P(h), P(ptr), P(idx), P(xcls), P(xtab), 6, P(wpack), P(bc), P(bhh),
-                                                   P(lw), P(lb), ctypes.c_float(1e-5), P(gy), P(out), P(gd), P(ga), *[P(t_) for t_ in acc], 0, None, None, None, 0, st)
-        torch.cuda.synchronize()
-        assert rc == 0
-        t = stamps.view(8, 16).double().cpu()
-        tot = t.sum()
-        print('backward, %s CSR:' % ('out' if rev else 'in'))
-        for k, name in enumerate(BWD):
-            print('   %-26s %5.1f%%' % (name, 100 * t[:, k].sum() / tot))
 
 
 if __name__ == '__main__':
