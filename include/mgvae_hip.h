@@ -353,6 +353,32 @@ int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float
  * cap < 0: MGV_EINVAL. */
 int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
                          float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
+/* ---- functional-similarity search on hf (added functionality; the inference side of the functional loss, trainer.py:158-160:
+ * 1 - cosine_similarity(hf[a], hf[b], eps = 1e-8); csrc/pair_scores.hip).  Unit rows first, then the pair entries above on (y, y): a
+ * cosine is ONE k-ascending fmaf chain over two unit rows, the same bits whichever entry reports it.  A row's top-k needs all its
+ * candidates and is mgv_pair_topk(y, y, sigmoid = 0, skip_self = 1); listed pairs are mgv_pair_scores_at(y, y, sigmoid = 0).
+ * unit rows (trainer.py:158-160): y[i] = x[i] / max(|x[i]|, eps) — the clamp is per row, as torch.cosine_similarity applies it and as
+ * mgv_func_loss_fwd does — and norm[i] = |x[i]| unclamped when norm is not NULL.  H / 4 lanes per row, float4 loads and stores, the sum of
+ * squares in float32 WITHOUT rescaling: the contract is a finite sum of squares (hf is a GRU output in (-1, 1)).  A zero row gives a
+ * zero row, a row that holds a NaN a row of NaNs (and a NaN norm).  y may be exactly x (same pointer, same stride); no other overlap
+ * is promised.  H in {16, 32, 64, 128}, else MGV_EUNSUPPORTED before anything else is looked at; x [N][ldx], y [N][ldy] under the
+ * rule of the pair entries (strides multiples of 4 and >= H, bases 16-byte aligned), else MGV_EINVAL; N < 0: MGV_EINVAL; N = 0
+ * launches nothing. */
+int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm, void* stream);
+/* the symmetric form of mgv_pair_select_count (trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): s = t = y, raw scores, no
+ * sigmoid.  With s = t the score matrix is symmetric bit for bit (every product commutes and k keeps its order), so the candidates of
+ * row u are the nodes v of u's own graph with v > u, and a row tile walks the column tiles from its own diagonal tile on.  n_sel[N]
+ * int32 is written for every row.  Everything else is the contract of mgv_pair_select_count: `>` is strict and a NaN is never
+ * selected; graph_ptr's two ends are read back, NULL is one graph; the same refusals and return codes.  Bit-identical or exactly
+ * power-of-two-scaled rows score within (2H + 6) 2^-24 of 1 and are not clamped to it: threshold = 1.0 selects nothing reliably. */
+int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* n_sel,
+                         void* stream);
+/* the symmetric form of mgv_pair_select_fill (trainer.py:158-160, digae_layer.py:31-33): row u's selected v > u as batch-wide int32 ids in
+ * ascending order at col[row_ptr[u] ..], score[cap] (or NULL) the cosine beside each — the bits of mgv_pair_scores_fwd(y, y, sigmoid = 0)
+ * at [u][v] and at [v][u].  Writes fall only inside [row_ptr[u], min(row_ptr[u+1], cap)); no atomics, a second call gives the same
+ * bytes; refusals as for mgv_pair_select_fill (cap < 0: MGV_EINVAL). */
+int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
+                        const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
 /* sums[0] += sum_pos -log(sigma+1e-15), sums[1] += sum_neg -log(1-sigma+1e-15); counts += {TP,FP,TN,FN}
  * (trainer.py:240-244); pred_bin[Epos+Eneg] optional */
 int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,

@@ -6,6 +6,8 @@
 //     acc = 0;  for k = 0 .. H-1: acc = fmaf(s[i][k], t[j][k], acc)
 // which k_pair_at restates with scalar fmaf.  The dense tile code (tile_scores) is shared by the dense forward and the top-k kernel,
 // so a score reported by one is the other's bit for bit; these are decisions at a threshold and ranks, like k_edge_dot's.
+// The same entries on unit rows (k_row_unit) are the cosine search on hf, the inference side of the functional loss (trainer.py:158-160);
+// its thresholded pairs come from the symmetric form of the selection walk (k_pair_select<.., SYM>).
 #include "mgv_common.h"
 #include "../../include/mgvae_hip.h"
 
@@ -287,7 +289,11 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
 //                 the popcount of the lower columns, and the cursor (the same number in the row's 16 lanes) moves on by the block's
 //                 popcount through the whole walk.  Ascending columns, no atomics, the same bytes from call to call.  A row writes
 //                 only slots in [row_ptr[u], min(row_ptr[u+1], cap)) that are >= 0; what has no room is dropped.
-template <int H, bool FILL>
+//   SYM = true  : s = t = unit rows (mgv_sim_select_*; trainer.py:158-160 in the arithmetic of digae_layer.py:31-33).  The score matrix
+//                 is symmetric in bits, so row u lists only v > u: the walk starts at the row tile's own column tile (row and column
+//                 tiles are both 64 wide, the diagonal tile of workgroup b is column tile b) and the decision gets `col > row`.
+//                 Raw scores, no self: `sigmoid` and `skip_self` are not looked at.
+template <int H, bool FILL, bool SYM = false>
 __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                           int G, int sigmoid, float threshold, int skip_self, int32_t* n_sel,
                                                           const int64_t* row_ptr, int64_t cap, int32_t* col_out, float* score_out) {
@@ -335,7 +341,9 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
     float a[H / 4];
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     if (clo < chi) {
-        const int64_t ct0 = clo / kPairTile, ct1 = (chi + kPairTile - 1) / kPairTile;
+        int64_t ct0 = clo / kPairTile;
+        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
+        if constexpr (SYM) ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside t
         float4 nxt[H / 16];
         tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
         for (int64_t ct = ct0; ct < ct1; ++ct) {
@@ -351,8 +359,15 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const float v = acc[c][g];
-                    const bool valid = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
-                    const float rep = sigmoid ? sigmoidf_(v) : v;
+                    bool valid;
+                    float rep;
+                    if constexpr (SYM) {
+                        valid = col > row0 + 4 * q + g && col < myhi[g] && v == v;     // col > row >= the graph's start
+                        rep = v;
+                    } else {
+                        valid = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
+                        rep = sigmoid ? sigmoidf_(v) : v;
+                    }
                     const bool pass = valid && rep > threshold;
                     if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
                     const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
@@ -380,6 +395,23 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
             const int64_t u = row0 + 4 * q + g;
             if (r == 0 && u < N) n_sel[u] = n;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------- unit rows
+// y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
+// row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
+// row comes out NaN.  A row is read in full before any of it is written, so y may be x.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_row_unit(int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm) {
+    constexpr int LPR = H / 4, RPB = kThreads / LPR;
+    const int lr = threadIdx.x % LPR;
+    for (int64_t i = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR; i < N; i += (int64_t)gridDim.x * RPB) {
+        const float4 v = ld4(x + i * (int64_t)ldx + 4 * lr);
+        const float n = sqrtf(group_sum<LPR>(dot4(v, v)));
+        const float d = n < eps ? eps : n;
+        st4(y + i * (int64_t)ldy + 4 * lr, make_float4(v.x / d, v.y / d, v.z / d, v.w / d));
+        if (norm != nullptr && lr == 0) norm[i] = n;
     }
 }
 
@@ -528,5 +560,47 @@ extern "C" int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, c
     const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
     MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t,
                                               ldt, graph_ptr, G, sigmoid, threshold, skip_self, (int32_t*)nullptr, row_ptr, cap, col, score));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(N >= 0);
+    if (N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(x, ldx, H) && mgv::pair_rows_ok(y, ldy, H));
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = mgv::kThreads / (H / 4);
+    const int grid = mgv::grid_for((N + rows - 1) / rows, 8);
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_row_unit<HH>), dim3(grid), dim3(mgv::kThreads), 0, st, N, x, ldx, eps, y, ldy, norm));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
+                                    int32_t* n_sel, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(n_sel != nullptr);
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, false, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy,
+                                              y, ldy, graph_ptr, G, 0, threshold, 0, n_sel, (const int64_t*)nullptr, (int64_t)0,
+                                              (int32_t*)nullptr, (float*)nullptr));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
+                                   const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(cap >= 0);
+    bool launch;
+    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
+    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy,
+                                              y, ldy, graph_ptr, G, 0, threshold, 0, (int32_t*)nullptr, row_ptr, cap, col, score));
     MGV_LAUNCH_RET();
 }

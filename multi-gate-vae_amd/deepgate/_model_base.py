@@ -156,6 +156,32 @@ class FunctionalModel(nn.Module):
             return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
                                          with_scores=with_scores, max_edges=max_edges)
 
+    def similar_gates(self, hf, k, graph_ptr=None, threshold=0.999):
+        """(idx [N, k] int32, cos [N, k], n_above [N] int32) on the functional embeddings hf: every gate's k functionally closest gates
+        inside its own graph by cosine (batch-wide ids, -1 / -inf past the end) and the number of gates whose cosine with it is
+        > threshold (ops.sim_topk, streamed without an N x N array).  Added functionality: it mirrors the functional loss,
+        1 - cosine_similarity(hf[a], hf[b], eps=1e-8) regressed on truth-table distance (trainer.py:158-160), which the reference only
+        evaluates on the listed training pairs.  Primary inputs and other never-updated nodes have hf = 0: their cosine is 0 with
+        everything, so no positive threshold ever reports them.  Bit-identical or power-of-two-scaled rows score within
+        (2H + 6) 2^-24 of 1 and are not clamped to it: threshold = 1.0 selects nothing reliably, hence the default 0.999."""
+        return ops.sim_topk(hf, k, graph_ptr=graph_ptr, threshold=threshold)
+
+    def equivalence_candidates(self, hf, graph_ptr=None, threshold=0.999, with_scores=False, max_pairs=None):
+        """(pair_index int64 [2, P] with pair_index[0] < pair_index[1], row_ptr int64 [N + 1], cos [P] or None): every unordered pair
+        of gates of one graph whose functional embeddings have a cosine > threshold, once — the candidates for SAT sweeping and
+        equivalence checking (ops.sim_pairs: unit rows, then the symmetric count / scan / fill; nothing of size N^2).  Added
+        functionality: the search side of the functional loss 1 - cosine_similarity(hf[a], hf[b], eps=1e-8) (trainer.py:158-160).  More
+        than `max_pairs` pairs raise HipLibraryError before anything is filled.  Primary inputs and other never-updated nodes have
+        hf = 0 (cosine 0 with everything) and are never reported at a positive threshold; equal rows score within (2H + 6) 2^-24 of
+        1, not exactly 1, so threshold = 1.0 selects nothing reliably and the default is 0.999."""
+        return ops.sim_pairs(hf, graph_ptr=graph_ptr, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
+
+    def functional_similarity(self, hf, pair_index):
+        """cos(hf[a], hf[b]) of the listed pairs [2, P]: 1 - this is the `dis` of the functional loss (trainer.py:158-160, eps = 1e-8 per
+        row), in the arithmetic of similar_gates and equivalence_candidates — the same bits for the same pair.  Added functionality.
+        A never-updated node (hf = 0) has cosine 0 with everything."""
+        return ops.sim_at(hf, pair_index)
+
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the

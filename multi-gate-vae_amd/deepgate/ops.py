@@ -1088,6 +1088,102 @@ def dense_scores(s, t):
     return pair_scores(s, t, sigmoid=False)
 
 
+# ------------------------------------------------------------------------------------------------
+# functional-similarity search on hf (added functionality: the inference side of the functional loss, trainer.py:158-160)
+# ------------------------------------------------------------------------------------------------
+# Two facts for every function below.  Primary inputs and other never-updated nodes have hf = 0: their cosine is 0 with everything, so no
+# positive threshold ever reports them.  Bit-identical or exactly power-of-two-scaled rows score within (2H + 6) 2^-24 of 1 and are not
+# clamped to it: threshold = 1.0 selects nothing reliably, hence the default 0.999.
+SIM_THRESHOLD = 0.999
+
+
+def _sim_width(x, name):
+    if x.dim() == 2 and x.shape[1] not in _PAIR_WIDTHS:
+        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
+                              % (name, list(_PAIR_WIDTHS), x.shape[1]))
+
+
+def _sim_graphs(graph_ptr, dev):
+    if graph_ptr is None:
+        return None, 0
+    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
+    if gp.numel() < 1:
+        raise HipLibraryError('graph_ptr needs at least one entry')
+    return gp, gp.numel() - 1
+
+
+def row_unit(x, eps=1e-8, want_norm=False):
+    """y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity and of the functional loss (trainer.py:158-160,
+    mgv_func_loss_fwd); with want_norm also |x[i]| unclamped: (y, norm).  A zero row stays a zero row, a row with a NaN becomes NaN.
+    The sum of squares is float32 without rescaling (hf is a GRU output in (-1, 1)).  No grad."""
+    _sim_width(x, 'row_unit')
+    with torch.no_grad():
+        xd, ldx = _pair_rows(x, 'x')
+        N, H = xd.shape
+        y = torch.empty((N, H), dtype=F32, device=xd.device)
+        norm = torch.empty(N, dtype=F32, device=xd.device) if want_norm else None
+        _hip.call('mgv_row_unit', H, N, ptr(xd), ldx, float(eps), ptr(y), H, ptr(norm))
+    return (y, norm) if want_norm else y
+
+
+def sim_topk(x, k, graph_ptr=None, threshold=SIM_THRESHOLD, eps=1e-8):
+    """(idx [N, k] int32, cos [N, k], n_above [N] int32): per row u the k nodes v != u of u's own graph with the largest cosine
+    (ties: lower id first; -1 / -inf past the end), and the number of ALL candidates v != u whose cosine is > threshold (so n_above
+    is symmetric).  A row needs all its candidates, so this is pair_topk on the unit rows; a cosine is the same bits as in sim_pairs
+    and sim_at.  Zero rows (primary inputs) score 0 with everything; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1."""
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        return pair_topk(y, y, k, graph_ptr=graph_ptr, sigmoid=False, threshold=threshold, skip_self=True)
+
+
+def _sim_room(total, with_scores, max_pairs, free):
+    """The two refusals of sim_pairs between its count and its fill, as _select_room's: more pairs than the caller allows, or a result
+    (int64 pair_index, the int32 list it is made from, float32 scores when asked for) the device cannot hold."""
+    hint = 'raise the threshold, or take the k most similar gates per node with ops.sim_topk / similar_gates'
+    if max_pairs is not None and total > int(max_pairs):
+        raise HipLibraryError('sim_pairs: %d pairs are above the threshold, max_pairs allows %d: %s' % (total, int(max_pairs), hint))
+    need = (24 if with_scores else 20) * total
+    if free is not None and need > free:
+        raise HipLibraryError('sim_pairs: %d pairs above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
+                              % (total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
+
+
+def sim_pairs(x, graph_ptr=None, threshold=SIM_THRESHOLD, with_scores=False, max_pairs=None, eps=1e-8):
+    """(pair_index int64 [2, P] with pair_index[0] < pair_index[1], row_ptr int64 [N + 1], score [P] or None): every unordered pair of
+    nodes of one graph whose cosine is > threshold, once, ordered by the smaller id and then the larger — the candidates for SAT
+    sweeping and equivalence checking.  Unit rows, then the symmetric selection (mgv_sim_select_*: half the tiles of pair_select on
+    the same rows): count, exclusive int64 scan, ONE read-back of the total, fill; nothing of size N^2, no atomics.  A total above
+    `max_pairs` or beyond the free memory raises HipLibraryError before anything is allocated or filled.  Zero rows (primary inputs)
+    pair with nothing at a positive threshold; threshold = 1.0 selects nothing reliably (equal rows score within (2H + 6) 2^-24 of 1)."""
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        N, H = y.shape
+        dev = y.device
+        gp, G = _sim_graphs(graph_ptr, dev)
+        common = (H, N, ptr(y), H, ptr(gp), G, float(threshold))
+        n_sel = torch.empty(N, dtype=I32, device=dev)
+        _hip.call('mgv_sim_select_count', *common, ptr(n_sel))
+        row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
+        total = int(row_ptr[-1])                                      # the read-back
+        free, _ = torch.cuda.mem_get_info(dev)
+        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # as _dense_fits
+        _sim_room(total, with_scores, max_pairs, free)
+        col = torch.empty(total, dtype=I32, device=dev)
+        score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
+        _hip.call('mgv_sim_select_fill', *common, ptr(row_ptr), total, ptr(col), ptr(score))
+        rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=dev), row_ptr[1:] - row_ptr[:-1], output_size=total)
+        return torch.stack([rows, col.to(torch.int64)]), row_ptr, score
+
+
+def sim_at(x, pair_index, eps=1e-8):
+    """cos(x[a], x[b]) of the listed pairs [2, P], the cosine of the functional loss (1 - sim_at is its `dis`, trainer.py:158-160) in
+    the arithmetic of sim_topk and sim_pairs: the same bits for the same pair."""
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        return pair_scores_at(y, y, pair_index, sigmoid=False)
+
+
 class ReconLossFn(torch.autograd.Function):
     """-mean log(sigma(<s_u,t_v>)+1e-15) over positives - mean log(1-sigma+1e-15) over negatives
     (dg_ae_model_aig.py:108-130) on st = hs_decompose(hs) [N,2H]; also the confusion counters and,

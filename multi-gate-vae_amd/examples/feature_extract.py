@@ -7,6 +7,8 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --link_metrics      # + ROC-AUC / AP of the decoder per batch
     python examples/feature_extract.py --type aig --synthetic 4 --predict_links 8   # + every gate's 8 most probable fan-out targets
     python examples/feature_extract.py --type aig --synthetic 4 --reconstruct 0.5   # + the decoded edge list of every graph
+    python examples/feature_extract.py --type aig --synthetic 4 --similar 8         # + every gate's 8 functionally closest gates
+    python examples/feature_extract.py --type aig --synthetic 4 --equivalences 0.999   # + the gate pairs with cos(hf) above 0.999
 """
 import argparse
 import os
@@ -40,6 +42,13 @@ def main(argv=None):
                     'pair inside a graph scored above THR (name/rec_edge_index [2, E\'], ids local to the graph, listed per source in '
                     'ascending target order) with its precision and recall against the true edges (name/rec_precision, name/rec_recall; '
                     'Model.reconstruct_edges / reconstruction_counts)')
+    ap.add_argument('--similar', type=int, default=0, metavar='K', help='also store every gate\'s K functionally closest gates inside its '
+                    'graph by cosine of hf (name/sim_idx, ids local to the graph, -1 past the end; name/sim_cos; Model.similar_gates; '
+                    '1 <= K <= 32).  Primary inputs have hf = 0 and cosine 0 with everything')
+    ap.add_argument('--equivalences', type=float, default=None, metavar='THR', help='also store the unordered gate pairs of every graph '
+                    'whose hf have a cosine above THR, the candidates for equivalence checking (name/eq_pairs [2, P], local ids, first < '
+                    'second; name/eq_cos; Model.equivalence_candidates).  Equal rows score within (2H + 6) 2^-24 of 1, not exactly 1: '
+                    'use 0.999 rather than 1.0; primary inputs (hf = 0) are never reported at a positive THR')
     a = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
@@ -71,8 +80,23 @@ def main(argv=None):
                 rec_ei, rec_ptr, _ = model.reconstruct_edges(hs, graph_ptr=batch.graph_ptr, threshold=a.reconstruct)
                 rc = model.reconstruction_counts(hs, batch.edge_index, batch.graph_ptr, threshold=a.reconstruct).double().cpu()
                 rec_ei, eptr = rec_ei.cpu().numpy(), rec_ptr[batch.graph_ptr.to(rec_ptr.device).long()].tolist()      # the graphs' places in the list
+            if a.similar:
+                sim_idx, sim_cos, _ = model.similar_gates(hf, a.similar, graph_ptr=batch.graph_ptr)
+                sim_idx, sim_cos = sim_idx.cpu().numpy(), sim_cos.cpu().numpy()
+            if a.equivalences is not None:
+                eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=a.equivalences, with_scores=True)
+                eq, eq_cos = eq.cpu().numpy(), eq_cos.cpu().numpy()
+                qptr = eq_ptr[batch.graph_ptr.to(eq_ptr.device).long()].tolist()               # the graphs' places in the list
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if a.similar:
+                    loc = sim_idx[ptr[k]:ptr[k + 1]]
+                    out[name + '/sim_idx'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
+                    out[name + '/sim_cos'] = sim_cos[ptr[k]:ptr[k + 1]]
+                if a.equivalences is not None:
+                    out[name + '/eq_pairs'] = (eq[:, qptr[k]:qptr[k + 1]] - ptr[k]).astype(np.int32)
+                    out[name + '/eq_cos'] = eq_cos[qptr[k]:qptr[k + 1]]
+                    print('[INFO] %s: %d gate pairs with cos(hf) > %g' % (name, qptr[k + 1] - qptr[k], a.equivalences))
                 if a.reconstruct is not None:
                     out[name + '/rec_edge_index'] = (rec_ei[:, eptr[k]:eptr[k + 1]] - ptr[k]).astype(np.int32)
                     out[name + '/rec_precision'] = np.float64(rc[k, 0] / max(float(rc[k, 1]), 1.0))
