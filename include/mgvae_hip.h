@@ -379,6 +379,45 @@ int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_
  * bytes; refusals as for mgv_pair_select_fill (cap < 0: MGV_EINVAL). */
 int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                         const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
+/* ---- connected components on the device (added functionality; csrc/components.hip, csrc/mgv_unionfind.h): candidate classes of the
+ * relation "same graph and cosine > threshold" on hf (trainer.py:158-160) and components of decoded link lists (digae_layer.py:31-33).
+ * One forest parent[N] int32, N < 2^31, with 0 <= parent[x] <= x at all times: a root is only ever hooked under a smaller root
+ * (compare-and-swap), so a finished component's root is its smallest id whatever the schedule, and the labels are the same bits from
+ * run to run.  While hooks can happen every access to parent is an agent-scope atomic.  status[4] int32 = {code, a, b, rounds}, all 0
+ * when nothing went wrong; the first error wins: 1 = an entry of parent outside [0, x] (parent never went through mgv_cc_init), 2 = a
+ * loop reached its cap of 2^20 rounds (no schedule of a sound forest gets there), 3 = a listed id outside [0, N).  The thread that
+ * records an error leaves; the host reads status in the read-back it does anyway (mgv_cc_class_count hands it over).
+ * init (trainer.py:158-160, digae_layer.py:31-33): parent[i] = i, status = 0.  N = 0 only clears status. */
+int mgv_cc_init(int64_t N, int32_t* parent, int32_t* status, void* stream);
+/* unites a[e] and b[e] for e < P (trainer.py:158-160, digae_layer.py:31-33): int64 lists like mgv_pair_scores_at's, in any order and
+ * orientation, duplicates allowed, a[e] == b[e] does nothing.  Ids are the caller's contract as there, but one outside [0, N) is never
+ * dereferenced: the pair is skipped and status records it (code 3).  Grid-stride, one pair per thread.  P = 0 launches nothing. */
+int mgv_cc_union_pairs(int64_t N, int64_t P, const int64_t* a, const int64_t* b, int32_t* parent, int32_t* status, void* stream);
+/* after the last hook (trainer.py:158-160, digae_layer.py:31-33): label[i] = the root of i = the smallest id of i's component; size[r]
+ * (or NULL) = the number of nodes whose root is r, 0 where r is no root (int32 atomic adds: exact, order-free); with size, parent is
+ * flattened to the labels.  N = 0 launches nothing. */
+int mgv_cc_labels(int64_t N, int32_t* parent, int32_t* label, int32_t* size, void* stream);
+/* the classes with at least min_size members as a compact table (trainer.py:158-160, digae_layer.py:31-33): class_ptr int64 [C + 1],
+ * members int32 [M]; classes in the order of their labels, members ascending inside a class, so members[class_ptr[c]] is the class's
+ * label.  label[N] as mgv_cc_labels writes it (label[i] <= i, label[label[i]] = label[i]; an entry outside [0, N) belongs to nothing).
+ * count: sizes from the labels, two flag arrays, two exclusive scans (mgv_scan_exclusive_i32), then counts[6] int32 = {C, M, status[0..3]}
+ * (status may be NULL: zeros) — the ONE read-back between sizing and filling.  ws: mgv_cc_class_ws_ints(N) int32s (-1: N out of range),
+ * 256-byte aligned, handed unchanged to fill.  min_size < 1: MGV_EINVAL.
+ * fill: the selected nodes in id order, a stable sort by label (mgv_sort_pairs; sort_temp of mgv_sort_pairs_temp_ints(4, M) int32s),
+ * then members and class_ptr.  C = M = 0 writes class_ptr[0] = 0 only. */
+int mgv_cc_class_ws_ints(int64_t N);
+int mgv_cc_class_count(int64_t N, const int32_t* label, int min_size, const int32_t* status, int32_t* ws, int64_t ws_ints, int32_t* counts,
+                       void* stream);
+int mgv_cc_class_fill(int64_t N, const int32_t* label, int64_t C, int64_t M, int32_t* ws, int64_t ws_ints, void* sort_temp,
+                      int64_t sort_temp_ints, int64_t* class_ptr, int32_t* members, void* stream);
+/* classes straight from the symmetric tile walk (trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): the tiles, scores and
+ * decision of mgv_sim_select_fill — v > u, v in u's graph, cosine not NaN and > threshold — but where the fill would store v in row u's
+ * list, u and v are united in parent (initialised by mgv_cc_init; several calls may add to one forest).  No pair list ever exists: memory
+ * is O(N) whatever the threshold.  A cosine is the same bits whichever entry computes it, so mgv_cc_labels afterwards gives exactly the
+ * components of the list mgv_sim_select_fill returns for the same arguments.  Arguments and refusals as mgv_sim_select_count; NULL
+ * parent (N > 0) or status: MGV_EINVAL. */
+int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,
+                  int32_t* status, void* stream);
 /* sums[0] += sum_pos -log(sigma+1e-15), sums[1] += sum_neg -log(1-sigma+1e-15); counts += {TP,FP,TN,FN}
  * (trainer.py:240-244); pred_bin[Epos+Eneg] optional */
 int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,

@@ -8,7 +8,9 @@
 // so a score reported by one is the other's bit for bit; these are decisions at a threshold and ranks, like k_edge_dot's.
 // The same entries on unit rows (k_row_unit) are the cosine search on hf, the inference side of the functional loss (trainer.py:158-160);
 // its thresholded pairs come from the symmetric form of the selection walk (k_pair_select<.., SYM>).
+// The classes of that relation come from the same walk with a union-find in place of the lists (k_sim_union, mgv_unionfind.h).
 #include "mgv_common.h"
+#include "mgv_unionfind.h"
 #include "../../include/mgvae_hip.h"
 
 #include <limits.h>
@@ -398,6 +400,80 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
     }
 }
 
+// ---------------------------------------------------------------------------------- classes straight from the walk
+// The symmetric walk of k_pair_select<H, ., true> — the same tiles, tile_scores and decision `col > row && col < hi && v == v &&
+// v > threshold` — as a sibling kernel on the shared helpers (the selection kernels are not touched and compile as before).  Where the
+// fill would store column `col` of row `row`, the pair is united in `parent` (mgv_unionfind.h: every access an agent-scope atomic, the
+// smaller root wins, bounded retries).  A cosine is the same bits whichever kernel computes it, so the components are exactly those of
+// the list mgv_sim_select_fill writes.  Outside the MFMA section: a lane first decides its 16 entries of the tile into a bit mask, then
+// unites the set bits; uf_unite starts with the two finds and leaves when the roots agree, which at a low threshold is nearly always.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* y, int ldy, const int32_t* gp, int G, float threshold,
+                                                        int32_t* parent, int32_t* status) {
+    constexpr int LDT = PairCfg<H>::LDT;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    if (threadIdx.x < kPairTile) {
+        const int64_t u = u0 + threadIdx.x;
+        int64_t lo = 0, hi = 0;
+        if (u < N) {
+            if (gp == nullptr) { hi = N; }
+            else {
+                int a = 0, b = G;                          // first graph whose end lies behind u
+                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
+                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no node outside [0, N) is touched
+                hi = hi < lo ? lo : (hi > N ? N : hi);
+            }
+        }
+        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+    }
+    __syncthreads();
+    int64_t clo = N, chi = 0;
+    for (int i = 0; i < kPairTile; ++i) {
+        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
+    }
+    const int64_t row0 = u0 + 16 * w;
+    int myhi[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) myhi[g] = rhi[16 * w + 4 * q + g];      // 0 for a row past N: it decides nothing
+    float a[H / 4];
+    load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
+    if (clo < chi) {
+        int64_t ct0 = clo / kPairTile;
+        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
+        ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside y
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+            unsigned bits = 0;                              // bit 4 c + g: the lane's entry (row 4 q + g, column 16 c + r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t col = ct * kPairTile + 16 * c + r;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float v = acc[c][g];
+                    const bool pass = col > row0 + 4 * q + g && col < myhi[g] && v == v && v > threshold;
+                    bits |= pass ? 1u << (4 * c + g) : 0u;
+                }
+            }
+            while (bits != 0) {                             // row < col < myhi <= N: both ids inside parent
+                const int b = __ffs(bits) - 1;
+                bits &= bits - 1;
+                uf_unite(parent, (int)(row0 + 4 * q + (b & 3)), (int)(ct * kPairTile + 16 * (b >> 2) + r), status);
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- unit rows
 // y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
 // row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
@@ -602,5 +678,19 @@ extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, co
     const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
     MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy,
                                               y, ldy, graph_ptr, G, 0, threshold, 0, (int32_t*)nullptr, row_ptr, cap, col, score));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,
+                             int32_t* status, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK) return rc;
+    MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
+    if (!launch) return MGV_OK;
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_sim_union<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy, graph_ptr, G,
+                                              threshold, parent, status));
     MGV_LAUNCH_RET();
 }

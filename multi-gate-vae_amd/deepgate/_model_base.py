@@ -176,6 +176,19 @@ class FunctionalModel(nn.Module):
         1, not exactly 1, so threshold = 1.0 selects nothing reliably and the default is 0.999."""
         return ops.sim_pairs(hf, graph_ptr=graph_ptr, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
 
+    def equivalence_classes(self, hf, graph_ptr=None, threshold=0.999, min_size=2):
+        """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]): the equivalence candidate CLASSES of a batch, what a SAT sweeper
+        consumes — the connected components of equivalence_candidates' relation (same graph, cosine of hf > threshold), computed on the
+        device without the pair list (ops.sim_classes, route='walk': memory O(N); a class of 5,000 equal gates is 5,000 integers, not
+        12.5 M pairs).  label[i] is the smallest id of gate i's class, so label[i] == i marks the representative the others are checked
+        against; class c of the table is members[class_ptr[c] : class_ptr[c + 1]], ascending, for the classes with at least min_size
+        gates.  Added functionality: the search side of the functional loss 1 - cosine_similarity(hf[a], hf[b], eps=1e-8)
+        (trainer.py:158-160).  Single linkage: two gates of one class can have a cosine below the threshold.  Primary inputs and other
+        never-updated nodes have hf = 0 (cosine 0 with everything) and are always singletons at a positive threshold, as are rows with
+        a NaN; classes never cross graphs; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1, so threshold = 1.0 is unreliable
+        and the default is 0.999.  Exact and the same bits from run to run: equal to ops.components of equivalence_candidates."""
+        return ops.sim_classes(hf, graph_ptr=graph_ptr, threshold=threshold, min_size=min_size)
+
     def functional_similarity(self, hf, pair_index):
         """cos(hf[a], hf[b]) of the listed pairs [2, P]: 1 - this is the `dis` of the functional loss (trainer.py:158-160, eps = 1e-8 per
         row), in the arithmetic of similar_gates and equivalence_candidates — the same bits for the same pair.  Added functionality.

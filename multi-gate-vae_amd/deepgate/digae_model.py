@@ -39,6 +39,11 @@ class DirectedGAE(torch.nn.Module):
             return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
                                          with_scores=with_scores, max_edges=max_edges)
 
+    def reconstructed_components(self, edge_index, N):
+        """label int32 [N]: the weakly connected components of a decoded link list (reconstruct_edges' edge_index, direction ignored) —
+        label[i] is the smallest id of i's component (ops.components, a union-find on the device).  Added functionality."""
+        return ops.components(edge_index, N)
+
     def encode(self, *args, **kwargs):
         return self.encoder(*args, **kwargs)
 

@@ -1184,6 +1184,140 @@ def sim_at(x, pair_index, eps=1e-8):
         return pair_scores_at(y, y, pair_index, sigmoid=False)
 
 
+# ------------------------------------------------------------------------------------------------
+# connected components and candidate classes (added functionality: csrc/components.hip, csrc/mgv_unionfind.h)
+# ------------------------------------------------------------------------------------------------
+_CC_ERR = {1: 'an entry of the forest outside [0, x] (parent was not initialised)', 2: 'a union-find loop reached its cap of 2^20 rounds',
+           3: 'a listed node id outside [0, N)'}
+
+
+def _cc_status(name, st):
+    """st = the four ints of the union-find's status record, already on the host."""
+    if st[0] != 0:
+        raise HipLibraryError('%s: the union-find reported an error: %s (code %d, a = %d, b = %d, rounds = %d)'
+                              % (name, _CC_ERR.get(st[0], 'unknown'), st[0], st[1], st[2], st[3]))
+
+
+def _cc_forest(N, dev):
+    if N >= 2 ** 31:
+        raise HipLibraryError('components: node ids are int32, N = %d is beyond them' % N)
+    parent = torch.empty(N, dtype=I32, device=dev)
+    status = torch.empty(4, dtype=I32, device=dev)
+    _hip.call('mgv_cc_init', N, ptr(parent), ptr(status))
+    return parent, status
+
+
+def _cc_labels(N, parent):
+    label = torch.empty(N, dtype=I32, device=parent.device)
+    _hip.call('mgv_cc_labels', N, ptr(parent), ptr(label), None)      # sizes come with the class table
+    return label
+
+
+def _cc_from_pairs(pair_index, N):
+    """(label, status) of the pair list's components; status is still on the device."""
+    a, b = _edge_rows(pair_index)
+    parent, status = _cc_forest(N, pair_index.device)
+    _hip.call('mgv_cc_union_pairs', N, a.numel(), ptr(a), ptr(b), ptr(parent), ptr(status))
+    return _cc_labels(N, parent), status
+
+
+def _min_size(min_size):
+    if int(min_size) != min_size or int(min_size) < 1:
+        raise HipLibraryError('min_size must be an integer >= 1 (1 lists every node, singletons included), got %r' % (min_size,))
+    return int(min_size)
+
+
+def components(pair_index, N):
+    """label int32 [N]: the connected components of the undirected graph on nodes 0 .. N - 1 whose edges are the columns of pair_index
+    (int64 [2, P], P = 0 included; any order and orientation, duplicates and a == a allowed) — label[i] is the smallest id of i's
+    component, so label[i] == i marks a component's representative and an untouched node is its own.  A concurrent union-find on the
+    device in which a root is only ever hooked under a smaller root: exact, and the same bits from run to run.  For lists from
+    sim_pairs / equivalence_candidates (candidate classes) and from reconstruct_edges (components of the decoded graph,
+    digae_layer.py:31-33) alike.  One synchronisation: the union-find's status record is read back, and anything in it (an id outside
+    [0, N)) raises HipLibraryError.  No grad."""
+    N = int(N)
+    if N < 0:
+        raise HipLibraryError('components: N must be >= 0, got %d' % N)
+    if not (torch.is_tensor(pair_index) and pair_index.dim() == 2 and pair_index.shape[0] == 2):
+        raise HipLibraryError('components: pair_index must be an int64 tensor [2, P]')
+    if not pair_index.is_cuda:
+        raise HipLibraryError('pair_index must live on the GPU (got %s); the hot path has no CPU implementation' % pair_index.device)
+    if pair_index.dtype != torch.int64:
+        raise HipLibraryError('pair_index must be torch.int64 (got %s)' % pair_index.dtype)
+    with torch.no_grad():
+        label, status = _cc_from_pairs(pair_index, N)
+        _cc_status('components', status.tolist())             # the read-back
+    return label
+
+
+def _class_table(label, min_size, status, name):
+    N, dev = label.numel(), label.device
+    ws_ints = _hip.call_value('mgv_cc_class_ws_ints', N)
+    if ws_ints < 0:
+        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): N = %d' % (name, N))
+    ws = torch.empty(ws_ints, dtype=I32, device=dev)
+    counts = torch.empty(6, dtype=I32, device=dev)
+    _hip.call('mgv_cc_class_count', N, ptr(label), min_size, ptr(status), ptr(ws), ws_ints, ptr(counts))
+    got = counts.tolist()                                     # the read-back: C, M and the status record
+    _cc_status(name, got[2:])
+    C, M = got[0], got[1]
+    class_ptr = torch.empty(C + 1, dtype=torch.int64, device=dev)
+    members = torch.empty(M, dtype=I32, device=dev)
+    temp_ints = _hip.call_value('mgv_sort_pairs_temp_ints', 4, max(M, 1))
+    temp = torch.empty(max(temp_ints, 1), dtype=I32, device=dev)
+    _hip.call('mgv_cc_class_fill', N, ptr(label), C, M, ptr(ws), ws_ints, ptr(temp), temp_ints, ptr(class_ptr), ptr(members))
+    return class_ptr, members
+
+
+def class_table(label, min_size=2):
+    """(class_ptr int64 [C + 1], members int32 [M]): the classes of `label` (int32 [N] as components / sim_classes return it) with at
+    least min_size members, as one compact table.  Classes come in the order of their labels and members ascend inside a class, so
+    members[class_ptr[c]] is class c's label (its smallest id, the natural representative) and members[class_ptr[c] : class_ptr[c + 1]]
+    the whole class.  min_size = 2 leaves the singletons out; 1 lists every node.  Sizes, two scans and a stable sort by label on the
+    device with ONE read-back (C and M: the result must be allocated).  No grad."""
+    min_size = _min_size(min_size)
+    check(label, I32, 'label')
+    if label.dim() != 1:
+        raise HipLibraryError('class_table: label must be int32 [N]')
+    with torch.no_grad():
+        return _class_table(label, min_size, None, 'class_table')
+
+
+def sim_classes(x, graph_ptr=None, threshold=SIM_THRESHOLD, min_size=2, route='walk', eps=1e-8, max_pairs=None):
+    """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]): the candidate classes a SAT sweeper consumes — the connected
+    components of the relation "same graph and cosine > threshold" on the rows of x (hf), as components' labels (label[i] = the
+    smallest id of i's class) and class_table's table of the classes with at least min_size members.
+    The classes are SINGLE-LINKAGE components of the thresholded relation: two members of one class can have a cosine below the
+    threshold (a chain of close neighbours links them); every member has at least one other member above it.  Primary inputs
+    (hf = 0: cosine 0 with everything) and rows that hold a NaN are always singletons at a positive threshold.  Classes never cross
+    graphs (graph_ptr [G + 1]; None: one graph).  threshold = 1.0 is unreliable: equal rows score within (2H + 6) 2^-24 of 1, not
+    exactly 1, hence the default 0.999.
+    route='walk': the symmetric tile walk of sim_pairs unites each pair where it finds it (mgv_sim_union).  No pair list ever exists:
+    memory is O(N) and nothing is refused for size — 5,000 equal gates are 12.5 M pairs but one class of 5,000.
+    route='pairs': sim_pairs followed by components; it keeps sim_pairs' refusals (max_pairs, free memory).
+    Both routes give the same labels, exactly, and the same bits from run to run.  Unit rows come from row_unit.  One read-back (the
+    table's two sizes and the union-find's status record) besides the two ends of a graph_ptr.  No grad."""
+    if route not in ('walk', 'pairs'):
+        raise HipLibraryError("sim_classes: route must be 'walk' (classes straight from the tile walk) or 'pairs' (sim_pairs, then "
+                              "components), got %r" % (route,))
+    min_size = _min_size(min_size)
+    if route == 'walk' and max_pairs is not None:
+        raise HipLibraryError("sim_classes: max_pairs belongs to route='pairs'; the walk holds no pair list")
+    if route == 'pairs':
+        pi, _, _ = sim_pairs(x, graph_ptr=graph_ptr, threshold=threshold, max_pairs=max_pairs, eps=eps)
+        with torch.no_grad():
+            label, status = _cc_from_pairs(pi, x.shape[0])
+            return (label,) + _class_table(label, min_size, status, 'sim_classes')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        N, H = y.shape
+        gp, G = _sim_graphs(graph_ptr, y.device)
+        parent, status = _cc_forest(N, y.device)
+        _hip.call('mgv_sim_union', H, N, ptr(y), H, ptr(gp), G, float(threshold), ptr(parent), ptr(status))
+        label = _cc_labels(N, parent)
+        return (label,) + _class_table(label, min_size, status, 'sim_classes')
+
+
 class ReconLossFn(torch.autograd.Function):
     """-mean log(sigma(<s_u,t_v>)+1e-15) over positives - mean log(1-sigma+1e-15) over negatives
     (dg_ae_model_aig.py:108-130) on st = hs_decompose(hs) [N,2H]; also the confusion counters and,

@@ -49,6 +49,11 @@ def main(argv=None):
                     'whose hf have a cosine above THR, the candidates for equivalence checking (name/eq_pairs [2, P], local ids, first < '
                     'second; name/eq_cos; Model.equivalence_candidates).  Equal rows score within (2H + 6) 2^-24 of 1, not exactly 1: '
                     'use 0.999 rather than 1.0; primary inputs (hf = 0) are never reported at a positive THR')
+    ap.add_argument('--classes', type=float, default=None, metavar='THR', help='also store every graph\'s equivalence candidate classes, '
+                    'what a SAT sweeper consumes: the connected components of "cos(hf) above THR" (name/eq_label [n], the smallest local '
+                    'id of a gate\'s class; name/eq_class_ptr [C + 1] and name/eq_members [M], the classes with at least two gates, '
+                    'members ascending, local ids; Model.equivalence_classes).  Single linkage: two gates of one class can have a '
+                    'cosine below THR.  Primary inputs (hf = 0) are always singletons; use 0.999 rather than 1.0')
     a = ap.parse_args(argv)
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
@@ -87,8 +92,18 @@ def main(argv=None):
                 eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=a.equivalences, with_scores=True)
                 eq, eq_cos = eq.cpu().numpy(), eq_cos.cpu().numpy()
                 qptr = eq_ptr[batch.graph_ptr.to(eq_ptr.device).long()].tolist()               # the graphs' places in the list
+            if a.classes is not None:
+                cl_label, cl_ptr, cl_mem = (x.cpu().numpy() for x in model.equivalence_classes(hf, graph_ptr=batch.graph_ptr,
+                                                                                               threshold=a.classes))
+                cptr = np.searchsorted(cl_mem[cl_ptr[:-1]], ptr).tolist()      # classes come by label and never cross graphs
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if a.classes is not None:
+                    cp = cl_ptr[cptr[k]:cptr[k + 1] + 1]
+                    out[name + '/eq_label'] = (cl_label[ptr[k]:ptr[k + 1]] - ptr[k]).astype(np.int32)
+                    out[name + '/eq_class_ptr'] = (cp - cp[0]).astype(np.int64)
+                    out[name + '/eq_members'] = (cl_mem[cp[0]:cp[-1]] - ptr[k]).astype(np.int32)
+                    print('[INFO] %s: %d classes of %d gates with cos(hf) > %g' % (name, cptr[k + 1] - cptr[k], cp[-1] - cp[0], a.classes))
                 if a.similar:
                     loc = sim_idx[ptr[k]:ptr[k + 1]]
                     out[name + '/sim_idx'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
