@@ -379,6 +379,28 @@ int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_
  * bytes; refusals as for mgv_pair_select_fill (cap < 0: MGV_EINVAL). */
 int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                         const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
+/* ---- the distribution of all-pair scores (added functionality; the thresholds of the entries above chosen by count: digae_layer.py:31-33,
+ * digae_model.py:118-122 for the decoder, trainer.py:158-160 for the cosine; csrc/pair_scores.hip).  One walk of mgv_pair_select_count —
+ * the same candidates (u's own graph, without v = u when skip_self), the same reported score (the sigmoid when `sigmoid`), a NaN counted
+ * nowhere — bins every candidate by the number of edges it passes: hist[g][k] = candidates of graph g with #{j : rep > edges[j]} == k, so
+ * bin 0 holds rep <= edges[0] and bin B rep > edges[B-1].  edges [B] float32 on the device, strictly ascending, no NaN, 1 <= B <= 256;
+ * hist int64 [max(G, 1)][B + 1] is OVERWRITTEN (the launcher zeroes it; NULL graph_ptr: row 0).  The bin comes from the comparisons
+ * `rep > edges[j]` themselves (a binary search over the table in LDS), never from an affine map of the score: for every j and g,
+ * sum(hist[g][j+1:]) equals the sum over g's rows of n_sel of mgv_pair_select_count at threshold = edges[j] as integers.  Integer atomics
+ * only (64-bit counters in LDS, one global add per non-zero (graph, bin) of a workgroup's first and last graph; the graphs between them,
+ * at most 62 nodes in all, add directly): exact, the same bytes from call to call, no counter can overflow for any N <= 2^31 - 1.
+ * Refused before anything is launched or zeroed: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); B outside [1, 256], NULL edges or
+ * hist, a bad row stride or alignment, N out of range, a graph_ptr that does not start at 0 and end at N, a table that does not ascend
+ * strictly or holds a NaN (edges is read back for this, as graph_ptr's two ends are: one small blocking copy): MGV_EINVAL.  N = 0
+ * zeroes hist and launches nothing. */
+int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                  int skip_self, const float* edges, int B, int64_t* hist, void* stream);
+/* the symmetric form (trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): the walk, candidates and score of mgv_sim_select_count
+ * — unit rows y, v > u only, raw cosine, half the tiles from the diagonal tile on — binned as above; sum(hist[g][j+1:]) equals the
+ * total of mgv_sim_select_count at threshold = edges[j].  Zero rows score 0; equal rows score within (2H + 6) 2^-24 of 1 and are not
+ * clamped to it.  Arguments and refusals as mgv_pair_hist. */
+int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B, int64_t* hist,
+                 void* stream);
 /* ---- connected components on the device (added functionality; csrc/components.hip, csrc/mgv_unionfind.h): candidate classes of the
  * relation "same graph and cosine > threshold" on hf (trainer.py:158-160) and components of decoded link lists (digae_layer.py:31-33).
  * One forest parent[N] int32, N < 2^31, with 0 <= parent[x] <= x at all times: a root is only ever hooked under a smaller root

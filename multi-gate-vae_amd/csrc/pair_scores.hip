@@ -474,6 +474,141 @@ __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* 
     }
 }
 
+// ---------------------------------------------------------------------------------- the distribution of all-pair scores
+// The walk of k_pair_select<H, false, SYM> — the same tiles, tile_scores, `valid` and `rep` — as a sibling kernel on the shared helpers
+// (the selection and union kernels are not touched and compile as before).  Where the count adds `rep > threshold`, a candidate is
+// binned by bin = #{j : rep > edges[j]}: a branch-free binary search over the table in LDS, padded with +inf (nothing passes it) to
+// 2^p - 1 entries, 2^p the first power of two above B, so that p steps `pos += rep > el[pos + step - 1] ? step : 0` from step = 2^(p-1)
+// down to 1 count the edges below rep.  The same `>` on the same bits as the count entry: sum(hist[g][j+1:]) IS its total at edges[j].
+//
+// Accumulation.  A tile's 64 rows are consecutive nodes, so of the graphs they belong to only the first and the last can reach beyond
+// the tile; every graph between them lies inside it and has at most 62 nodes.  The first and the last graph get an LDS histogram each
+// (kHistSlots), filled with ds atomics and flushed at the end with one global integer atomic per non-zero (graph, bin); the graphs
+// between them add straight to hist, at most 62^2 candidates per workgroup in all.  A lane merges consecutive candidates of one
+// (graph, bin) in registers through the whole walk before it issues an atomic (run_*), which takes the same-address contention of a
+// peaked distribution out of the tile loop.  Integer adds only: exact, and the same bits whatever the order.
+// Counters.  One workgroup sees up to 64 (2^31 - 1) candidates, past 32 bits, and a periodic flush would put a barrier and a pass
+// over the slots into the tile loop; 64-bit LDS counters (ds_add_u64) cost 2 x 257 x 8 = 4112 B instead.  A lane's run counts at most
+// 16 candidates per tile over at most 2^25 tiles: int32.
+// LDS at H = 128: score tile 33,792 B + row tables 768 B + edges 2,048 B + counters 4,112 B = 40,720 B against 34,304 B of
+// k_pair_select: four workgroups (one wave per SIMD each) would still fit the 160 KB of a CU, 4 x 40,720 = 162,880 <= 163,840.  The
+// bound is the registers, as it is for k_pair_select: 154 - 162 VGPRs + 16 AGPRs at H = 128 give 2 waves per SIMD (two workgroups per
+// CU, 81 KB of LDS), 117 - 121 at H = 64 give 3 (24,336 B each), so the histogram costs no occupancy at any width.
+constexpr int kHistMaxEdges = 256;
+constexpr int kHistTable = 512;        // >= 2^p - 1 for every B <= kHistMaxEdges
+constexpr int kHistSlots = 2;          // the tile's first and last graph
+
+template <int H, bool SYM>
+__global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
+                                                        int G, int sigmoid, int skip_self, const float* edges, int B, int top,
+                                                        unsigned long long* hist) {
+    constexpr int LDT = PairCfg<H>::LDT;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], rgi[kPairTile];
+    __shared__ float el[kHistTable];
+    __shared__ unsigned long long lh[kHistSlots * (kHistMaxEdges + 1)];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    const int B1 = B + 1;
+    if (threadIdx.x < kPairTile) {
+        const int64_t u = u0 + threadIdx.x;
+        int64_t lo = 0, hi = 0;
+        int gi = 0;
+        if (u < N) {
+            if (gp == nullptr) { hi = N; }
+            else {
+                int a = 0, b = G;                          // first graph whose end lies behind u
+                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+                if (a < G) { lo = gp[a]; hi = gp[a + 1]; gi = a; }
+                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
+                hi = hi < lo ? lo : (hi > N ? N : hi);
+            }
+        }
+        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi; rgi[threadIdx.x] = gi;     // gi < max(G, 1): a row of hist
+    }
+    for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
+    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) lh[i] = 0ull;
+    __syncthreads();
+    int64_t clo = N, chi = 0;
+    for (int i = 0; i < kPairTile; ++i) {
+        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
+    }
+    const int64_t row0 = u0 + 16 * w;
+    const int64_t left = N - 1 - u0;                       // u0 < N: the tile's last row inside N
+    const int gfirst = rgi[0], glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
+    int mylo[4], myhi[4], mygi[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int lr = 16 * w + 4 * q + g;
+        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; mygi[g] = rgi[lr];
+    }
+    // the lane's run: run_n candidates of bin run_bin of graph run_gi that no atomic has seen yet
+    int run_gi = 0, run_bin = 0, run_n = 0;
+    auto flush = [&]() {
+        if (run_n > 0) {
+            if (run_gi == gfirst) atomicAdd(&lh[run_bin], (unsigned long long)run_n);
+            else if (run_gi == glast) atomicAdd(&lh[B1 + run_bin], (unsigned long long)run_n);
+            else atomicAdd(&hist[(int64_t)run_gi * B1 + run_bin], (unsigned long long)run_n);
+        }
+    };
+    float a[H / 4];
+    load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
+    if (clo < chi) {
+        int64_t ct0 = clo / kPairTile;
+        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
+        if constexpr (SYM) ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside t
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {                  // row by row: a run lasts as long as the row's scores stay in one bin
+                bool valid[4], any = false;
+                float rep[4];
+                int pos[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int64_t col = ct * kPairTile + 16 * c + r;
+                    const float v = acc[c][g];
+                    if constexpr (SYM) {
+                        valid[c] = col > row0 + 4 * q + g && col < myhi[g] && v == v;  // col > row >= the graph's start
+                        rep[c] = v;
+                    } else {
+                        valid[c] = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
+                        rep[c] = sigmoid ? sigmoidf_(v) : v;
+                    }
+                    any = any || valid[c];
+                    pos[c] = 0;
+                }
+                if (__ballot(any) == 0ull) continue;       // the wave has no candidate in these rows of this tile
+                for (int step = top; step > 0; step >>= 1) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (!valid[c]) continue;
+                    const int bin = pos[c] < B ? pos[c] : B;     // an ascending table never gives more; nothing else is indexed
+                    if (run_n > 0 && run_gi == mygi[g] && run_bin == bin) { ++run_n; continue; }
+                    flush();
+                    run_gi = mygi[g]; run_bin = bin; run_n = 1;
+                }
+            }
+        }
+    }
+    flush();
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) {
+        const unsigned long long n = lh[i];
+        if (n != 0ull) atomicAdd(&hist[(int64_t)(i < B1 ? gfirst : glast) * B1 + (i < B1 ? i : i - B1)], n);
+    }
+}
+
 // ---------------------------------------------------------------------------------- unit rows
 // y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
 // row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
@@ -693,4 +828,47 @@ extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const in
     MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_sim_union<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy, graph_ptr, G,
                                               threshold, parent, status));
     MGV_LAUNCH_RET();
+}
+
+// the two profile entries: checks in the order of the selection entries, then the table; *launch = false: hist is zero and nothing is left to do
+static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                         int skip_self, bool sym, const float* edges, int B, int64_t* hist, hipStream_t st) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(B >= 1 && B <= mgv::kHistMaxEdges && edges != nullptr && hist != nullptr);
+    bool launch;
+    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK) return rc;
+    // the table must ascend strictly and hold no NaN: it is read back, like the two ends of graph_ptr (one small blocking copy)
+    float e[mgv::kHistMaxEdges];
+    hipError_t err = hipMemcpyAsync(e, edges, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return (int)err;
+    MGV_CHECK_ARG(e[0] == e[0]);
+    for (int j = 1; j < B; ++j) MGV_CHECK_ARG(e[j] > e[j - 1]);           // false for a NaN on either side
+    const int64_t rows = G > 1 ? G : 1;
+    err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)rows * (size_t)(B + 1), st);
+    if (err != hipSuccess) return (int)err;
+    if (!launch) return MGV_OK;
+    int top = 1;                                                          // half the first power of two above B
+    while (2 * top <= B) top *= 2;
+    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
+    unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
+    if (sym) {
+        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_hist<HH, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
+                                                  graph_ptr, G, 0, 0, edges, B, top, h));
+    } else {
+        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_hist<HH, false>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
+                                                  graph_ptr, G, sigmoid, skip_self, edges, B, top, h));
+    }
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                             int skip_self, const float* edges, int B, int64_t* hist, void* stream) {
+    return pair_hist_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, false, edges, B, hist, (hipStream_t)stream);
+}
+
+extern "C" int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B,
+                            int64_t* hist, void* stream) {
+    return pair_hist_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, 0, true, edges, B, hist, (hipStream_t)stream);
 }

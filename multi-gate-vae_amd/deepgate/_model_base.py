@@ -146,6 +146,15 @@ class FunctionalModel(nn.Module):
             s, t = self._decoder_halves(hs)
             return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
+    def reconstruction_curve(self, hs, edge_index, graph_ptr, thresholds):
+        """int64 [G, B, 4] on the device: reconstruction_counts at every one of `thresholds` (strictly ascending, at most 256) — the
+        precision-recall curve of the decoder against the FULL adjacency from ONE all-pairs walk instead of one per threshold
+        (ops.reconstruction_curve: the score distribution of ops.pair_profile), entry for entry what reconstruction_counts gives at
+        each threshold.  Added functionality: the reference can only form the dense matrix (digae_layer.py:31-33)."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+
     def reconstruct_edges(self, hs, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None) on st = hs_decompose(hs): the graph the decoder
         reconstructs, every pair inside a graph with sigma > threshold, as (source, target) rows listed per source in ascending target
@@ -188,6 +197,25 @@ class FunctionalModel(nn.Module):
         a NaN; classes never cross graphs; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1, so threshold = 1.0 is unreliable
         and the default is 0.999.  Exact and the same bits from run to run: equal to ops.components of equivalence_candidates."""
         return ops.sim_classes(hf, graph_ptr=graph_ptr, threshold=threshold, min_size=min_size)
+
+    def similarity_profile(self, hf, thresholds, graph_ptr=None):
+        """int64 [G, B] on the device: per graph, the number of unordered gate pairs whose cosine of hf is > each of `thresholds`
+        (strictly ascending, at most 256) — what equivalence_candidates would list at each of them, as integers, from ONE walk
+        (ops.counts_above of ops.sim_profile).  Added functionality: the distribution behind the functional loss
+        1 - cosine_similarity(hf[a], hf[b], eps=1e-8) (trainer.py:158-160), by which a threshold is chosen instead of guessed.  Primary
+        inputs and other never-updated nodes have hf = 0: they score 0 with everything.  Equal rows score within (2H + 6) 2^-24 of
+        1, not exactly 1."""
+        return ops.counts_above(ops.sim_profile(hf, thresholds, graph_ptr=graph_ptr))
+
+    def equivalence_threshold(self, hf, max_pairs, graph_ptr=None, lo=0.0):
+        """{'threshold', 'pairs', 'lower', 'pairs_lower', 'tight'}: the lowest cosine threshold above `lo` at which
+        equivalence_candidates lists at most `max_pairs` pairs for the whole batch, and exactly `pairs` of them — "the 100,000 best
+        candidates of this design" (ops.sim_threshold_for: a few profile walks in place of a bisection of count walks).  When `lower`
+        is not None, equivalence_candidates(threshold=lower, max_pairs=max_pairs) is refused: pairs_lower > max_pairs.  Added
+        functionality (trainer.py:158-160).  Ties are the caller's to understand: equal gates share ONE cosine value, which a threshold
+        takes or leaves as a whole (5,000 equal gates are 12.5 M pairs), so `pairs` can lie far below max_pairs.  Rows with hf = 0
+        score 0 with everything; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1."""
+        return ops.sim_threshold_for(hf, max_pairs, graph_ptr=graph_ptr, lo=lo)
 
     def functional_similarity(self, hf, pair_index):
         """cos(hf[a], hf[b]) of the listed pairs [2, P]: 1 - this is the `dis` of the functional loss (trainer.py:158-160, eps = 1e-8 per

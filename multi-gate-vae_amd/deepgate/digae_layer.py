@@ -45,6 +45,11 @@ class DirectedInnerProductDecoder(nn.Module):
         return ops.pair_select(s, t, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self, by=by,
                                with_scores=with_scores, max_edges=max_edges)
 
+    def reconstruction_curve(self, s, t, edge_index, graph_ptr, thresholds):
+        """The confusion of `select` against the full adjacency at every one of `thresholds` from one walk (added functionality):
+        int64 [G, B, 4] of ops.reconstruction_curve — true positives, predicted positives, edges, ordered pairs per graph."""
+        return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+
 
 def _classes_once(x, classes, width):
     """Integer one-hot rows -> (rows, ids) once per encoder call (feature_classes runs a torch.unique with a host read-back); float

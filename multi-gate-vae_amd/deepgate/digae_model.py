@@ -31,6 +31,12 @@ class DirectedGAE(torch.nn.Module):
         with torch.no_grad():
             return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
+    def reconstruction_curve(self, s, t, edge_index, graph_ptr, thresholds):
+        """int64 [G, B, 4]: reconstruction_counts at every one of `thresholds` (strictly ascending, at most 256) from one all-pairs
+        walk (ops.reconstruction_curve).  Added functionality."""
+        with torch.no_grad():
+            return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+
     def reconstruct_edges(self, s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None): every pair inside a graph that the decoder calls an
         edge (score > threshold) as (source, target) rows, listed per source or (by='dst') per target (ops.reconstruct_edges).  Added

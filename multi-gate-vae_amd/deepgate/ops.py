@@ -1185,6 +1185,161 @@ def sim_at(x, pair_index, eps=1e-8):
 
 
 # ------------------------------------------------------------------------------------------------
+# the distribution of all-pair scores (added functionality: thresholds chosen by count; mgv_pair_hist / mgv_sim_hist)
+# ------------------------------------------------------------------------------------------------
+# The two facts above hold here too: zero rows score 0 with everything, equal rows score within (2H + 6) 2^-24 of 1.
+PROFILE_MAX_EDGES = 256
+
+
+def _profile_edges(edges, dev):
+    """The table as the launchers take it: float32 [B] on the device, converted ONCE — every count refers to these float32 values."""
+    e = torch.as_tensor(edges).detach().to(device=dev, dtype=F32).contiguous().flatten()
+    if not 1 <= e.numel() <= PROFILE_MAX_EDGES:
+        raise HipLibraryError('a profile takes 1 to %d edges (got %d)' % (PROFILE_MAX_EDGES, e.numel()))
+    return e
+
+
+def pair_profile(s, t, edges, graph_ptr=None, sigmoid=True, skip_self=False):
+    """int64 [G, B + 1] on the device (G = 1 without graph_ptr): per graph, the candidates of pair_select — v in u's graph, without v = u
+    when skip_self, sigmoid or raw score — binned by the number of `edges` (float32, strictly ascending, 1 <= B <= 256) their score is
+    > than: bin 0 holds score <= edges[0], bin B score > edges[-1]; a NaN score is in no bin.  ONE all-pairs walk for the whole table
+    (mgv_pair_hist), the decisions the bits of pair_select's: counts_above(profile)[g, j] is the number of links pair_select would
+    list for graph g at threshold edges[j].  Integer atomics: exact and the same from call to call.  No grad."""
+    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
+        _sim_width(s, 'pair_profile')
+    with torch.no_grad():
+        sd, lds, td, ldt, H = _pair_operands(s, t)
+        N = sd.shape[0]
+        if td.shape[0] != N:
+            raise HipLibraryError('pair_profile bins the pairs of one batch: s and t need the same number of rows (got %d and %d)'
+                                  % (N, td.shape[0]))
+        dev = sd.device
+        e = _profile_edges(edges, dev)
+        gp, G = _sim_graphs(graph_ptr, dev)
+        hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=dev)
+        _hip.call('mgv_pair_hist', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), int(bool(skip_self)), ptr(e), e.numel(),
+                  ptr(hist))
+        return hist if gp is None else hist[:G]
+
+
+def _unit_profile(y, e, graph_ptr):
+    """mgv_sim_hist on unit rows y and a device table e -> int64 [G, B + 1]."""
+    N, H = y.shape
+    gp, G = _sim_graphs(graph_ptr, y.device)
+    hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=y.device)
+    _hip.call('mgv_sim_hist', H, N, ptr(y), H, ptr(gp), G, ptr(e), e.numel(), ptr(hist))
+    return hist if gp is None else hist[:G]
+
+
+def sim_profile(x, edges, graph_ptr=None, eps=1e-8):
+    """int64 [G, B + 1]: pair_profile's bins for the cosine of sim_pairs — unit rows (row_unit), every unordered pair of one graph once
+    (v > u), half the tiles (mgv_sim_hist).  counts_above(profile)[g, j] is the number of pairs sim_pairs lists for graph g at
+    threshold edges[j], as integers.  Zero rows (primary inputs) score 0 with everything; equal rows score within (2H + 6) 2^-24 of
+    1, not exactly 1."""
+    _sim_width(x, 'sim_profile')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        return _unit_profile(y, _profile_edges(edges, y.device), graph_ptr)
+
+
+def counts_above(profile):
+    """int64 [G, B]: pairs above each edge — the reverse cumulative sum of a profile without its bin 0."""
+    with torch.no_grad():
+        return profile[:, 1:].flip(1).cumsum(1).flip(1)
+
+
+def reconstruction_curve(s, t, edge_index, graph_ptr, thresholds):
+    """int64 [G, B, 4] on the device: reconstruction_counts at every threshold of `thresholds` (strictly ascending), entry for entry
+    equal to torch.stack([reconstruction_counts(s, t, edge_index, graph_ptr, thr) for thr in thresholds], 1), from ONE all-pairs walk:
+    the predicted positives are counts_above of pair_profile, the true positives pair_scores_at over the edges, binned by the same
+    float32 table (bucketize: the number of thresholds the score is > than) and added per source graph.  Integer sums throughout."""
+    with torch.no_grad():
+        dev = s.device
+        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64)
+        G = gp.numel() - 1
+        e = _profile_edges(thresholds, dev)
+        B = e.numel()
+        src, dst = _edge_rows(edge_index)
+        pp = counts_above(pair_profile(s, t, e, graph_ptr=gp, sigmoid=True, skip_self=False))
+        if G <= 0:
+            return torch.zeros((0, B, 4), dtype=torch.int64, device=dev)
+        rep = pair_scores_at(s, t, edge_index, sigmoid=True)
+        k = torch.bucketize(rep, e, right=False)                       # #{j : rep > e[j]}
+        ok = ~torch.isnan(rep)                                         # a NaN passes no threshold (bucketize would put it behind all)
+        gid = torch.bucketize(src, gp[1:].contiguous(), right=True).clamp_(max=G - 1)
+        tbin = torch.zeros(G * (B + 1), dtype=torch.int64, device=dev).index_add_(0, gid * (B + 1) + k, ok.to(torch.int64))
+        tp = counts_above(tbin.view(G, B + 1))
+        edges = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, torch.ones_like(gid))
+        n = gp[1:] - gp[:-1]
+        return torch.stack([tp, pp, edges[:, None].expand(G, B), (n * n)[:, None].expand(G, B)], dim=2)
+
+
+def _f32(v):
+    return float(torch.tensor(float(v), dtype=F32))
+
+
+def _f32_key(v):
+    """The place of float32(v) in the order of all float32 values, as an integer: adjacent floats differ by 1, -0.0 and 0.0 are both 0."""
+    bits = int(torch.tensor(float(v), dtype=F32).view(I32))
+    return bits if bits >= 0 else -(bits & 0x7fffffff)
+
+
+def _edges_between(lo, hi, bins):
+    """min(bins, all) distinct float32 values across [lo, hi], both ends included, ascending, evenly spaced in the ORDER of the float32
+    values (linear inside a binade, geometric across binades): a bracket of at most 2^32 floats shrinks by bins - 1 per round, so six
+    rounds of 64 edges reach adjacent floats from any start."""
+    a, b = _f32_key(lo), _f32_key(hi)
+    n = max(min(int(bins), b - a + 1), 1)
+    ks = a + (torch.arange(n, dtype=torch.int64) * (b - a)) // max(n - 1, 1)
+    return torch.where(ks >= 0, ks, -ks - (1 << 31)).to(I32).view(F32)
+
+
+def threshold_search(profile_fn, max_pairs, lo=0.0, hi=2.0, bins=64, max_rounds=6):
+    """The bracket logic of sim_threshold_for on any walk: profile_fn(edges float32 [B], ascending) -> int64 [G, B + 1].  The bracket
+    (lower, threshold] always has count(lower) > max_pairs >= count(threshold) with both counts taken from a walk; count(hi) must
+    be 0 <= max_pairs for the caller's `hi`.  -> the dict of sim_threshold_for."""
+    max_pairs = int(max_pairs)
+    if max_pairs < 0:
+        raise HipLibraryError('max_pairs must be >= 0 (got %d)' % max_pairs)
+    bins = min(max(int(bins), 3), PROFILE_MAX_EDGES)
+    lower, upper, pairs_lower, pairs, tight = _f32(lo), _f32(hi), None, None, False
+    if not lower < upper:
+        raise HipLibraryError('the search needs lo < %g (got %g)' % (upper, lower))
+    for rnd in range(max(int(max_rounds), 1)):
+        e = _edges_between(lower, upper, bins)
+        above = counts_above(profile_fn(e)).sum(0).tolist()           # the round's ONE read-back: batch-wide pairs above each edge
+        ev = e.tolist()
+        j = next((i for i, n in enumerate(above) if n <= max_pairs), None)      # the count falls along the table
+        if j is None:
+            raise HipLibraryError('%d pairs are above %g, the upper end of the search: more than max_pairs = %d' % (above[-1], ev[-1], max_pairs))
+        if j == 0:                                                     # only in the first round: the count at lo already fits
+            return {'threshold': ev[0], 'pairs': above[0], 'lower': None, 'pairs_lower': None, 'tight': True}
+        lower, pairs_lower, upper, pairs = ev[j - 1], above[j - 1], ev[j], above[j]
+        tight = _f32_key(upper) - _f32_key(lower) <= 1                 # no float32 strictly between the two ends
+        if tight:
+            break
+    return {'threshold': upper, 'pairs': pairs, 'lower': lower, 'pairs_lower': pairs_lower, 'tight': tight}
+
+
+def sim_threshold_for(x, max_pairs, graph_ptr=None, lo=0.0, bins=64, max_rounds=6, eps=1e-8):
+    """The lowest cosine threshold whose batch-wide pair count fits `max_pairs`, from the distribution instead of trial walks:
+    {'threshold' (a Python float holding a float32 value), 'pairs', 'lower', 'pairs_lower', 'tight'}.  pairs <= max_pairs and pairs is
+    the total sim_pairs lists at `threshold`; when `lower` is not None it is the bracket's other end, lower < threshold with
+    pairs_lower > max_pairs.  The bracket starts as (lo, 2.0] — no cosine exceeds 1 + (2H + 6) 2^-24, so nothing is above 2.0 — and
+    each round puts `bins` distinct float32 edges across it, both ends included, takes ONE sim_profile walk and ONE read-back, and
+    keeps the adjacent pair of edges between which the count crosses max_pairs; it stops when no float32 lies strictly between the
+    two ends (tight) or after max_rounds.  If the count at `lo` already fits, the result is lo with lower = None.
+    Ties are the caller's to understand: 5,000 equal gates are 12.5 M pairs at ONE cosine value, which a threshold takes or leaves
+    as a whole, so the tight answer can lie far below max_pairs.  Zero rows score 0 with everything and never pass a threshold
+    >= 0; equal rows score within (2H + 6) 2^-24 of 1."""
+    _sim_width(x, 'sim_threshold_for')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        return threshold_search(lambda e: _unit_profile(y, _profile_edges(e, y.device), graph_ptr), max_pairs, lo=lo, hi=2.0, bins=bins,
+                                max_rounds=max_rounds)
+
+
+# ------------------------------------------------------------------------------------------------
 # connected components and candidate classes (added functionality: csrc/components.hip, csrc/mgv_unionfind.h)
 # ------------------------------------------------------------------------------------------------
 _CC_ERR = {1: 'an entry of the forest outside [0, x] (parent was not initialised)', 2: 'a union-find loop reached its cap of 2^20 rounds',

@@ -9,6 +9,9 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --reconstruct 0.5   # + the decoded edge list of every graph
     python examples/feature_extract.py --type aig --synthetic 4 --similar 8         # + every gate's 8 functionally closest gates
     python examples/feature_extract.py --type aig --synthetic 4 --equivalences 0.999   # + the gate pairs with cos(hf) above 0.999
+    python examples/feature_extract.py --type aig --synthetic 4 --equivalences_max 1000   # the same, at most 1000 pairs per batch
+    python examples/feature_extract.py --type aig --synthetic 4 --similarity_profile 12   # + pairs per graph above 1 - 2^-j, j = 1..12
+    python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
 """
 import argparse
 import os
@@ -54,7 +57,22 @@ def main(argv=None):
                     'id of a gate\'s class; name/eq_class_ptr [C + 1] and name/eq_members [M], the classes with at least two gates, '
                     'members ascending, local ids; Model.equivalence_classes).  Single linkage: two gates of one class can have a '
                     'cosine below THR.  Primary inputs (hf = 0) are always singletons; use 0.999 rather than 1.0')
+    ap.add_argument('--equivalences_max', type=int, default=None, metavar='P', help='choose the threshold of --equivalences by count: the '
+                    'lowest one (not below --equivalences when that is given too, else 0) at which a batch lists at most P pairs '
+                    '(Model.equivalence_threshold), then store the pairs as --equivalences does and the threshold used '
+                    '(name/eq_threshold).  Equal gates share one cosine, which a threshold takes or leaves as a whole: fewer than P pairs '
+                    'can come back')
+    ap.add_argument('--similarity_profile', type=int, default=0, metavar='B', help='also store, per graph, the number of gate pairs whose '
+                    'hf have a cosine above 1 - 2^-j, j = 1 .. B (B capped at 20): name/sim_thresholds [B] and name/sim_counts_above [B] '
+                    '(Model.similarity_profile, one walk for all B).  Primary inputs (hf = 0) score 0; equal rows score within '
+                    '(2H + 6) 2^-24 of 1')
+    ap.add_argument('--recon_curve', type=int, default=0, metavar='B', help='also store the decoder\'s confusion against the FULL '
+                    'adjacency at B evenly spaced thresholds in (0, 1), i / (B + 1): name/recon_thresholds [B] and name/recon_curve '
+                    '[B, 4] = true positives, predicted positives, edges, ordered pairs (Model.reconstruction_curve, one walk; '
+                    '1 <= B <= 256)')
     a = ap.parse_args(argv)
+    sim_thr = [1.0 - 2.0 ** -j for j in range(1, min(a.similarity_profile, 20) + 1)]
+    rc_thr = [float(np.float32(i / (a.recon_curve + 1.0))) for i in range(1, a.recon_curve + 1)]
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
                                                      enable_reverse=True, layernorm=True)
@@ -88,8 +106,16 @@ def main(argv=None):
             if a.similar:
                 sim_idx, sim_cos, _ = model.similar_gates(hf, a.similar, graph_ptr=batch.graph_ptr)
                 sim_idx, sim_cos = sim_idx.cpu().numpy(), sim_cos.cpu().numpy()
-            if a.equivalences is not None:
-                eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=a.equivalences, with_scores=True)
+            eq_thr = a.equivalences
+            if a.equivalences_max is not None:
+                eq_thr = model.equivalence_threshold(hf, a.equivalences_max, graph_ptr=batch.graph_ptr,
+                                                     lo=0.0 if a.equivalences is None else a.equivalences)['threshold']
+            if sim_thr:
+                sim_above = model.similarity_profile(hf, sim_thr, graph_ptr=batch.graph_ptr).cpu().numpy()
+            if rc_thr:
+                curve = model.reconstruction_curve(hs, batch.edge_index, batch.graph_ptr, rc_thr).cpu().numpy()
+            if eq_thr is not None:
+                eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=eq_thr, with_scores=True)
                 eq, eq_cos = eq.cpu().numpy(), eq_cos.cpu().numpy()
                 qptr = eq_ptr[batch.graph_ptr.to(eq_ptr.device).long()].tolist()               # the graphs' places in the list
             if a.classes is not None:
@@ -108,10 +134,19 @@ def main(argv=None):
                     loc = sim_idx[ptr[k]:ptr[k + 1]]
                     out[name + '/sim_idx'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
                     out[name + '/sim_cos'] = sim_cos[ptr[k]:ptr[k + 1]]
-                if a.equivalences is not None:
+                if eq_thr is not None:
                     out[name + '/eq_pairs'] = (eq[:, qptr[k]:qptr[k + 1]] - ptr[k]).astype(np.int32)
                     out[name + '/eq_cos'] = eq_cos[qptr[k]:qptr[k + 1]]
-                    print('[INFO] %s: %d gate pairs with cos(hf) > %g' % (name, qptr[k + 1] - qptr[k], a.equivalences))
+                    print('[INFO] %s: %d gate pairs with cos(hf) > %s' % (name, qptr[k + 1] - qptr[k],
+                                                                         ('%g' if a.equivalences_max is None else '%.9g') % eq_thr))
+                if a.equivalences_max is not None:
+                    out[name + '/eq_threshold'] = np.float32(eq_thr)
+                if sim_thr:
+                    out[name + '/sim_thresholds'] = np.asarray(sim_thr, dtype=np.float32)
+                    out[name + '/sim_counts_above'] = sim_above[k]
+                if rc_thr:
+                    out[name + '/recon_thresholds'] = np.asarray(rc_thr, dtype=np.float32)
+                    out[name + '/recon_curve'] = curve[k]
                 if a.reconstruct is not None:
                     out[name + '/rec_edge_index'] = (rec_ei[:, eptr[k]:eptr[k + 1]] - ptr[k]).astype(np.int32)
                     out[name + '/rec_precision'] = np.float64(rc[k, 0] / max(float(rc[k, 1]), 1.0))
