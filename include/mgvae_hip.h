@@ -169,6 +169,16 @@ int mgv_linear_wgrad_x3_ws_floats(int M, int K, int64_t N);
 int mgv_linear_wgrad_x3(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                         const float* dY, int lddy, int M, float* dW, float* db, float* workspace, int64_t workspace_floats,
                         void* stream);
+/* The whole backward of one Linear in ONE pass over dY: dW and db as mgv_linear_wgrad_x3 (same arguments, same workspace size, same
+ * bits), and the input gradients dX1[N][K1] = dY W[:, :K1] (+ R, nullable, [N][ldr >= K1]: a second consumer's gradient),
+ * dX2[N][K2] = dY W[:, K1:] — bit for bit what mgv_linear_fwd_x3(_res) gives on the transposed packs of the two column blocks.
+ * wtpack_bf16 = mgv_wpack_bf16x3(W, K1+K2, M, ldw, transpose = 1): the [K x M] view of the whole W.  X2, K2 = 0 and dX2 are NULL / 0
+ * together; dX1 is required.  (M, K1+K2) in {(64,128), (128,64), (64,64)} (mgv_linear_bwd_x3_supported), any other shape returns
+ * MGV_EUNSUPPORTED; N = 0 returns MGV_OK; both launch nothing. */
+int mgv_linear_bwd_x3_supported(int M, int K);
+int mgv_linear_bwd_x3(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2, const float* dY, int lddy,
+                      int M, const void* wtpack_bf16, float* dW, float* db, float* dX1, int ldx1, float* dX2, int ldx2,
+                      const float* R, int ldr, float* workspace, int64_t workspace_floats, void* stream);
 /* agg[i] = sum_{j in nbr(i)} h[j] added in list order, deg[i] = |nbr(i)| (deg may be NULL): the scatter-add half of
  * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34).  H in {16, 32, 64, 128} here and in the three
  * row-sum entries below; any other H (0 and other non-multiples of 4 included) returns MGV_EUNSUPPORTED before anything is computed. */

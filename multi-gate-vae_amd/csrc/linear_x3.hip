@@ -3,7 +3,8 @@
 // kernels of dense.hip price these streaming layers at the fp32-MFMA rate (K=128, M=64: 69 GFLOP per pass);
 // here they are HBM-bound: rows are split into bf16 hi/lo planes in LDS once, the forward keeps its weight
 // fragments in registers for the whole launch, the weight gradient reads both operands transposed from the
-// row-major planes, and the next tile's rows are in flight (registers) while the current tile is multiplied.
+// row-major planes, and the next tile's rows are in flight (registers) while the current tile is multiplied.  The whole backward
+// of a layer (k_linear_bwd_x3) is the weight-gradient kernel with the input gradient formed from the dY planes it already holds.
 #include "mgv_x3.h"
 #include "mgv_slab.h"
 #include "../../include/mgvae_hip.h"
@@ -18,6 +19,7 @@ struct LinX3Args {
     const float* b;
     float* Y; int ldy;
     const float* R; int ldr;     // optional residual rows added to Y on the way out
+    float* Y2; int ldy2;         // fused backward: dX1 -> Y (its residual R), dX2 -> Y2; wpack = the transposed pack of the whole W
     const float* dY; int lddy;
     float* dW; float* db;
     float* slab;            // weight gradient: [gridDim][M*K + M] per-workgroup partials (dW row-major, then db)
@@ -176,8 +178,24 @@ struct LinWgGeom {
     static constexpr int smem_bytes = o_db + M * 4;
 };
 
-template <int M, int K, int NW, int WI, bool GROUPED = false>
-__global__ __launch_bounds__(64 * NW) void k_linear_wgrad_x3(LinX3Args a) {
+// The input gradient of the same tile, dX[64][K] = dY[64][M] W (fused backward): the forward kernel's product with the dY planes as
+// its row-major operand, 4 row tiles x K/16 column tiles over the NW waves, one column tile per wave.
+template <int M, int K, int NW>
+struct LinDxGeom {
+    static constexpr int KS = M / 32;
+    static constexpr int WPC = K / 16, WPR = NW / WPC, RTW = 4 / WPR;
+    static_assert(WPC * WPR == NW && RTW * WPR == 4, "one column tile per wave, the row tiles split over the rest");
+    static constexpr int LDY = K + 4;                         // fp32 staging row, over the X planes
+    static_assert(kTileRows * LDY * 4 <= 2 * kTileRows * (K + 8) * 2, "the staged tile must fit the X planes");
+    static constexpr int PF = kTileRows * K / 4 / (64 * NW);  // float4 per thread in the store phase
+    static_assert(PF * 64 * NW * 4 == kTileRows * K, "the output tile must split over the threads");
+};
+
+// DX: also the input gradient (k_linear_bwd_x3).
+// KSR: the transposed weight fragments of k-steps < KSR live in registers for the whole launch, those of the other k-steps in LDS
+// behind s_db (M = 128: four k-steps of both planes are 32 registers, which the 128 of two workgroups per CU do not leave).
+template <int M, int K, int NW, int WI, bool GROUPED, bool DX, int KSR>
+__device__ __forceinline__ void linear_wgrad_x3_body(const LinX3Args& a) {
     using G = LinWgGeom<M, K, NW, WI>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __bf16* g_hi = reinterpret_cast<__bf16*>(smem_raw);
@@ -221,6 +239,24 @@ __global__ __launch_bounds__(64 * NW) void k_linear_wgrad_x3(LinX3Args a) {
             else px[u] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
+    // fused backward: this wave's column tile of W^T, hi and lo (without DX the geometry is a placeholder that satisfies its asserts)
+    using D = LinDxGeom<DX ? M : 32, DX ? K : 16 * NW, NW>;
+    const int dwc = w % D::WPC, dwr = w / D::WPC;
+    bf16x8 th[KSR > 0 ? KSR : 1], tl[KSR > 0 ? KSR : 1];
+    constexpr int KSL = DX ? D::KS - KSR : 0, WTL = (K / 16) * KSL * 512;      // k-steps and elements per plane in LDS
+    __bf16* s_wt = reinterpret_cast<__bf16*>(smem_raw + G::smem_bytes);
+    auto wt_lds = [&](int plane, int ks) { return ldfrag(s_wt + plane * WTL + (dwc * KSL + ks - KSR) * 512 + lane * 8); };
+    if constexpr (DX) {
+#pragma unroll
+        for (int ks = 0; ks < KSR; ++ks) {
+            const int wo = (dwc * D::KS + ks) * 512 + lane * 8;
+            th[ks] = ldfrag(a.wpack + wo); tl[ks] = ldfrag(a.wpack + M * K + wo);
+        }
+        if constexpr (KSL > 0) for (int c = tid; c < 2 * WTL / 8; c += G::NT) {         // (the first tile barrier publishes it)
+            const int plane = c / (WTL / 8), blk = (c % (WTL / 8)) / 64, ct = blk / KSL, ks = KSR + blk % KSL;
+            *reinterpret_cast<bf16x8*>(s_wt + c * 8) = ldfrag(a.wpack + plane * M * K + (ct * D::KS + ks) * 512 + (c % 64) * 8);
+        }
+    }
     int64_t tile = blockIdx.x;
     if (tile < ntiles) prefetch(tile);
     for (; tile < ntiles; tile += gridDim.x) {
@@ -264,6 +300,44 @@ __global__ __launch_bounds__(64 * NW) void k_linear_wgrad_x3(LinX3Args a) {
             }
         }
         lds_barrier();
+        if constexpr (DX) {
+            // dX = dY W as k_linear_fwd_x3 forms it (ks ascending, mma_x3, zero-initialised accumulators: the same bits), from the dY
+            // planes still in LDS; the fp32 tile is staged over the X planes, which nobody reads after the barrier above
+            float* s_y = reinterpret_cast<float*>(smem_raw + 2 * G::GPB);
+            const int64_t first = tile * kTileRows;
+            f32x4 dacc[D::RTW];
+#pragma unroll
+            for (int i = 0; i < D::RTW; ++i) dacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < D::KS; ++ks)
+#pragma unroll
+                for (int i = 0; i < D::RTW; ++i) {
+                    const int off = ((dwr * D::RTW + i) * 16 + r) * G::LDG + 32 * ks + 8 * q;
+                    const bf16x8 gh = ldfrag(g_hi + off), gl = ldfrag(g_lo + off);
+                    if (ks < KSR) mma_x3(dacc[i], gh, gl, th[ks], tl[ks]);
+                    else mma_x3(dacc[i], gh, gl, wt_lds(0, ks), wt_lds(1, ks));
+                }
+#pragma unroll
+            for (int i = 0; i < D::RTW; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s_y[((dwr * D::RTW + i) * 16 + q * 4 + e) * D::LDY + dwc * 16 + r] = dacc[i][e] + 0.f;   // (the forward's absent bias)
+            lds_barrier();
+#pragma unroll
+            for (int u = 0; u < D::PF; ++u) {
+                const int f = tid + u * G::NT;
+                const int row = f / (K / 4), c4 = (f % (K / 4)) * 4;
+                if (first + row < a.N) {
+                    float4 v = ld4(s_y + row * D::LDY + c4);
+                    if (c4 < a.K1) {
+                        if (a.R) v = add4(v, ld4(a.R + (first + row) * a.ldr + c4));
+                        st4(a.Y + (first + row) * a.ldy + c4, v);
+                    } else {
+                        st4(a.Y2 + (first + row) * a.ldy2 + (c4 - a.K1), v);
+                    }
+                }
+            }
+            lds_barrier();      // the next tile's X planes overwrite the staged rows
+        }
     }
     // per-workgroup partials to this workgroup's slab row (plain stores); k_slab_sum adds the rows in a fixed order
     float* slab = a.slab + (int64_t)blockIdx.x * (M * K + M);
@@ -287,6 +361,17 @@ __global__ __launch_bounds__(64 * NW) void k_linear_wgrad_x3(LinX3Args a) {
             slab[M * K + tid] = sum;
         }
     }
+}
+
+template <int M, int K, int NW, int WI, bool GROUPED = false>
+__global__ __launch_bounds__(64 * NW) void k_linear_wgrad_x3(LinX3Args a) {
+    linear_wgrad_x3_body<M, K, NW, WI, GROUPED, false, 0>(a);
+}
+
+// dW, db as k_linear_wgrad_x3 (same grid, tile walk and slab rows) and dX1 | dX2 = dY W (+ R) in the same pass over dY
+template <int M, int K, int NW, int WI, int KSR>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void k_linear_bwd_x3(LinX3Args a) {
+    linear_wgrad_x3_body<M, K, NW, WI, false, true, KSR>(a);
 }
 
 // fp32 matrix -> bf16 hi/lo planes in MFMA fragment order: block (row tile, k-step) = 512 elements, lane 16q+r holds
@@ -328,6 +413,26 @@ int launch_linear_wgrad_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st
     const int grid = grid_for(ntiles, per_cu);
     if (a.slab == nullptr || ws_floats < (int64_t)grid * (M * K + M)) return MGV_EINVAL;
     hipLaunchKernelGGL((k_linear_wgrad_x3<M, K, NW, WI, GROUPED>), dim3(grid), dim3(G::NT), G::smem_bytes, st, a);
+    launch_slab_sum<float, float>(a.slab, grid, M * K + M, M * K, a.dW, st);
+    if (a.db) launch_slab_sum<float, float>(a.slab + M * K, grid, M * K + M, M, a.db, st);
+    MGV_LAUNCH_RET();
+}
+
+// the weight-gradient launch of the same shape with the input-gradient phase in its kernel: same grid, same slab rows, same sums
+template <int M, int K, int NW, int WI, int KSR>
+int launch_linear_bwd_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st) {
+    using G = LinWgGeom<M, K, NW, WI>;
+    static bool set = false;
+    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_bwd_x3<M, K, NW, WI, KSR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
+    int per_cu = 160 * 1024 / G::smem_bytes;
+    const int cap = 1024 / G::NT;
+    per_cu = per_cu > cap ? cap : per_cu;
+    const int grid = grid_for(ntiles, per_cu);
+    if (a.slab == nullptr || ws_floats < (int64_t)grid * (M * K + M)) return MGV_EINVAL;
+    constexpr int smem = G::smem_bytes + 2 * (K / 16) * (M / 32 - KSR) * 512 * 2;
+    static_assert(2 * smem <= 160 * 1024, "two workgroups per CU, as the weight-gradient kernel runs");
+    hipLaunchKernelGGL((k_linear_bwd_x3<M, K, NW, WI, KSR>), dim3(grid), dim3(G::NT), smem, st, a);
     launch_slab_sum<float, float>(a.slab, grid, M * K + M, M * K, a.dW, st);
     if (a.db) launch_slab_sum<float, float>(a.slab + M * K, grid, M * K + M, M, a.db, st);
     MGV_LAUNCH_RET();
@@ -390,6 +495,26 @@ extern "C" int mgv_linear_wgrad_x3(int64_t N, const float* X1, int K1, int ld1, 
     MGV_WGX(64, 128, 8, 2) MGV_WGX(128, 64, 8, 4) MGV_WGX(64, 64, 8, 2) MGV_WGX(64, 32, 8, 4) MGV_WGX(32, 64, 8, 2) MGV_WGX(32, 32, 4, 2)
 #undef MGV_WGX
     return MGV_EUNSUPPORTED;
+}
+
+extern "C" int mgv_linear_bwd_x3_supported(int M, int K) { return (M == 64 && K == 128) || (M == 128 && K == 64) || (M == 64 && K == 64); }
+
+extern "C" int mgv_linear_bwd_x3(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2, const float* dY, int lddy,
+                                 int M, const void* wtpack_bf16, float* dW, float* db, float* dX1, int ldx1, float* dX2, int ldx2,
+                                 const float* R, int ldr, float* workspace, int64_t workspace_floats, void* stream) {
+    if (!mgv_linear_bwd_x3_supported(M, K1 + K2)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(N >= 0 && X1 && dY && dW && wtpack_bf16 && dX1 && K1 > 0 && K2 >= 0 && (K2 == 0) == (X2 == nullptr) && (X2 == nullptr) == (dX2 == nullptr));
+    MGV_CHECK_ARG(K1 % 4 == 0 && K2 % 4 == 0 && ld1 >= K1 && ld1 % 4 == 0 && (K2 == 0 || (ld2 >= K2 && ld2 % 4 == 0)) && lddy % 4 == 0 && lddy >= M);
+    MGV_CHECK_ARG(ldx1 >= K1 && ldx1 % 4 == 0 && (K2 == 0 || (ldx2 >= K2 && ldx2 % 4 == 0)) && (R == nullptr || (ldr >= K1 && ldr % 4 == 0)));
+    if (N == 0) return MGV_OK;
+    mgv::LinX3Args a{};
+    a.N = N; a.X1 = X1; a.K1 = K1; a.ld1 = ld1; a.X2 = X2; a.K2 = K2; a.ld2 = ld2; a.dY = dY; a.lddy = lddy; a.dW = dW; a.db = db; a.slab = workspace;
+    a.wpack = static_cast<const __bf16*>(wtpack_bf16); a.Y = dX1; a.ldy = ldx1; a.Y2 = dX2; a.ldy2 = ldx2; a.R = R; a.ldr = ldr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int K = K1 + K2;
+    if (M == 64 && K == 128) return mgv::launch_linear_bwd_x3<64, 128, 8, 2, 2>(a, workspace_floats, st);
+    if (M == 128 && K == 64) return mgv::launch_linear_bwd_x3<128, 64, 8, 4, 1>(a, workspace_floats, st);
+    return mgv::launch_linear_bwd_x3<64, 64, 8, 2, 2>(a, workspace_floats, st);
 }
 
 extern "C" int mgv_wpack_bf16x3(const float* W, int R, int K, int ldw, int transpose, void* hi, void* lo, void* stream) {

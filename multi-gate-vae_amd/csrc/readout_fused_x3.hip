@@ -7,7 +7,8 @@
 //             F3  y2 -> a2 -> prob
 //   backward: B1  y2, dprob -> head gradients, BN2 sums
 //             B2  y1, y2, dprob -> BN1 sums                   (dy2 recomputed; dA1 = dy2 W2)
-//             B3  hf, y1, y2, dprob -> dW1, db1, dW2, db2, dhf = dy1 W1
+//             B3w y1, y2, dprob -> dW2, db2                   (on the <32, 32> weight-gradient grid)
+//             B3  hf, y1, y2, dprob -> dW1, db1, dhf = dy1 W1
 // The products are the bf16x3 ones of linear_x3.hip on the same fragment layout (F1 / F2 give y1 / y2 bit for bit as the
 // per-layer kernels do); every cross-workgroup sum goes through a per-workgroup slab row added in a fixed order (mgv_slab.h).
 #include "mgv_x3.h"
@@ -32,7 +33,7 @@ constexpr int g_w1 = 0, g_b1 = C * D, g_g1 = g_b1 + C, g_be1 = g_g1 + C, g_w2 = 
 constexpr int s_f = 2 * C;                             // F1, F2: sum y, sum y^2
 constexpr int s_b1 = 3 * C + 1;                        // B1: dw3, db3, sum dz2, sum dz2 xhat2
 constexpr int s_b2 = 2 * C;                            // B2: sum dz1, sum dz1 xhat1
-// B3: fp32 rows as k_linear_wgrad_x3 leaves them: dW1 + db1 per workgroup, dW2 + db2 per workgroup of the <32, 32> grid
+// B3 / B3w: fp32 rows as k_linear_wgrad_x3 leaves them: dW1 + db1 per workgroup of B3, dW2 + db2 per workgroup of B3w
 constexpr int s_b3 = C * D + C, s_b3w2 = C * C + C;
 
 // Y[64][M] (+)= X[64][K] W^T + b from bf16 hi/lo planes, exactly as k_linear_fwd_x3 forms it (same wave split, same MFMA order)
@@ -491,17 +492,15 @@ __device__ __forceinline__ void wgrad_colsum(const float4* s_part, int nthreads,
     }
 }
 
-// B3: dy1 = bn1'(dz1), dhf = dy1 W1, and the weight gradients as the per-layer weight-gradient launches form them: dW1, db1 as
-// k_linear_wgrad_x3<32, 64> (this grid, min(tiles, 512); db1 from 512 threads, one row each per tile), dW2, db2 as
-// k_linear_wgrad_x3<32, 32> (grid G2 = min(tiles, 1024), 256 threads, rows r and r + 32): with this grid the tiles of workgroup b
-// belong alternately to its workgroups b and b + 512.  The MFMA partial of an output tile is the same chain of mma_x3 over the
-// same tiles whichever wave holds it, and the workgroup rows are added in fp32 by the same k_slab_sum.
+// B3: dy1 = bn1'(dz1), dhf = dy1 W1, and dW1, db1 as the per-layer weight-gradient launch forms them: k_linear_wgrad_x3<32, 64>
+// (this grid, min(tiles, 512); db1 from 512 threads, one row each per tile).  The MFMA partial of an output tile is the same chain
+// of mma_x3 over the same tiles whichever wave holds it, and the workgroup rows are added in fp32 by the same k_slab_sum.
 __global__ __launch_bounds__(kThreads) void k_ro_b3(int64_t N, const float* HF, const float* Y1, const float* Y2, const float* dprob,
                                                     const float* stats, const float* g1, const float* be1, const float* g2, const float* be2,
                                                     float p1, float p2, uint64_t seed1, uint64_t seed2, const float* w3, const float* b3,
                                                     int clamp01, const double* sums1, const double* sums2, const __bf16* w2t, const __bf16* w1t,
-                                                    float* dHF, float* slab1, float* slab2, int g2n) {
-    __shared__ __attribute__((aligned(16))) __bf16 x_hi[PD], x_lo[PD], g_hi[PC], g_lo[PC], a_hi[PC], a_lo[PC];
+                                                    float* dHF, float* slab1) {
+    __shared__ __attribute__((aligned(16))) __bf16 x_hi[PD], x_lo[PD], g_hi[PC], g_lo[PC];
     __shared__ __attribute__((aligned(16))) float s_o[kTileRows * LSD];     // dA1 [64][LSC], then dhf [64][LSD]; column-sum partials at the end
     const int tid = threadIdx.x, c4 = (tid % (C / 4)) * 4;
     BnQuad q1, q2;
@@ -518,13 +517,10 @@ __global__ __launch_bounds__(kThreads) void k_ro_b3(int64_t N, const float* HF, 
     mm1.load(w1t, nullptr);
     MmWgrad<C, D> wg;
     wg.zero();
-    MmWgrad<C, C> wg2[2];
-    wg2[0].zero(); wg2[1].zero();
     constexpr int U = kTileRows * C / 4 / kThreads, UX = kTileRows * D / 4 / kThreads;
-    float db1[U][4] = {}, db2[2][4] = {};                 // db1[u]: the 512-thread launch's thread tid + 256 u; db2[set]
+    float db1[U][4] = {};                                 // db1[u]: the 512-thread launch's thread tid + 256 u
     const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
-    for (int64_t tile = blockIdx.x, k = 0; tile < ntiles; tile += gridDim.x, ++k) {
-        const int set = (int)(k & 1);
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t r0 = tile * kTileRows;
         float4 xv[UX];
         float y1[U][4], y2[U][4], dp[U];
@@ -553,18 +549,9 @@ __global__ __launch_bounds__(kThreads) void k_ro_b3(int64_t N, const float* HF, 
             const int row = (tid + u * kThreads) / (C / 4);
             const int64_t i = r0 + row;
             const Dy2 d = recompute_dy2(y2[u], dp[u], i < N, i, c4, q2, bq2, w, bias, clamp01, p2, ks2, seed2);
-            if (set == 0) add_nc(db2[0], d.dy2); else add_nc(db2[1], d.dy2);
             split_store(g_hi, g_lo, row * LDC + c4, d.dy2);
-            float a1[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float xh;
-                a1[k] = i < N ? fmaxf(q1.pre(y1[u][k], k, xh), 0.f) * drop_scale(seed1, i * C + c4 + k, p1, ks1) : 0.f;
-            }
-            split_store(a_hi, a_lo, row * LDC + c4, a1);
         }
         lds_barrier();
-        if (set == 0) wg2[0].run(g_hi, g_lo, LDC, a_hi, a_lo, LDC); else wg2[1].run(g_hi, g_lo, LDC, a_hi, a_lo, LDC);  // dW2 += dy2^T a1
         mm2.run(g_hi, g_lo, LDC, s_o, LSC);                     // dA1 = dy2 W2
         lds_barrier();
 #pragma unroll
@@ -596,25 +583,73 @@ __global__ __launch_bounds__(kThreads) void k_ro_b3(int64_t N, const float* HF, 
     }
     float* row1 = slab1 + (int64_t)blockIdx.x * s_b3;
     wg.store(row1);
-    if (blockIdx.x < g2n) wg2[0].store(slab2 + (int64_t)blockIdx.x * s_b3w2);
-    if (blockIdx.x + gridDim.x < g2n) wg2[1].store(slab2 + (int64_t)(blockIdx.x + gridDim.x) * s_b3w2);
     float4* s_part = reinterpret_cast<float4*>(s_o);          // 512 float4 fit in s_o (64 x 68 floats)
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < U; ++u) s_part[tid + u * kThreads] = make_float4(db1[u][0], db1[u][1], db1[u][2], db1[u][3]);
     __syncthreads();
     wgrad_colsum(s_part, U * kThreads, row1 + C * D);
-#pragma unroll
-    for (int set = 0; set < 2; ++set) {
-        const int wg2 = blockIdx.x + set * gridDim.x;
-        __syncthreads();
-        s_part[tid] = make_float4(db2[set][0], db2[set][1], db2[set][2], db2[set][3]);
-        __syncthreads();
-        if (wg2 < g2n) wgrad_colsum(s_part, kThreads, slab2 + (int64_t)wg2 * s_b3w2 + C * C);
-    }
 }
 
-// workgroups: the forward tile kernels 4 per CU; B3 min(tiles, 512) and its db2 G2 = min(tiles, 1024), the grids of
+// B3w: dW2 = dy2^T a1 and db2 = colsum(dy2) as k_linear_wgrad_x3<32, 32> forms them, on its grid (min(tiles, 1024)), 256 threads, rows r
+// and r + 32 of a tile per thread: a pass of its own over y1, y2 and dprob, so that B3 keeps two waves per SIMD
+__global__ __launch_bounds__(kThreads) void k_ro_b3w(int64_t N, const float* Y1, const float* Y2, const float* dprob, const float* stats,
+                                                     const float* g1, const float* be1, const float* g2, const float* be2, float p1, float p2,
+                                                     uint64_t seed1, uint64_t seed2, const float* w3, const float* b3, int clamp01,
+                                                     const double* sums2, float* slab2) {
+    __shared__ __attribute__((aligned(16))) __bf16 g_hi[PC], g_lo[PC], a_hi[PC], a_lo[PC];
+    __shared__ float4 s_part[kThreads];
+    const int tid = threadIdx.x, c4 = (tid % (C / 4)) * 4;
+    BnQuad q1, q2;
+    q1.load(stats, g1, be1, c4);
+    q2.load(stats + 2 * C, g2, be2, c4);
+    BnBwdQuad bq2;
+    bq2.load(q2, sums2, N, c4);
+    const float ks1 = p1 > 0.f ? 1.0f / (1.0f - p1) : 1.0f, ks2 = p2 > 0.f ? 1.0f / (1.0f - p2) : 1.0f;
+    const float w[4] = {w3[c4], w3[c4 + 1], w3[c4 + 2], w3[c4 + 3]}, bias = b3[0];
+    MmWgrad<C, C> wg2;
+    wg2.zero();
+    constexpr int U = kTileRows * C / 4 / kThreads;
+    float db2[4] = {};
+    const int64_t ntiles = (N + kTileRows - 1) / kTileRows;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t r0 = tile * kTileRows;
+        float y1[U][4], y2[U][4], dp[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = r0 + (tid + u * kThreads) / (C / 4);
+            const bool ok = i < N;
+            to4(ok ? ld4(Y1 + i * C + c4) : zero4(), y1[u]);
+            to4(ok ? ld4(Y2 + i * C + c4) : zero4(), y2[u]);
+            dp[u] = ok ? dprob[i] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int row = (tid + u * kThreads) / (C / 4);
+            const int64_t i = r0 + row;
+            const Dy2 d = recompute_dy2(y2[u], dp[u], i < N, i, c4, q2, bq2, w, bias, clamp01, p2, ks2, seed2);
+            add_nc(db2, d.dy2);
+            split_store(g_hi, g_lo, row * LDC + c4, d.dy2);
+            float a1[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float xh;
+                a1[k] = i < N ? fmaxf(q1.pre(y1[u][k], k, xh), 0.f) * drop_scale(seed1, i * C + c4 + k, p1, ks1) : 0.f;
+            }
+            split_store(a_hi, a_lo, row * LDC + c4, a1);
+        }
+        lds_barrier();
+        wg2.run(g_hi, g_lo, LDC, a_hi, a_lo, LDC);             // dW2 += dy2^T a1
+        lds_barrier();
+    }
+    float* row2 = slab2 + (int64_t)blockIdx.x * s_b3w2;
+    wg2.store(row2);
+    s_part[tid] = make_float4(db2[0], db2[1], db2[2], db2[3]);
+    __syncthreads();
+    wgrad_colsum(s_part, kThreads, row2 + C * C);
+}
+
+// workgroups: the forward tile kernels 4 per CU; B3 min(tiles, 512) and B3w G2 = min(tiles, 1024), the grids of
 // k_linear_wgrad_x3<32, 64> and <32, 32>; B1 and B2 take k_bn_act_bwd's grid (8 per CU)
 constexpr int kGridF = 256 * 4, kGridB3 = 256 * 2, kGridDb2 = 256 * 4, kGridS = 256 * 8;
 inline int grid_tiles(int64_t N, int cap) { return grid_for((N + kTileRows - 1) / kTileRows, cap / 256); }
@@ -696,8 +731,10 @@ extern "C" int mgv_readout_fused_bwd(int64_t N, const float* hf, const float* y1
     const int g3n = grid_tiles(N, kGridB3), g2n = grid_tiles(N, kGridDb2);
     float* slab1 = reinterpret_cast<float*>(workspace);
     float* slab2 = slab1 + (int64_t)g3n * s_b3;
+    hipLaunchKernelGGL(mgv::ro::k_ro_b3w, dim3(g2n), dim3(mgv::kThreads), 0, st, N, y1, y2, dprob, stats, g1, be1, g2, be2, p1, p2, seed1,
+                       seed2, w3, b3, clamp01, sums2, slab2);
     hipLaunchKernelGGL(mgv::ro::k_ro_b3, dim3(g3n), dim3(mgv::kThreads), 0, st, N, hf, y1, y2, dprob, stats, g1, be1, g2, be2, p1, p2, seed1,
-                       seed2, w3, b3, clamp01, sums1, sums2, wp + o_w2t, wp + o_w1t, dhf, slab1, slab2, g2n);
+                       seed2, w3, b3, clamp01, sums1, sums2, wp + o_w2t, wp + o_w1t, dhf, slab1);
     // [dW1][db1] and [dW2][db2] are contiguous in grads, as in a slab row
     mgv::launch_slab_sum<float, float>(slab1, g3n, s_b3, C * D + C, grads + g_w1, st);
     mgv::launch_slab_sum<float, float>(slab2, g2n, s_b3w2, C * C + C, grads + g_w2, st);

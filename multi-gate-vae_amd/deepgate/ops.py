@@ -407,6 +407,20 @@ def _lin_x3(M, K):
     return _LIN_X3[key]
 
 
+# MGV_FUSED_LINEAR_BWD=0 keeps a Linear's input- and weight-gradient launches separate for a same-process A/B: tests flip this flag
+FUSED_LINEAR_BWD = os.environ.get('MGV_FUSED_LINEAR_BWD', '1') != '0'
+
+
+def _lin_bwd_x3(M, K):
+    """Layer shapes whose whole backward is one launch (mgv_linear_bwd_x3)."""
+    if PRECISION != 'x3':
+        return False
+    key = ('bwd', int(M), int(K))
+    if key not in _LIN_X3:
+        _LIN_X3[key] = bool(_hip.call_value('mgv_linear_bwd_x3_supported', int(M), int(K)))
+    return _LIN_X3[key]
+
+
 def _lin_fwd(x1, x2, W, b, M, wpack=None, res=None):
     """wpack given: W is ignored (bf16x3 path with a ready fragment-order pack).  res [N, M]: added to the result (in the
     kernel's store phase on the bf16x3 path)."""
@@ -473,11 +487,26 @@ class LinearFn(torch.autograd.Function):
                 _pack_into(pack, 0, Ws, True)
                 return _lin_fwd(gy, None, None, None, Kx, wpack=pack, res=res)
             return _lin_fwd(gy, None, Ws.t().contiguous(), None, Kx, res=res)
+        want_w = ctx.needs_input_grad[2] or (ctx.has_b and ctx.needs_input_grad[3])
+        if (FUSED_LINEAR_BWD and want_w and ctx.needs_input_grad[0] and (x2 is None or ctx.needs_input_grad[1]) and _lin_bwd_x3(M, K1 + K2)
+                and _lin_x3(K1, M) and (x2 is None or _lin_x3(K2, M))):
+            # input and weight gradients in one pass over gy (the same bits as the separate launches below)
+            pack = torch.empty(2 * W.numel(), dtype=torch.bfloat16, device=W.device)
+            _pack_into(pack, 0, W, True)
+            res = _rowmajor(check(g_pass.detach(), F32, 'g_pass')) if g_pass is not None else None
+            gx1 = torch.empty(N, K1, dtype=F32, device=W.device)
+            gx2 = torch.empty(N, K2, dtype=F32, device=W.device) if x2 is not None else None
+            gW = torch.zeros_like(W)
+            gb = torch.zeros(M, dtype=F32, device=W.device) if ctx.has_b else None
+            ws = workspace(_hip.call_value('mgv_linear_wgrad_x3_ws_floats', M, K1 + K2, N), W.device)
+            _hip.call('mgv_linear_bwd_x3', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0), ptr(gy), gy.stride(0),
+                      M, ptr(pack), ptr(gW), ptr(gb), ptr(gx1), K1, ptr(gx2), K2, ptr(res), 0 if res is None else res.stride(0), ptr(ws), ws.numel())
+            return gx1, gx2, gW, gb, None
         if ctx.needs_input_grad[0]:
             gx1 = dgrad(W[:, :K1], K1, res=g_pass.detach() if g_pass is not None else None)
         if x2 is not None and ctx.needs_input_grad[1]:
             gx2 = dgrad(W[:, K1:], K2)
-        if ctx.needs_input_grad[2] or (ctx.has_b and ctx.needs_input_grad[3]):
+        if want_w:
             gW = torch.zeros_like(W)
             gb = torch.zeros(M, dtype=F32, device=W.device) if ctx.has_b else None
             if _lin_x3(M, K1 + K2):
