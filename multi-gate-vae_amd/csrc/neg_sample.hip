@@ -58,8 +58,9 @@ __global__ __launch_bounds__(kThreads) void k_neg_bucket(int64_t E, const int64_
 extern "C" int mgv_neg_sample(int64_t N, int64_t E, uint64_t seed, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
                               int64_t* neg_src, int64_t* neg_dst, int32_t* cnt_out, int32_t* cnt_in, int32_t* rank_out, int32_t* rank_in,
                               void* stream) {
-    MGV_CHECK_ARG(N >= 2 && N < (1ll << 31) && E >= 0 && pos_out_ptr && neg_src && neg_dst && cnt_out && cnt_in && rank_out && rank_in);
-    if (E == 0) return MGV_OK;
+    MGV_CHECK_ARG(N >= 2 && N < (1ll << 31) && E >= 0 && pos_out_ptr && cnt_out && cnt_in && rank_out && rank_in);
+    if (E == 0) return MGV_OK;              // no slots: the pair arrays of an empty draw have no address (as in mgv_neg_bucket)
+    MGV_CHECK_ARG(neg_src && neg_dst);
     hipLaunchKernelGGL(mgv::k_neg_sample, dim3(mgv::grid_for((E + mgv::kThreads - 1) / mgv::kThreads, 16)), dim3(mgv::kThreads), 0,
                        static_cast<hipStream_t>(stream), N, E, seed, pos_out_ptr, pos_out_dst, neg_src, neg_dst, cnt_out, cnt_in, rank_out, rank_in);
     MGV_LAUNCH_RET();
