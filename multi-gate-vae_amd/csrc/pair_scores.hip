@@ -72,13 +72,83 @@ __device__ __forceinline__ void tile_scores(f32x4 (&acc)[4], const float (&a)[H 
     }
 }
 
+// ---------------------------------------------------------------------------------- the walk every all-pairs kernel is a consumer of
+// Its loop over the column tiles ct0 .. ct1 - 1 stands in every consumer as the same five lines — barrier (every wave is done with the
+// previous tile), tile_store of the prefetched tile, barrier, tile_load of the next one (in flight under the MFMAs), tile_scores — with
+// the consumer behind them.  As a function (a step the loop calls, or the loop with the consumer as a callable) the compiler allocates
+// and branches differently around it: a wave less in k_pair_fwd<32>, k_pair_topk<16> and k_sim_union<16>, 2 - 5 % on the general count
+// (NOTEBOOK 2026-10-19, eighth entry).  What decides — the rows' ranges, the tile range, who is a candidate — exists once, below.
+
+// The candidate columns [rlo[i], rhi[i]) of row u0 + i, i < 64: the row's own graph (the whole batch without a table, nothing for a row
+// past N), and in rgi — only where the caller keeps that table (GI) — the graph's index.  The caller's barrier publishes the tables.
+template <bool GI = false>
+__device__ __forceinline__ void row_ranges(int64_t N, int64_t u0, const int32_t* gp, int G, int* rlo, int* rhi, int* rgi = nullptr) {
+    if (threadIdx.x >= kPairTile) return;
+    const int64_t u = u0 + threadIdx.x;
+    int64_t lo = 0, hi = 0;
+    int gi = 0;
+    if (u < N) {
+        if (gp == nullptr) { hi = N; }
+        else {
+            int a = 0, b = G;                              // first graph whose end lies behind u
+            while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+            if (a < G) { lo = gp[a]; hi = gp[a + 1]; gi = a; }
+            lo = lo < 0 ? 0 : (lo > N ? N : lo);           // whatever the table holds, no column outside [0, N) is touched
+            hi = hi < lo ? lo : (hi > N ? N : hi);
+        }
+    }
+    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+    if constexpr (GI) rgi[threadIdx.x] = gi;               // gi < max(G, 1)
+}
+
+// The columns [clo, chi) that hold a candidate of any of the 64 rows (clo >= chi: none, nothing to walk).
+__device__ __forceinline__ void col_span(int64_t N, const int* rlo, const int* rhi, int64_t& clo, int64_t& chi) {
+    clo = N; chi = 0;
+    for (int i = 0; i < kPairTile; ++i) {
+        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
+    }
+}
+
+// The column tiles [ct0, ct1) that cover [clo, chi), asked only behind `clo < chi`, as each kernel had it: with the tile range computed
+// in front of that branch k_pair_topk<16> takes 62 - 67 VGPRs for 60 and loses a wave, and every symmetric kernel changes by some
+// hundred instructions (NOTEBOOK 2026-10-19, eighth entry).  SYM (s = t, the score matrix symmetric in bits, row u takes only v > u):
+// from the row tile's own column tile on — row and column tiles are both 64 wide, so the diagonal tile of workgroup b is column tile
+// b, and it starts inside t because u0 < N.
+template <bool SYM>
+__device__ __forceinline__ void tile_span(int64_t clo, int64_t chi, int64_t& ct0, int64_t& ct1) {
+    ct0 = clo / kPairTile;
+    ct1 = (chi + kPairTile - 1) / kPairTile;
+    if constexpr (SYM) ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;
+}
+
+// WHO is a candidate of row `row` and WHAT score is reported for it: the one statement behind every list, count, class and bin.
+//   general: a column of the row's graph [lo, hi), without the row itself when skip_self; the sigmoid of the dot product when asked for.
+//   SYM    : col > row (>= the graph's start) below hi; the raw score; `lo`, `skip_self` and `sigmoid` are not looked at.
+// A NaN score is nobody's candidate.
+// The symmetric form is stated as text (MGV_CAND_SYM) because k_sim_union needs it in one flat chain with its `> threshold`: behind
+// the function the chain reaches the back end in another order (`(a ? b : false) & gt` for `a ? (b & gt) : false`), its 16 float
+// compares per tile go through VCC one after the other, and mgv_sim_union ran 1.6 - 4.9 % slower (NOTEBOOK 2026-10-19, eighth entry).
+// The function's arguments come by reference on purpose: by value they are `noundef`, the compiler turns the `&&` chain into plain ands,
+// and where `> threshold` follows, its SLP vectoriser packs them into 4-wide 64-bit compares (seen in k_sim_union: a wave less at H = 128).
+#define MGV_CAND_SYM(v, col, row, hi) ((col) > (row) && (col) < (hi) && (v) == (v))
+template <bool SYM>
+__device__ __forceinline__ bool candidate(const float& v, const int64_t& col, const int64_t& row, const int& lo, const int& hi,
+                                          const int& skip_self, const int& sigmoid, float& rep) {
+    if constexpr (SYM) {
+        rep = v;
+        return MGV_CAND_SYM(v, col, row, hi);
+    } else {
+        rep = sigmoid ? sigmoidf_(v) : v;
+        return col >= lo && col < hi && !(skip_self && col == row) && v == v;
+    }
+}
+
 // ---------------------------------------------------------------------------------- dense forward
 // grid (row tiles, chunks of kPairChunk column tiles): no cap, every tile has its workgroup position
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_pair_fwd(int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt,
                                                        int sigmoid, float* out, int64_t ldo) {
-    constexpr int LDT = PairCfg<H>::LDT;
-    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t row0 = (int64_t)blockIdx.x * kPairTile + 16 * w;
     float a[H / 4];
@@ -89,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_fwd(int64_t M, int64_t N, con
     tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
     for (int64_t ct = ct0; ct < ct1; ++ct) {
         __syncthreads();                                   // every wave is done with the previous tile
-        tile_store<H, LDT>(tl, nxt);
+        tile_store<H, PairCfg<H>::LDT>(tl, nxt);
         __syncthreads();
         if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);   // in flight under the MFMAs
         f32x4 acc[4];
@@ -179,44 +249,28 @@ __global__ __launch_bounds__(kThreads) void k_pair_bwd(int64_t A, int64_t B, con
 // order of the lists: raw dot product descending, ties by ascending node id
 __device__ __forceinline__ bool pair_better(float v, int i, float kv, int ki) { return v > kv || (v == kv && i < ki); }
 
-// One workgroup per 64 rows u; it walks the column tiles that meet the rows' graphs with the dense kernel's tile loop.  Each wave
-// leaves its 16 x 16 score blocks in LDS, where 4 lanes per row scan them in ascending column order against the row's k-th best and
-// insert into the row's sorted list (LDS).  A row only ever sees the columns of its own graph.
+// One workgroup per 64 rows u; it walks the column tiles that meet the rows' graphs.  Each wave leaves its 16 x 16 score blocks in
+// LDS, where 4 lanes per row scan them in ascending column order against the row's k-th best and insert into the row's sorted list
+// (LDS).  A row only ever sees the columns of its own graph.
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                         int G, int k, int sigmoid, float threshold, int skip_self, int32_t* idx,
                                                         float* score, int32_t* n_above) {
-    constexpr int LDT = PairCfg<H>::LDT, LDS_SC = 17;
-    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    constexpr int LDS_SC = 17;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
     __shared__ float sc[kPairTile * LDS_SC];
     __shared__ float lv[kPairTile * kTopkMax];
     __shared__ int li[kPairTile * kTopkMax];
     __shared__ int rlo[kPairTile], rhi[kPairTile];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
-    if (threadIdx.x < kPairTile) {
-        const int64_t u = u0 + threadIdx.x;
-        int64_t lo = 0, hi = 0;
-        if (u < N) {
-            if (gp == nullptr) { hi = N; }
-            else {
-                int a = 0, b = G;                          // first graph whose end lies behind u
-                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
-                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
-                hi = hi < lo ? lo : (hi > N ? N : hi);
-            }
-        }
-        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
-    }
+    row_ranges(N, u0, gp, G, rlo, rhi);
     // the wave's rows: lane (row = lane >> 2, sub = lane & 3) in the scan, list rows initialised by their own wave
     const int srow = 16 * w + (lane >> 2), sub = lane & 3;
     for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
     __syncthreads();
-    int64_t clo = N, chi = 0;
-    for (int i = 0; i < kPairTile; ++i) {
-        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
-    }
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
     const int64_t su = u0 + srow;                          // the row this lane scans for
     const int mylo = rlo[srow], myhi = rhi[srow];
     const int64_t row0 = u0 + 16 * w;
@@ -224,19 +278,20 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     int cnt = 0;
     if (clo < chi) {
-        const int64_t ct0 = clo / kPairTile, ct1 = (chi + kPairTile - 1) / kPairTile;
+        int64_t ct0, ct1;
+        tile_span<false>(clo, chi, ct0, ct1);
         float4 nxt[H / 16];
         tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
         for (int64_t ct = ct0; ct < ct1; ++ct) {
             __syncthreads();
-            tile_store<H, LDT>(tl, nxt);
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
             __syncthreads();
             if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
             f32x4 acc[4];
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                wave_lds_fence();                          // the previous block's reads are done
+                wave_lds_fence();                              // the previous block's reads are done
 #pragma unroll
                 for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * LDS_SC + r] = acc[c][g];
                 wave_lds_fence();
@@ -244,12 +299,12 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
                 for (int st = 0; st < 4; ++st) {
                     const int64_t col = cb + 4 * st + sub;
                     const float v = sc[srow * LDS_SC + 4 * st + sub];
-                    const bool valid = col >= mylo && col < myhi && !(skip_self && col == su) && v == v;
-                    const float rep = sigmoid ? sigmoidf_(v) : v;
+                    float rep;
+                    const bool valid = candidate<false>(v, col, su, mylo, myhi, skip_self, sigmoid, rep);
                     cnt += (valid && rep > threshold) ? 1 : 0;
                     const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
                     if (__ballot(pass) == 0ull) continue;
-                    for (int turn = 0; turn < 4; ++turn) {  // the row's four lanes insert one after the other, lowest column first
+                    for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
                         if (pass && sub == turn) {
                             float* L = lv + srow * kTopkMax;
                             int* I = li + srow * kTopkMax;
@@ -282,48 +337,29 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
 }
 
 // ---------------------------------------------------------------------------------- thresholded links as per-row lists
-// The tile walk of k_pair_topk without its lists: one workgroup per 64 rows u, the rows' s fragments in registers, the t tiles through
+// The walk of k_pair_topk without its lists: one workgroup per 64 rows u, the rows' s fragments in registers, the t tiles through
 // LDS with the next one prefetched.  Nothing leaves the accumulators: lane (r, q) holds column 16 c + r of rows 4 q + g, so the 16
-// lanes of quarter q are one row's 16-column block in ascending column order, and the decision `reported score > threshold` (the
-// expression behind k_pair_topk's n_above) is taken where the score lies.
+// lanes of quarter q are one row's 16-column block in ascending column order, and the decision `candidate and reported score >
+// threshold` (the expression behind k_pair_topk's n_above) is taken where the score lies.
 //   FILL = false: every lane counts its own columns; the 16 lanes of a quarter add up at the end -> n_sel[u].
 //   FILL = true : a ballot per (c, g) gives the block's 16 decisions to all of the row's lanes; a lane's slot is the row's cursor plus
 //                 the popcount of the lower columns, and the cursor (the same number in the row's 16 lanes) moves on by the block's
 //                 popcount through the whole walk.  Ascending columns, no atomics, the same bytes from call to call.  A row writes
 //                 only slots in [row_ptr[u], min(row_ptr[u+1], cap)) that are >= 0; what has no room is dropped.
-//   SYM = true  : s = t = unit rows (mgv_sim_select_*; trainer.py:158-160 in the arithmetic of digae_layer.py:31-33).  The score matrix
-//                 is symmetric in bits, so row u lists only v > u: the walk starts at the row tile's own column tile (row and column
-//                 tiles are both 64 wide, the diagonal tile of workgroup b is column tile b) and the decision gets `col > row`.
-//                 Raw scores, no self: `sigmoid` and `skip_self` are not looked at.
+//   SYM = true  : s = t = unit rows (mgv_sim_select_*; trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): row u lists only
+//                 v > u, on half the tiles (tile_span<true>, candidate<true>).
 template <int H, bool FILL, bool SYM = false>
 __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                           int G, int sigmoid, float threshold, int skip_self, int32_t* n_sel,
                                                           const int64_t* row_ptr, int64_t cap, int32_t* col_out, float* score_out) {
-    constexpr int LDT = PairCfg<H>::LDT;
-    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
     __shared__ int rlo[kPairTile], rhi[kPairTile];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
-    if (threadIdx.x < kPairTile) {
-        const int64_t u = u0 + threadIdx.x;
-        int64_t lo = 0, hi = 0;
-        if (u < N) {
-            if (gp == nullptr) { hi = N; }
-            else {
-                int a = 0, b = G;                          // first graph whose end lies behind u
-                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
-                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
-                hi = hi < lo ? lo : (hi > N ? N : hi);
-            }
-        }
-        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
-    }
+    row_ranges(N, u0, gp, G, rlo, rhi);
     __syncthreads();
-    int64_t clo = N, chi = 0;
-    for (int i = 0; i < kPairTile; ++i) {
-        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
-    }
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
     const int64_t row0 = u0 + 16 * w;
     // the lane's four rows 4 q + g: candidate range, slots, cursor
     int mylo[4], myhi[4], cnt[4];
@@ -343,14 +379,13 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
     float a[H / 4];
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     if (clo < chi) {
-        int64_t ct0 = clo / kPairTile;
-        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
-        if constexpr (SYM) ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside t
+        int64_t ct0, ct1;
+        tile_span<SYM>(clo, chi, ct0, ct1);
         float4 nxt[H / 16];
         tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
         for (int64_t ct = ct0; ct < ct1; ++ct) {
             __syncthreads();
-            tile_store<H, LDT>(tl, nxt);
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
             __syncthreads();
             if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
             f32x4 acc[4];
@@ -360,22 +395,14 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
                 const int64_t col = ct * kPairTile + 16 * c + r;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const float v = acc[c][g];
-                    bool valid;
                     float rep;
-                    if constexpr (SYM) {
-                        valid = col > row0 + 4 * q + g && col < myhi[g] && v == v;     // col > row >= the graph's start
-                        rep = v;
-                    } else {
-                        valid = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
-                        rep = sigmoid ? sigmoidf_(v) : v;
-                    }
-                    const bool pass = valid && rep > threshold;
+                    const bool pass = candidate<SYM>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], skip_self, sigmoid, rep) &&
+                                      rep > threshold;
                     if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
                     const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
                     const uint64_t i = (uint64_t)(unsigned)cnt[g] + (uint64_t)__popc(bits & ((1u << r) - 1u));
                     cnt[g] += __popc(bits);
-                    if (pass && i < room[g]) {              // i < room: base + i < min(row_ptr[u+1], cap), no overflow
+                    if (pass && i < room[g]) {                  // i < room: base + i < min(row_ptr[u+1], cap), no overflow
                         const int64_t pos = base[g] + (int64_t)i;
                         if (pos >= 0) {
                             col_out[pos] = (int32_t)col;
@@ -401,40 +428,23 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
 }
 
 // ---------------------------------------------------------------------------------- classes straight from the walk
-// The symmetric walk of k_pair_select<H, ., true> — the same tiles, tile_scores and decision `col > row && col < hi && v == v &&
-// v > threshold` — as a sibling kernel on the shared helpers (the selection kernels are not touched and compile as before).  Where the
-// fill would store column `col` of row `row`, the pair is united in `parent` (mgv_unionfind.h: every access an agent-scope atomic, the
-// smaller root wins, bounded retries).  A cosine is the same bits whichever kernel computes it, so the components are exactly those of
-// the list mgv_sim_select_fill writes.  Outside the MFMA section: a lane first decides its 16 entries of the tile into a bit mask, then
-// unites the set bits; uf_unite starts with the two finds and leaves when the roots agree, which at a low threshold is nearly always.
+// The symmetric walk of k_pair_select<H, ., true> — the same tiles, candidate<true> and `> threshold` — with a union-find as its
+// consumer.  Where the fill would store column `col` of row `row`, the pair is united in `parent` (mgv_unionfind.h: every access an
+// agent-scope atomic, the smaller root wins, bounded retries).  A cosine is the same bits whichever kernel computes it, so the components
+// are exactly those of the list mgv_sim_select_fill writes.  Outside the MFMA section: a lane first decides its 16 entries of the tile
+// into a bit mask, then unites the set bits; uf_unite starts with the two finds and leaves when the roots agree, which at a low
+// threshold is nearly always.
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* y, int ldy, const int32_t* gp, int G, float threshold,
                                                         int32_t* parent, int32_t* status) {
-    constexpr int LDT = PairCfg<H>::LDT;
-    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
     __shared__ int rlo[kPairTile], rhi[kPairTile];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
-    if (threadIdx.x < kPairTile) {
-        const int64_t u = u0 + threadIdx.x;
-        int64_t lo = 0, hi = 0;
-        if (u < N) {
-            if (gp == nullptr) { hi = N; }
-            else {
-                int a = 0, b = G;                          // first graph whose end lies behind u
-                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-                if (a < G) { lo = gp[a]; hi = gp[a + 1]; }
-                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no node outside [0, N) is touched
-                hi = hi < lo ? lo : (hi > N ? N : hi);
-            }
-        }
-        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
-    }
+    row_ranges(N, u0, gp, G, rlo, rhi);
     __syncthreads();
-    int64_t clo = N, chi = 0;
-    for (int i = 0; i < kPairTile; ++i) {
-        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
-    }
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
     const int64_t row0 = u0 + 16 * w;
     int myhi[4];
 #pragma unroll
@@ -442,30 +452,29 @@ __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* 
     float a[H / 4];
     load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
     if (clo < chi) {
-        int64_t ct0 = clo / kPairTile;
-        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
-        ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside y
+        int64_t ct0, ct1;
+        tile_span<true>(clo, chi, ct0, ct1);
         float4 nxt[H / 16];
         tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
         for (int64_t ct = ct0; ct < ct1; ++ct) {
             __syncthreads();
-            tile_store<H, LDT>(tl, nxt);
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
             __syncthreads();
             if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
             f32x4 acc[4];
             tile_scores<H>(acc, a, tl, r, q);
-            unsigned bits = 0;                              // bit 4 c + g: the lane's entry (row 4 q + g, column 16 c + r)
+            unsigned bits = 0;                                  // bit 4 c + g: the lane's entry (row 4 q + g, column 16 c + r)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int64_t col = ct * kPairTile + 16 * c + r;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const float v = acc[c][g];
-                    const bool pass = col > row0 + 4 * q + g && col < myhi[g] && v == v && v > threshold;
+                    const float v = acc[c][g];                  // candidate<true>'s statement; the raw score is what is reported
+                    const bool pass = MGV_CAND_SYM(v, col, row0 + 4 * q + g, myhi[g]) && v > threshold;
                     bits |= pass ? 1u << (4 * c + g) : 0u;
                 }
             }
-            while (bits != 0) {                             // row < col < myhi <= N: both ids inside parent
+            while (bits != 0) {                                 // row < col < myhi <= N: both ids inside parent
                 const int b = __ffs(bits) - 1;
                 bits &= bits - 1;
                 uf_unite(parent, (int)(row0 + 4 * q + (b & 3)), (int)(ct * kPairTile + 16 * (b >> 2) + r), status);
@@ -475,11 +484,11 @@ __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* 
 }
 
 // ---------------------------------------------------------------------------------- the distribution of all-pair scores
-// The walk of k_pair_select<H, false, SYM> — the same tiles, tile_scores, `valid` and `rep` — as a sibling kernel on the shared helpers
-// (the selection and union kernels are not touched and compile as before).  Where the count adds `rep > threshold`, a candidate is
-// binned by bin = #{j : rep > edges[j]}: a branch-free binary search over the table in LDS, padded with +inf (nothing passes it) to
-// 2^p - 1 entries, 2^p the first power of two above B, so that p steps `pos += rep > el[pos + step - 1] ? step : 0` from step = 2^(p-1)
-// down to 1 count the edges below rep.  The same `>` on the same bits as the count entry: sum(hist[g][j+1:]) IS its total at edges[j].
+// The walk of k_pair_select<H, false, SYM> — the same tiles and candidate<SYM> — with a histogram as its consumer.  Where the count adds
+// `rep > threshold`, a candidate is binned by bin = #{j : rep > edges[j]}: a branch-free binary search over the table in LDS, padded
+// with +inf (nothing passes it) to 2^p - 1 entries, 2^p the first power of two above B, so that p steps
+// `pos += rep > el[pos + step - 1] ? step : 0` from step = 2^(p-1) down to 1 count the edges below rep.  The same `>` on the same bits
+// as the count entry: sum(hist[g][j+1:]) IS its total at edges[j].
 //
 // Accumulation.  A tile's 64 rows are consecutive nodes, so of the graphs they belong to only the first and the last can reach beyond
 // the tile; every graph between them lies inside it and has at most 62 nodes.  The first and the last graph get an LDS histogram each
@@ -492,8 +501,8 @@ __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* 
 // 16 candidates per tile over at most 2^25 tiles: int32.
 // LDS at H = 128: score tile 33,792 B + row tables 768 B + edges 2,048 B + counters 4,112 B = 40,720 B against 34,304 B of
 // k_pair_select: four workgroups (one wave per SIMD each) would still fit the 160 KB of a CU, 4 x 40,720 = 162,880 <= 163,840.  The
-// bound is the registers, as it is for k_pair_select: 154 - 162 VGPRs + 16 AGPRs at H = 128 give 2 waves per SIMD (two workgroups per
-// CU, 81 KB of LDS), 117 - 121 at H = 64 give 3 (24,336 B each), so the histogram costs no occupancy at any width.
+// bound is the registers, as it is for k_pair_select: 154 - 162 VGPRs + 16 AGPRs at H = 128 give 2 waves per SIMD (two workgroups
+// per CU, 81 KB of LDS, fit either way), 117 - 121 at H = 64 give 3 (24,336 B each), so the histogram costs no occupancy at any width.
 constexpr int kHistMaxEdges = 256;
 constexpr int kHistTable = 512;        // >= 2^p - 1 for every B <= kHistMaxEdges
 constexpr int kHistSlots = 2;          // the tile's first and last graph
@@ -502,37 +511,19 @@ template <int H, bool SYM>
 __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                         int G, int sigmoid, int skip_self, const float* edges, int B, int top,
                                                         unsigned long long* hist) {
-    constexpr int LDT = PairCfg<H>::LDT;
-    __shared__ __attribute__((aligned(16))) float tl[kPairTile * LDT];
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
     __shared__ int rlo[kPairTile], rhi[kPairTile], rgi[kPairTile];
     __shared__ float el[kHistTable];
     __shared__ unsigned long long lh[kHistSlots * (kHistMaxEdges + 1)];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
     const int B1 = B + 1;
-    if (threadIdx.x < kPairTile) {
-        const int64_t u = u0 + threadIdx.x;
-        int64_t lo = 0, hi = 0;
-        int gi = 0;
-        if (u < N) {
-            if (gp == nullptr) { hi = N; }
-            else {
-                int a = 0, b = G;                          // first graph whose end lies behind u
-                while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-                if (a < G) { lo = gp[a]; hi = gp[a + 1]; gi = a; }
-                lo = lo < 0 ? 0 : (lo > N ? N : lo);       // whatever the table holds, no column outside [0, N) is touched
-                hi = hi < lo ? lo : (hi > N ? N : hi);
-            }
-        }
-        rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi; rgi[threadIdx.x] = gi;     // gi < max(G, 1): a row of hist
-    }
+    row_ranges<true>(N, u0, gp, G, rlo, rhi, rgi);         // rgi: a row of hist
     for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
     for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) lh[i] = 0ull;
     __syncthreads();
-    int64_t clo = N, chi = 0;
-    for (int i = 0; i < kPairTile; ++i) {
-        if (rlo[i] < rhi[i]) { clo = rlo[i] < clo ? rlo[i] : clo; chi = rhi[i] > chi ? rhi[i] : chi; }
-    }
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
     const int64_t row0 = u0 + 16 * w;
     const int64_t left = N - 1 - u0;                       // u0 < N: the tile's last row inside N
     const int gfirst = rgi[0], glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
@@ -554,38 +545,30 @@ __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* 
     float a[H / 4];
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     if (clo < chi) {
-        int64_t ct0 = clo / kPairTile;
-        const int64_t ct1 = (chi + kPairTile - 1) / kPairTile;
-        if constexpr (SYM) ct0 = ct0 > (int64_t)blockIdx.x ? ct0 : (int64_t)blockIdx.x;      // u0 < N: the tile starts inside t
+        int64_t ct0, ct1;
+        tile_span<SYM>(clo, chi, ct0, ct1);
         float4 nxt[H / 16];
         tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
         for (int64_t ct = ct0; ct < ct1; ++ct) {
             __syncthreads();
-            tile_store<H, LDT>(tl, nxt);
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
             __syncthreads();
             if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
             f32x4 acc[4];
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {                  // row by row: a run lasts as long as the row's scores stay in one bin
+            for (int g = 0; g < 4; ++g) {                      // row by row: a run lasts as long as the row's scores stay in one bin
                 bool valid[4], any = false;
                 float rep[4];
                 int pos[4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const int64_t col = ct * kPairTile + 16 * c + r;
-                    const float v = acc[c][g];
-                    if constexpr (SYM) {
-                        valid[c] = col > row0 + 4 * q + g && col < myhi[g] && v == v;  // col > row >= the graph's start
-                        rep[c] = v;
-                    } else {
-                        valid[c] = col >= mylo[g] && col < myhi[g] && !(skip_self && col == row0 + 4 * q + g) && v == v;
-                        rep[c] = sigmoid ? sigmoidf_(v) : v;
-                    }
+                    valid[c] = candidate<SYM>(acc[c][g], ct * kPairTile + 16 * c + r, row0 + 4 * q + g, mylo[g], myhi[g], skip_self, sigmoid,
+                                              rep[c]);
                     any = any || valid[c];
                     pos[c] = 0;
                 }
-                if (__ballot(any) == 0ull) continue;       // the wave has no candidate in these rows of this tile
+                if (__ballot(any) == 0ull) continue;           // the wave has no candidate in these rows of this tile
                 for (int step = top; step > 0; step >>= 1) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
@@ -593,7 +576,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* 
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     if (!valid[c]) continue;
-                    const int bin = pos[c] < B ? pos[c] : B;     // an ascending table never gives more; nothing else is indexed
+                    const int bin = pos[c] < B ? pos[c] : B;   // an ascending table never gives more; nothing else is indexed
                     if (run_n > 0 && run_gi == mygi[g] && run_bin == bin) { ++run_n; continue; }
                     flush();
                     run_gi = mygi[g]; run_bin = bin; run_n = 1;
@@ -638,6 +621,10 @@ inline bool pair_rows_ok(const float* x, int ld, int H) { return x != nullptr &&
         case 64: { constexpr int HH = 64; EXPR; } break;                        \
         default: { constexpr int HH = 128; EXPR; } break;                       \
     }
+// the same with the walk's form as SYM (true: s = t = unit rows, every unordered pair once)
+#define MGV_PAIR_DISPATCH_H_SYM(H, sym, EXPR)                                   \
+    if (sym) { constexpr bool SYM = true; MGV_PAIR_DISPATCH_H(H, EXPR) }        \
+    else { constexpr bool SYM = false; MGV_PAIR_DISPATCH_H(H, EXPR) }
 
 extern "C" int mgv_pair_scores_fwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid,
                                    float* out, int64_t ldo, void* stream) {
@@ -697,33 +684,9 @@ extern "C" int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, con
     MGV_LAUNCH_RET();
 }
 
-extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
-                             int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
-    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // node ids and idx offsets are int32 on the host side
-    MGV_CHECK_ARG(graph_ptr == nullptr || G >= 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (graph_ptr != nullptr) {
-        // the table must start at 0 and end at N: its two ends are read back (the only blocking step of this entry; NULL skips it)
-        int32_t ends[2] = {0, 0};
-        hipError_t e = hipMemcpyAsync(&ends[0], graph_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&ends[1], graph_ptr + G, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return (int)e;
-        MGV_CHECK_ARG(ends[0] == 0 && (int64_t)ends[1] == N);
-    }
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H) && idx != nullptr && score != nullptr && n_above != nullptr);
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_topk<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
-                                              graph_ptr, G, k, sigmoid, threshold, skip_self, idx, score, n_above));
-    MGV_LAUNCH_RET();
-}
-
-// the arguments the two selection entries share, checked in the order of mgv_pair_topk; *launch = false: nothing to do
-static int pair_select_args(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
-                            hipStream_t st, bool* launch) {
+// the arguments every walk entry shares, checked in this order by all of them; *launch = false: nothing to walk
+static int pair_walk_args(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                          hipStream_t st, bool* launch) {
     *launch = false;
     if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL);                           // node ids are int32
@@ -743,35 +706,65 @@ static int pair_select_args(int H, int64_t N, const float* s, int lds, const flo
     return MGV_OK;
 }
 
-extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
-                                     int sigmoid, float threshold, int skip_self, int32_t* n_sel, void* stream) {
+// a walk kernel's launch: one workgroup per 64 rows
+template <typename K, typename... A>
+static void launch_row_tiles(K kernel, int64_t N, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((N + mgv::kPairTile - 1) / mgv::kPairTile)), dim3(mgv::kThreads), 0, st, args...);
+}
+
+extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
+                             int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // node ids and idx offsets are int32 on the host side
     bool launch;
-    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(idx != nullptr && score != nullptr && n_above != nullptr);
+    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_pair_topk<HH>, N, st, N, s, lds, t, ldt, graph_ptr, G, k, sigmoid, threshold, skip_self,
+                                            idx, score, n_above));
+    MGV_LAUNCH_RET();
+}
+
+// the two count entries; sym: s = t = unit rows, and `sigmoid` / `skip_self` come in as 0
+static int select_count_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                            float threshold, int skip_self, bool sym, int32_t* n_sel, hipStream_t st) {
+    bool launch;
+    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
     if (rc != MGV_OK || !launch) return rc;
     MGV_CHECK_ARG(n_sel != nullptr);
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, false>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t,
-                                              ldt, graph_ptr, G, sigmoid, threshold, skip_self, n_sel, (const int64_t*)nullptr, (int64_t)0,
-                                              (int32_t*)nullptr, (float*)nullptr));
+    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_select<HH, false, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid,
+                                                     threshold, skip_self, n_sel, nullptr, 0, nullptr, nullptr));
     MGV_LAUNCH_RET();
+}
+
+// the two fill entries, as select_count_run
+static int select_fill_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                           float threshold, int skip_self, bool sym, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score,
+                           hipStream_t st) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(cap >= 0);
+    bool launch;
+    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
+    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
+    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_select<HH, true, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid,
+                                                     threshold, skip_self, nullptr, row_ptr, cap, col, score));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                     int sigmoid, float threshold, int skip_self, int32_t* n_sel, void* stream) {
+    return select_count_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, false, n_sel, (hipStream_t)stream);
 }
 
 extern "C" int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
                                     int sigmoid, float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col,
                                     float* score, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(cap >= 0);
-    bool launch;
-    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
-    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t,
-                                              ldt, graph_ptr, G, sigmoid, threshold, skip_self, (int32_t*)nullptr, row_ptr, cap, col, score));
-    MGV_LAUNCH_RET();
+    return select_fill_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, false, row_ptr, cap, col, score,
+                           (hipStream_t)stream);
 }
 
 extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm, void* stream) {
@@ -788,45 +781,23 @@ extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps
 
 extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                                     int32_t* n_sel, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    bool launch;
-    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    MGV_CHECK_ARG(n_sel != nullptr);
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, false, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy,
-                                              y, ldy, graph_ptr, G, 0, threshold, 0, n_sel, (const int64_t*)nullptr, (int64_t)0,
-                                              (int32_t*)nullptr, (float*)nullptr));
-    MGV_LAUNCH_RET();
+    return select_count_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, threshold, 0, true, n_sel, (hipStream_t)stream);
 }
 
 extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                                    const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(cap >= 0);
-    bool launch;
-    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
-    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_select<HH, true, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy,
-                                              y, ldy, graph_ptr, G, 0, threshold, 0, (int32_t*)nullptr, row_ptr, cap, col, score));
-    MGV_LAUNCH_RET();
+    return select_fill_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, threshold, 0, true, row_ptr, cap, col, score, (hipStream_t)stream);
 }
 
 extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,
                              int32_t* status, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     bool launch;
-    const int rc = pair_select_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
+    const int rc = pair_walk_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
     if (rc != MGV_OK) return rc;
     MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
     if (!launch) return MGV_OK;
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_sim_union<HH>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, y, ldy, graph_ptr, G,
-                                              threshold, parent, status));
+    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_sim_union<HH>, N, st, N, y, ldy, graph_ptr, G, threshold, parent, status));
     MGV_LAUNCH_RET();
 }
 
@@ -836,7 +807,7 @@ static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float*
     if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(B >= 1 && B <= mgv::kHistMaxEdges && edges != nullptr && hist != nullptr);
     bool launch;
-    const int rc = pair_select_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
     if (rc != MGV_OK) return rc;
     // the table must ascend strictly and hold no NaN: it is read back, like the two ends of graph_ptr (one small blocking copy)
     float e[mgv::kHistMaxEdges];
@@ -851,15 +822,9 @@ static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float*
     if (!launch) return MGV_OK;
     int top = 1;                                                          // half the first power of two above B
     while (2 * top <= B) top *= 2;
-    const int64_t nrt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
     unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-    if (sym) {
-        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_hist<HH, true>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
-                                                  graph_ptr, G, 0, 0, edges, B, top, h));
-    } else {
-        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_hist<HH, false>), dim3((unsigned)nrt), dim3(mgv::kThreads), 0, st, N, s, lds, t, ldt,
-                                                  graph_ptr, G, sigmoid, skip_self, edges, B, top, h));
-    }
+    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_hist<HH, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self,
+                                                     edges, B, top, h));
     MGV_LAUNCH_RET();
 }
 

@@ -939,11 +939,34 @@ def _pair_operands(s, t):
     return sd, lds, td, ldt, sd.shape[1]
 
 
+_PAIR_WIDTHS = (16, 32, 64, 128)
+
+
+def _pair_width(x, name):
+    if x.dim() == 2 and x.shape[1] not in _PAIR_WIDTHS:
+        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
+                              % (name, list(_PAIR_WIDTHS), x.shape[1]))
+
+
+def _pair_graphs(graph_ptr, dev):
+    """(gp int32 [G + 1] on the device, G) as the walk entries take a batch's graphs; None: (None, 0), one graph."""
+    if graph_ptr is None:
+        return None, 0
+    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
+    if gp.numel() < 1:
+        raise HipLibraryError('graph_ptr needs at least one entry')
+    return gp, gp.numel() - 1
+
+
+def _free_bytes(dev):
+    free, _ = torch.cuda.mem_get_info(dev)
+    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)  # blocks the caching allocator can hand out again
+
+
 def _dense_fits(M, N, dev):
     """A dense M x N result the device cannot hold is refused here, by name, instead of by the allocator."""
     need = 4 * M * N
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # blocks the caching allocator can hand out again
+    free = _free_bytes(dev)
     if need > free:
         raise HipLibraryError('dense scores of %d x %d pairs need %.1f GiB, the device has %.1f GiB free: use the streaming form, '
                               'ops.pair_topk / DirectedInnerProductDecoder.topk (top-k links and counts per row, no N x N array)'
@@ -1005,12 +1028,7 @@ def pair_topk(s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=Fa
         raise HipLibraryError('pair_topk ranks the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
     k = int(k)
     dev = sd.device
-    gp, G = None, 0
-    if graph_ptr is not None:
-        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
-        G = gp.numel() - 1
-        if G < 0:
-            raise HipLibraryError('graph_ptr needs at least one entry')
+    gp, G = _pair_graphs(graph_ptr, dev)
     kk = min(max(k, 1), 32)
     idx = torch.empty((N, kk), dtype=I32, device=dev)
     score = torch.empty((N, kk), dtype=F32, device=dev)
@@ -1020,19 +1038,38 @@ def pair_topk(s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=Fa
     return idx, score, n_above
 
 
-_PAIR_WIDTHS = (16, 32, 64, 128)
+def _list_room(name, total, free, *, noun, listed, limit_name, limit, item_bytes, hint):
+    """The two refusals between a selection's count and its fill (nothing is allocated before them): more than the caller's
+    `limit_name` allows, or a result — `listed` in words — of item_bytes per `noun` the device cannot hold; by name, like _dense_fits."""
+    if limit is not None and total > int(limit):
+        raise HipLibraryError('%s: %d %s are above the threshold, %s allows %d: %s' % (name, total, noun, limit_name, int(limit), hint))
+    need = item_bytes * total
+    if free is not None and need > free:
+        raise HipLibraryError('%s: %s above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
+                              % (name, listed % total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
 
 
 def _select_room(total, with_scores, max_edges, free):
-    """The two refusals of pair_select between its count and its fill (nothing is allocated before them): more links than the caller
-    allows, or lists (int32 ids, float32 scores beside them when asked for) the device cannot hold — by name, like _dense_fits."""
-    hint = 'raise the threshold, or take the k best links per node with ops.pair_topk / DirectedInnerProductDecoder.topk'
-    if max_edges is not None and total > int(max_edges):
-        raise HipLibraryError('pair_select: %d links are above the threshold, max_edges allows %d: %s' % (total, int(max_edges), hint))
-    need = (8 if with_scores else 4) * total
-    if free is not None and need > free:
-        raise HipLibraryError('pair_select: the lists of %d links above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
-                              % (total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
+    """pair_select's refusals: lists of int32 ids, float32 scores beside them when asked for."""
+    _list_room('pair_select', total, free, noun='links', listed='the lists of %d links', limit_name='max_edges', limit=max_edges,
+               item_bytes=8 if with_scores else 4,
+               hint='raise the threshold, or take the k best links per node with ops.pair_topk / DirectedInnerProductDecoder.topk')
+
+
+def _count_scan_fill(count_entry, fill_entry, N, common, dev, with_scores, room):
+    """(row_ptr int64 [N + 1], col int32 [total], score float32 [total] or None) of a selection walk over N rows with the arguments
+    `common` of both entries: count, exclusive scan on the device, ONE read-back of the total (the result must be allocated), room(total, free
+    bytes) — which refuses by raising —, allocate, fill."""
+    n_sel = torch.empty(N, dtype=I32, device=dev)
+    _hip.call(count_entry, *common, ptr(n_sel))
+    row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
+    total = int(row_ptr[-1])                                      # the read-back
+    room(total, _free_bytes(dev))
+    col = torch.empty(total, dtype=I32, device=dev)
+    score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
+    _hip.call(fill_entry, *common, ptr(row_ptr), total, ptr(col), ptr(score))
+    return row_ptr, col, score
 
 
 def pair_select(s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
@@ -1046,35 +1083,18 @@ def pair_select(s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=Fal
     beyond the free memory raises HipLibraryError before the fill.  No grad."""
     if by not in ('src', 'dst'):
         raise HipLibraryError("pair_select: by must be 'src' (row u lists its targets) or 'dst' (row v lists its sources), got %r" % (by,))
-    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1] and s.shape[1] not in _PAIR_WIDTHS:
-        raise HipLibraryError('pair_select: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
-                              % (list(_PAIR_WIDTHS), s.shape[1]))
+    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
+        _pair_width(s, 'pair_select')
     if by == 'dst':
         s, t = t, s
     sd, lds, td, ldt, H = _pair_operands(s, t)
     N = sd.shape[0]
     if td.shape[0] != N:
         raise HipLibraryError('pair_select lists the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
-    dev = sd.device
-    gp, G = None, 0
-    if graph_ptr is not None:
-        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
-        G = gp.numel() - 1
-        if G < 0:
-            raise HipLibraryError('graph_ptr needs at least one entry')
+    gp, G = _pair_graphs(graph_ptr, sd.device)
     common = (H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), float(threshold), int(bool(skip_self)))
-    n_sel = torch.empty(N, dtype=I32, device=dev)
-    _hip.call('mgv_pair_select_count', *common, ptr(n_sel))
-    row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
-    total = int(row_ptr[-1])                                      # the read-back
-    free, _ = torch.cuda.mem_get_info(dev)
-    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # as _dense_fits
-    _select_room(total, with_scores, max_edges, free)
-    col = torch.empty(total, dtype=I32, device=dev)
-    score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
-    _hip.call('mgv_pair_select_fill', *common, ptr(row_ptr), total, ptr(col), ptr(score))
-    return row_ptr, col, score
+    return _count_scan_fill('mgv_pair_select_count', 'mgv_pair_select_fill', N, common, sd.device, with_scores,
+                            lambda total, free: _select_room(total, with_scores, max_edges, free))
 
 
 def reconstruct_edges(s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
@@ -1126,26 +1146,11 @@ def dense_scores(s, t):
 SIM_THRESHOLD = 0.999
 
 
-def _sim_width(x, name):
-    if x.dim() == 2 and x.shape[1] not in _PAIR_WIDTHS:
-        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
-                              % (name, list(_PAIR_WIDTHS), x.shape[1]))
-
-
-def _sim_graphs(graph_ptr, dev):
-    if graph_ptr is None:
-        return None, 0
-    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
-    if gp.numel() < 1:
-        raise HipLibraryError('graph_ptr needs at least one entry')
-    return gp, gp.numel() - 1
-
-
 def row_unit(x, eps=1e-8, want_norm=False):
     """y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity and of the functional loss (trainer.py:158-160,
     mgv_func_loss_fwd); with want_norm also |x[i]| unclamped: (y, norm).  A zero row stays a zero row, a row with a NaN becomes NaN.
     The sum of squares is float32 without rescaling (hf is a GRU output in (-1, 1)).  No grad."""
-    _sim_width(x, 'row_unit')
+    _pair_width(x, 'row_unit')
     with torch.no_grad():
         xd, ldx = _pair_rows(x, 'x')
         N, H = xd.shape
@@ -1166,15 +1171,10 @@ def sim_topk(x, k, graph_ptr=None, threshold=SIM_THRESHOLD, eps=1e-8):
 
 
 def _sim_room(total, with_scores, max_pairs, free):
-    """The two refusals of sim_pairs between its count and its fill, as _select_room's: more pairs than the caller allows, or a result
-    (int64 pair_index, the int32 list it is made from, float32 scores when asked for) the device cannot hold."""
-    hint = 'raise the threshold, or take the k most similar gates per node with ops.sim_topk / similar_gates'
-    if max_pairs is not None and total > int(max_pairs):
-        raise HipLibraryError('sim_pairs: %d pairs are above the threshold, max_pairs allows %d: %s' % (total, int(max_pairs), hint))
-    need = (24 if with_scores else 20) * total
-    if free is not None and need > free:
-        raise HipLibraryError('sim_pairs: %d pairs above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
-                              % (total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
+    """sim_pairs' refusals: int64 pair_index, the int32 list it is made from, float32 scores when asked for."""
+    _list_room('sim_pairs', total, free, noun='pairs', listed='%d pairs', limit_name='max_pairs', limit=max_pairs,
+               item_bytes=24 if with_scores else 20,
+               hint='raise the threshold, or take the k most similar gates per node with ops.sim_topk / similar_gates')
 
 
 def sim_pairs(x, graph_ptr=None, threshold=SIM_THRESHOLD, with_scores=False, max_pairs=None, eps=1e-8):
@@ -1188,20 +1188,12 @@ def sim_pairs(x, graph_ptr=None, threshold=SIM_THRESHOLD, with_scores=False, max
     with torch.no_grad():
         N, H = y.shape
         dev = y.device
-        gp, G = _sim_graphs(graph_ptr, dev)
+        gp, G = _pair_graphs(graph_ptr, dev)
         common = (H, N, ptr(y), H, ptr(gp), G, float(threshold))
-        n_sel = torch.empty(N, dtype=I32, device=dev)
-        _hip.call('mgv_sim_select_count', *common, ptr(n_sel))
-        row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
-        total = int(row_ptr[-1])                                      # the read-back
-        free, _ = torch.cuda.mem_get_info(dev)
-        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # as _dense_fits
-        _sim_room(total, with_scores, max_pairs, free)
-        col = torch.empty(total, dtype=I32, device=dev)
-        score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
-        _hip.call('mgv_sim_select_fill', *common, ptr(row_ptr), total, ptr(col), ptr(score))
-        rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=dev), row_ptr[1:] - row_ptr[:-1], output_size=total)
+        row_ptr, col, score = _count_scan_fill('mgv_sim_select_count', 'mgv_sim_select_fill', N, common, dev, with_scores,
+                                               lambda total, free: _sim_room(total, with_scores, max_pairs, free))
+        rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=dev), row_ptr[1:] - row_ptr[:-1],
+                                       output_size=col.numel())
         return torch.stack([rows, col.to(torch.int64)]), row_ptr, score
 
 
@@ -1235,7 +1227,7 @@ def pair_profile(s, t, edges, graph_ptr=None, sigmoid=True, skip_self=False):
     (mgv_pair_hist), the decisions the bits of pair_select's: counts_above(profile)[g, j] is the number of links pair_select would
     list for graph g at threshold edges[j].  Integer atomics: exact and the same from call to call.  No grad."""
     if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
-        _sim_width(s, 'pair_profile')
+        _pair_width(s, 'pair_profile')
     with torch.no_grad():
         sd, lds, td, ldt, H = _pair_operands(s, t)
         N = sd.shape[0]
@@ -1244,7 +1236,7 @@ def pair_profile(s, t, edges, graph_ptr=None, sigmoid=True, skip_self=False):
                                   % (N, td.shape[0]))
         dev = sd.device
         e = _profile_edges(edges, dev)
-        gp, G = _sim_graphs(graph_ptr, dev)
+        gp, G = _pair_graphs(graph_ptr, dev)
         hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=dev)
         _hip.call('mgv_pair_hist', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), int(bool(skip_self)), ptr(e), e.numel(),
                   ptr(hist))
@@ -1254,7 +1246,7 @@ def pair_profile(s, t, edges, graph_ptr=None, sigmoid=True, skip_self=False):
 def _unit_profile(y, e, graph_ptr):
     """mgv_sim_hist on unit rows y and a device table e -> int64 [G, B + 1]."""
     N, H = y.shape
-    gp, G = _sim_graphs(graph_ptr, y.device)
+    gp, G = _pair_graphs(graph_ptr, y.device)
     hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=y.device)
     _hip.call('mgv_sim_hist', H, N, ptr(y), H, ptr(gp), G, ptr(e), e.numel(), ptr(hist))
     return hist if gp is None else hist[:G]
@@ -1265,7 +1257,7 @@ def sim_profile(x, edges, graph_ptr=None, eps=1e-8):
     (v > u), half the tiles (mgv_sim_hist).  counts_above(profile)[g, j] is the number of pairs sim_pairs lists for graph g at
     threshold edges[j], as integers.  Zero rows (primary inputs) score 0 with everything; equal rows score within (2H + 6) 2^-24 of
     1, not exactly 1."""
-    _sim_width(x, 'sim_profile')
+    _pair_width(x, 'sim_profile')
     y = row_unit(x, eps)
     with torch.no_grad():
         return _unit_profile(y, _profile_edges(edges, y.device), graph_ptr)
@@ -1361,7 +1353,7 @@ def sim_threshold_for(x, max_pairs, graph_ptr=None, lo=0.0, bins=64, max_rounds=
     Ties are the caller's to understand: 5,000 equal gates are 12.5 M pairs at ONE cosine value, which a threshold takes or leaves
     as a whole, so the tight answer can lie far below max_pairs.  Zero rows score 0 with everything and never pass a threshold
     >= 0; equal rows score within (2H + 6) 2^-24 of 1."""
-    _sim_width(x, 'sim_threshold_for')
+    _pair_width(x, 'sim_threshold_for')
     y = row_unit(x, eps)
     with torch.no_grad():
         return threshold_search(lambda e: _unit_profile(y, _profile_edges(e, y.device), graph_ptr), max_pairs, lo=lo, hi=2.0, bins=bins,
@@ -1495,7 +1487,7 @@ def sim_classes(x, graph_ptr=None, threshold=SIM_THRESHOLD, min_size=2, route='w
     y = row_unit(x, eps)
     with torch.no_grad():
         N, H = y.shape
-        gp, G = _sim_graphs(graph_ptr, y.device)
+        gp, G = _pair_graphs(graph_ptr, y.device)
         parent, status = _cc_forest(N, y.device)
         _hip.call('mgv_sim_union', H, N, ptr(y), H, ptr(gp), G, float(threshold), ptr(parent), ptr(status))
         label = _cc_labels(N, parent)
