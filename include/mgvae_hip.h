@@ -411,6 +411,29 @@ int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int
  * clamped to it.  Arguments and refusals as mgv_pair_hist. */
 int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B, int64_t* hist,
                  void* stream);
+/* ---- the rank of every true link among ALL candidates of its node (added functionality; exact MRR / Hits@K / mean rank over the full
+ * candidate set, where `test` ranks E positives against sampled non-edges: digae_layer.py:31-33, digae_model.py:118-122;
+ * csrc/pair_scores.hip).  One walk of mgv_pair_select_count with a LIST of thresholds per row where that entry has one scalar for
+ * everybody: for row u and every j in [thr_ptr[u], thr_ptr[u+1])
+ *     n_gt[j] = #{candidates v of u : score(u, v) >  thr[j]}        n_eq[j] = #{candidates v of u : score(u, v) == thr[j]}.
+ * Candidates are exactly those of mgv_pair_topk / mgv_pair_select_count: the columns of u's own graph (NULL graph_ptr: the whole
+ * batch), without v = u when skip_self; a NaN score is nobody's candidate.  The score is the RAW dot product, the order mgv_pair_topk
+ * ranks by — a float32 sigmoid saturates and would invent ties, so there is no `sigmoid` argument.  With thr = mgv_pair_scores_at
+ * (sigmoid = 0) of row u's links, 1 + n_gt and n_gt + n_eq are the best and the worst rank of each link, and a link always finds
+ * itself (n_eq >= 1): both sides of every comparison are the bits of one arithmetic.  A NaN threshold gets (0, 0), both comparisons
+ * being false; -inf and +inf are thresholds like any other.
+ * thr_ptr [N+1] int32 and thr [T] float32 on the device, T = thr_ptr[N].  EACH ROW'S LIST MUST ASCEND, NaNs last (duplicates allowed;
+ * the order torch.sort gives): the kernel searches it.  A list that does not ascend makes only its own counts meaningless.  Whatever
+ * thr_ptr holds between its ends, a row's range is clamped into [0, T) and no index outside it is read or written.
+ * n_gt, n_eq int32 [T] are WRITTEN for every listed j by exactly one owner (32 entries of a row's list per pass of its tile, int32
+ * counters in LDS, plain stores): no global atomics, nothing is zero-filled by the caller, two calls give the same bytes; entries
+ * that no row lists are not touched.
+ * Refused before anything is launched: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); a bad row stride or alignment, N out of range
+ * (N < 0 or N > 2^31 - 1), a graph_ptr that does not start at 0 and end at N, a NULL thr_ptr, a thr_ptr whose two ends are not 0 and
+ * a T with 0 <= T < 2^31 (its ends are read back in the same small blocking copy as graph_ptr's ends), a NULL thr, n_gt or n_eq with
+ * T > 0: MGV_EINVAL.  N = 0 or T = 0 launches nothing. */
+int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int skip_self,
+                         const int32_t* thr_ptr, const float* thr, int32_t* n_gt, int32_t* n_eq, void* stream);
 /* ---- connected components on the device (added functionality; csrc/components.hip, csrc/mgv_unionfind.h): candidate classes of the
  * relation "same graph and cosine > threshold" on hf (trainer.py:158-160) and components of decoded link lists (digae_layer.py:31-33).
  * One forest parent[N] int32, N < 2^31, with 0 <= parent[x] <= x at all times: a root is only ever hooked under a smaller root

@@ -9,6 +9,7 @@
 // The same entries on unit rows (k_row_unit) are the cosine search on hf, the inference side of the functional loss (trainer.py:158-160);
 // its thresholded pairs come from the symmetric form of the selection walk (k_pair_select<.., SYM>).
 // The classes of that relation come from the same walk with a union-find in place of the lists (k_sim_union, mgv_unionfind.h).
+// The rank of a true link among all candidates of its node comes from the same walk with a list of thresholds per row (k_pair_rank).
 #include "mgv_common.h"
 #include "mgv_unionfind.h"
 #include "../../include/mgvae_hip.h"
@@ -592,6 +593,136 @@ __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* 
     }
 }
 
+// ---------------------------------------------------------------------------------- ranks: counts against each row's own thresholds
+// The walk of k_pair_select<H, false> — the same tiles and candidate<false> on the raw score — where the count compares with one scalar
+// for everybody, a row compares with ITS list thr[thr_ptr[u] .. thr_ptr[u+1]) (ascending, NaNs last: the entry's contract) and every
+// listed j gets n_gt[j] = #{candidates > thr[j]} and n_eq[j] = #{candidates == thr[j]}: the rank of a true link among all candidates of
+// its node, as integers, when thr holds mgv_pair_scores_at of the row's links (the same bits the walk compares).
+// Passes.  A list is taken kRankPass = 32 entries at a time: in pass p row i holds entries [32 p, 32 p + 32) of its list in tb (LDS,
+// padded with +inf) and the tile repeats its column walk until its longest list is done; a tile whose rows list nothing walks nothing.
+// Counting.  A score first meets the row's smallest threshold of the pass (rmin, in registers; NaN for an empty list: nothing passes) —
+// a trained decoder scores true links high, so nearly every candidate leaves there.  The rest take a branch-free binary search,
+// pos = #{entries of the pass < v} in 0 .. 32 (six dependent LDS reads; a row that lists at most two entries in the pass — a gate's
+// fan-ins — answers from two registers instead: 1.60 -> 1.25 times the count walk on a fitted 65,536-node AIG, 2.91 -> 1.63 on random
+// rows, NOTEBOOK 2026-10-19, ninth entry), and add 1 to cgt[row][pos] (pos = 0 says nothing: v is above none) and, where
+// tb[row][pos] == v, to ceq[row][pos] — the first of the entries equal to v.  int32 ds atomics: exact in any order, and a row has fewer
+// than 2^31 candidates.  After the walk entry k of a row reads n_gt = sum of cgt[row][b] over b > k (ascending: v > thr_k exactly when
+// pos > k) and n_eq = sum of ceq[row][b] over the b of the pass with tb[b] == tb[k] (duplicates share the first one's counter), and
+// WRITES both with plain stores; a NaN threshold writes (0, 0).  Every listed j has one owner (its row's workgroup, its pass): no
+// global atomics, nothing to zero beforehand, the same bytes from call to call.
+// Whatever thr_ptr holds, a row's range is clamped into [0, T) as row_ranges clamps graph_ptr, and a list that does not ascend only
+// makes its own counts meaningless: pos stays in 0 .. 32.
+// LDS: score tile + 2 x 64 x 33 counters (16,896 B) + 64 x 33 thresholds (8,448 B) + 1,024 B of row tables = 60,160 B at H = 128
+// (two workgroups per CU), 43,776 B at H = 64, 35,584 B at H = 32, 31,488 B at H = 16.  Waves per SIMD: 2 at H = 128 (229 VGPRs + 20
+// AGPRs, as k_pair_select<128>) and at H = 64 (163 + 20), 3 at H = 32 (139 + 20) and H = 16 (125 + 20); registers bound it, not LDS.
+constexpr int kRankPass = 32;
+constexpr int kRankLd = kRankPass + 1;     // row stride of tb / cgt / ceq: bin 32 exists, and the four rows of a lane lie in four banks
+
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_pair_rank(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
+                                                        int G, int skip_self, const int32_t* thr_ptr, int T, const float* thr,
+                                                        int32_t* n_gt, int32_t* n_eq) {
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], lb[kPairTile], ln[kPairTile];
+    __shared__ float tb[kPairTile * kRankLd];
+    __shared__ int cgt[kPairTile * kRankLd], ceq[kPairTile * kRankLd];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    row_ranges(N, u0, gp, G, rlo, rhi);
+    if (threadIdx.x < kPairTile) {                         // the row's list [lb, lb + ln): inside [0, T) whatever thr_ptr holds
+        const int64_t u = u0 + threadIdx.x;
+        int b = 0, e = 0;
+        if (u < N) {
+            b = thr_ptr[u]; e = thr_ptr[u + 1];
+            b = b < 0 ? 0 : (b > T ? T : b);
+            e = e < b ? b : (e > T ? T : e);
+        }
+        lb[threadIdx.x] = b; ln[threadIdx.x] = e - b;
+    }
+    __syncthreads();
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
+    int longest = 0;
+    for (int i = 0; i < kPairTile; ++i) longest = ln[i] > longest ? ln[i] : longest;
+    const int64_t row0 = u0 + 16 * w;
+    const int sigmoid = 0;                                 // ranks are by the raw score, the order of k_pair_topk
+    int mylo[4], myhi[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { mylo[g] = rlo[16 * w + 4 * q + g]; myhi[g] = rhi[16 * w + 4 * q + g]; }
+    float a[H / 4];
+    load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
+    for (int p0 = 0; p0 < longest; p0 += kRankPass) {
+        __syncthreads();                                   // the previous pass has read its counters
+        for (int e = threadIdx.x; e < kPairTile * kRankLd; e += kThreads) {
+            const int i = e / kRankLd, k = e % kRankLd;
+            tb[e] = (k < kRankPass && p0 + k < ln[i]) ? thr[lb[i] + p0 + k] : INFINITY;
+            cgt[e] = 0; ceq[e] = 0;
+        }
+        __syncthreads();
+        float rmin[4], rsec[4];                            // a list of one or two (a gate's fan-ins) is searched in registers
+        bool two[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int lr = 16 * w + 4 * q + g;
+            rmin[g] = p0 < ln[lr] ? tb[lr * kRankLd] : NAN;
+            rsec[g] = tb[lr * kRankLd + 1];
+            two[g] = ln[lr] - p0 <= 2;
+        }
+        if (clo < chi) {
+            int64_t ct0, ct1;
+            tile_span<false>(clo, chi, ct0, ct1);
+            float4 nxt[H / 16];
+            tile_load<H>(nxt, t, ldt, ct0 * kPairTile, N);
+            for (int64_t ct = ct0; ct < ct1; ++ct) {
+                __syncthreads();
+                tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+                __syncthreads();
+                if (ct + 1 < ct1) tile_load<H>(nxt, t, ldt, (ct + 1) * kPairTile, N);
+                f32x4 acc[4];
+                tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int64_t col = ct * kPairTile + 16 * c + r;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        float v;
+                        if (!(candidate<false>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], skip_self, sigmoid, v) && v >= rmin[g]))
+                            continue;
+                        const int base = (16 * w + 4 * q + g) * kRankLd;
+                        int pos = 0;
+                        float at;                              // tb[pos]
+                        if (two[g]) {                          // entries 2 .. of the pass are +inf
+                            pos = (rmin[g] < v ? 1 : 0) + (rsec[g] < v ? 1 : 0);
+                            at = pos == 0 ? rmin[g] : (pos == 1 ? rsec[g] : INFINITY);
+                        } else {
+#pragma unroll
+                            for (int step = kRankPass / 2; step > 0; step >>= 1) pos += tb[base + pos + step - 1] < v ? step : 0;   // <= 31
+                            pos += tb[base + pos] < v ? 1 : 0; // <= 32: column 32 of tb is +inf and is never below v
+                            at = tb[base + pos];
+                        }
+                        if (pos > 0) atomicAdd(&cgt[base + pos], 1);
+                        if (at == v) atomicAdd(&ceq[base + pos], 1);     // (bin 32, the padding, is never read back)
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < kPairTile * kRankPass; e += kThreads) {
+            const int i = e / kRankPass, k = e % kRankPass;
+            if (p0 + k >= ln[i]) continue;
+            const float x = tb[i * kRankLd + k];
+            int gt = 0, eq = 0;
+            for (int b = 0; b <= kRankPass; ++b) {
+                gt += b > k ? cgt[i * kRankLd + b] : 0;
+                eq += (b < kRankPass && tb[i * kRankLd + b] == x) ? ceq[i * kRankLd + b] : 0;
+            }
+            const int j = lb[i] + p0 + k;                  // < T
+            n_gt[j] = x == x ? gt : 0;
+            n_eq[j] = eq;                                  // NaN == anything is false: 0
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- unit rows
 // y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
 // row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
@@ -836,4 +967,31 @@ extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const fl
 extern "C" int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B,
                             int64_t* hist, void* stream) {
     return pair_hist_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, 0, true, edges, B, hist, (hipStream_t)stream);
+}
+
+extern "C" int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                    int skip_self, const int32_t* thr_ptr, const float* thr, int32_t* n_gt, int32_t* n_eq, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL);                           // node ids are int32
+    MGV_CHECK_ARG(graph_ptr == nullptr || G >= 0);
+    MGV_CHECK_ARG(thr_ptr != nullptr);
+    // the two ends of both tables in one blocking step: graph_ptr from 0 to N (as pair_walk_args reads it), thr_ptr from 0 to T
+    int32_t ends[4] = {0, (int32_t)N, 0, 0};
+    hipError_t e = hipMemcpyAsync(&ends[2], thr_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&ends[3], thr_ptr + N, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && graph_ptr != nullptr) e = hipMemcpyAsync(&ends[0], graph_ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && graph_ptr != nullptr) e = hipMemcpyAsync(&ends[1], graph_ptr + G, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return (int)e;
+    MGV_CHECK_ARG(ends[0] == 0 && (int64_t)ends[1] == N);
+    MGV_CHECK_ARG(ends[2] == 0 && ends[3] >= 0);                          // T = thr_ptr[N] is an int32: below 2^31
+    const int T = ends[3];
+    if (N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H));
+    if (T == 0) return MGV_OK;                                            // nothing is listed: nothing to write
+    MGV_CHECK_ARG(thr != nullptr && n_gt != nullptr && n_eq != nullptr);
+    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_pair_rank<HH>, N, st, N, s, lds, t, ldt, graph_ptr, G, skip_self, thr_ptr, T, thr, n_gt,
+                                            n_eq));
+    MGV_LAUNCH_RET();
 }

@@ -155,6 +155,18 @@ class FunctionalModel(nn.Module):
             s, t = self._decoder_halves(hs)
             return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
+    def link_ranking(self, hs, edge_index, graph_ptr, ks=(1, 3, 10, 50), by='dst', filtered=True, plan=None):
+        """(RankMetrics, LinkRanks) on st = hs_decompose(hs): where every true link stands among ALL candidates of its node — by='dst',
+        the reconstruction question, every true fan-in of a gate among all gates of its circuit — as exact MRR, Hits@K (for both ends
+        of a tie) and rank sums per graph (ops.rank_metrics), with the per-link ranks in edge_index's order (ops.link_ranks: one
+        all-pairs walk per 32 links of a tile's busiest node, no N x N array).  filtered: a gate's other true links do not count
+        against a link.  Added functionality: link_metrics and the reference's `test` rank against sampled non-edges, whose AUC
+        saturates; reconstruction_counts sees the full adjacency only in aggregate at a threshold."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            ranks = ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
+            return ops.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
+
     def reconstruct_edges(self, hs, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None) on st = hs_decompose(hs): the graph the decoder
         reconstructs, every pair inside a graph with sigma > threshold, as (source, target) rows listed per source in ascending target

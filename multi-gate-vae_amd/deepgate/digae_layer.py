@@ -50,6 +50,11 @@ class DirectedInnerProductDecoder(nn.Module):
         int64 [G, B, 4] of ops.reconstruction_curve — true positives, predicted positives, edges, ordered pairs per graph."""
         return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
+    def rank(self, s, t, edge_index, graph_ptr=None, by='src', skip_self=False, filtered=True, plan=None):
+        """Where every listed link stands among ALL candidates of its node by raw score (added functionality: the reference's `test`
+        ranks against sampled non-edges): LinkRanks(rank_lo, rank_hi, valid) of ops.link_ranks, in the caller's edge order."""
+        return ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, skip_self=skip_self, filtered=filtered, plan=plan)
+
 
 def _classes_once(x, classes, width):
     """Integer one-hot rows -> (rows, ids) once per encoder call (feature_classes runs a torch.unique with a host read-back); float

@@ -37,6 +37,14 @@ class DirectedGAE(torch.nn.Module):
         with torch.no_grad():
             return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
+    def link_ranking(self, s, t, edge_index, graph_ptr, ks=(1, 3, 10, 50), by='dst', filtered=True, plan=None):
+        """(RankMetrics, LinkRanks): exact MRR, Hits@K and rank sums per graph over the FULL candidate set, and the per-link ranks
+        behind them (ops.rank_metrics of ops.link_ranks) — by='dst': every true link among all nodes of its graph that could feed its
+        target; `test` ranks against sampled non-edges only.  Added functionality."""
+        with torch.no_grad():
+            ranks = ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
+            return ops.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
+
     def reconstruct_edges(self, s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None): every pair inside a graph that the decoder calls an
         edge (score > threshold) as (source, target) rows, listed per source or (by='dst') per target (ops.reconstruct_edges).  Added

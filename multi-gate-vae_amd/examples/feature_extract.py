@@ -12,6 +12,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --equivalences_max 1000   # the same, at most 1000 pairs per batch
     python examples/feature_extract.py --type aig --synthetic 4 --similarity_profile 12   # + pairs per graph above 1 - 2^-j, j = 1..12
     python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
+    python examples/feature_extract.py --type aig --synthetic 4 --link_ranking 1,10    # + exact MRR / Hits@1 / Hits@10 of the true fan-ins
 """
 import argparse
 import os
@@ -70,7 +71,12 @@ def main(argv=None):
                     'adjacency at B evenly spaced thresholds in (0, 1), i / (B + 1): name/recon_thresholds [B] and name/recon_curve '
                     '[B, 4] = true positives, predicted positives, edges, ordered pairs (Model.reconstruction_curve, one walk; '
                     '1 <= B <= 256)')
+    ap.add_argument('--link_ranking', default='', metavar='K1,K2,...', help='also print, per circuit, where its true links stand among ALL '
+                    'candidates by target — every true fan-in of a gate ranked against all gates of the circuit, the gate\'s other fan-ins '
+                    'left out: links ranked, MRR, Hits@K for every K (for the best and the worst place a tie allows) and the mean rank '
+                    '(Model.link_ranking; exact, no sampled negatives)')
     a = ap.parse_args(argv)
+    rank_ks = [int(k) for k in a.link_ranking.split(',') if k.strip()]
     sim_thr = [1.0 - 2.0 ** -j for j in range(1, min(a.similarity_profile, 20) + 1)]
     rc_thr = [float(np.float32(i / (a.recon_curve + 1.0))) for i in range(1, a.recon_curve + 1)]
     dev = torch.device('cuda:0')
@@ -114,6 +120,9 @@ def main(argv=None):
                 sim_above = model.similarity_profile(hf, sim_thr, graph_ptr=batch.graph_ptr).cpu().numpy()
             if rc_thr:
                 curve = model.reconstruction_curve(hs, batch.edge_index, batch.graph_ptr, rc_thr).cpu().numpy()
+            if rank_ks:
+                rm = [x.cpu() for x in model.link_ranking(hs, batch.edge_index, batch.graph_ptr, ks=rank_ks, by='dst',
+                                                          plan=getattr(batch, '_mgv_plan', None))[0]]
             if eq_thr is not None:
                 eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=eq_thr, with_scores=True)
                 eq, eq_cos = eq.cpu().numpy(), eq_cos.cpu().numpy()
@@ -124,6 +133,11 @@ def main(argv=None):
                 cptr = np.searchsorted(cl_mem[cl_ptr[:-1]], ptr).tolist()      # classes come by label and never cross graphs
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if rank_ks:
+                    n = max(int(rm[0][k]), 1)
+                    hits = ' '.join('Hits@%d %.4f..%.4f' % (K, int(rm[2][k, j]) / n, int(rm[1][k, j]) / n) for j, K in enumerate(rank_ks))
+                    print('[INFO] %s: link ranking by target: %d links ranked, MRR %.6f, %s, mean rank %.2f..%.2f'
+                          % (name, int(rm[0][k]), float(rm[5][k]), hits, int(rm[3][k]) / n, int(rm[4][k]) / n))
                 if a.classes is not None:
                     cp = cl_ptr[cptr[k]:cptr[k + 1] + 1]
                     out[name + '/eq_label'] = (cl_label[ptr[k]:ptr[k + 1]] - ptr[k]).astype(np.int32)
