@@ -501,6 +501,30 @@ int mgv_recon_loss_bwd_csr(int H, int64_t N, const float* s, const float* t, int
 int mgv_recon_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, const float* gscale, int K,
                           const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node, const int32_t* seg_e0,
                           const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws, float* out, void* stream);
+/* The training step's loss in ONE walk of the lists: mgv_recon_loss_bwd_csr's walk (same ranges, chunks and arithmetic: ds / dt come out
+ * bit-identical to it at *gscale == expect_scale, a by-value float here because the upstream gradient is not known yet when the
+ * forward runs) which, on the out-list entries — every pair exactly once — also does mgv_recon_loss_fwd's work: sums[0..1] += the
+ * two loss sums (that entry's float terms, from a score formed its way — the products of the dot rounded one by one, where the
+ * gradient's score is contracted into fmas — added per thread in double, per-workgroup rows in `workspace` (>= 2 * grid doubles,
+ * mgv_sum_workspace_doubles() suffices) added in index order: the same bits from run to run), counts[0..3] += {TP, FP, TN, FN},
+ * equal to that entry's on every pair.
+ * No pair arrays, no pred_bin.  Positive lists longer than skip_pos_longer_than (> 0) are left to mgv_recon_step_heavy_lists. */
+int mgv_recon_step_csr(int H, int64_t N, const float* s, const float* t, int ld, const int32_t* pos_out_ptr,
+                       const int32_t* pos_out_dst, const int32_t* pos_in_ptr, const int32_t* pos_in_src, int64_t Epos,
+                       const int32_t* neg_out_ptr, const int32_t* neg_out_dst, const int32_t* neg_in_ptr,
+                       const int32_t* neg_in_src, int64_t Eneg, float expect_scale, double* sums, uint64_t* counts, float* ds,
+                       float* dt, int skip_pos_longer_than, double* workspace, int64_t workspace_doubles, void* stream);
+/* mgv_recon_heavy_lists for expect_scale by value; with which = 0 (the out lists) the segments' pairs also add their loss terms to
+ * sums[0] and their TP / FN to counts[0] / counts[3] (workspace >= min(S, 4096) doubles).  which = 1: sums, counts, workspace unused. */
+int mgv_recon_step_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, float expect_scale, int K,
+                               const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node,
+                               const int32_t* seg_e0, const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws,
+                               float* out, double* sums, uint64_t* counts, double* workspace, int64_t workspace_doubles,
+                               void* stream);
+/* rows[0 .. n_floats) *= *g_dev / expect_scale — unless *g_dev == expect_scale: then every workgroup returns after reading the scalar
+ * and the rows keep their bits.  The backward of the one-walk loss: the rows were formed for expect_scale in the forward.
+ * rows 16-byte aligned; expect_scale 0 or NaN: MGV_EINVAL. */
+int mgv_rows_rescale_unless(int64_t n_floats, float* rows, const float* g_dev, float expect_scale, void* stream);
 /* ---- link-prediction ranking metrics (digvae_model.py:177-189, digae_model.py:156-168: `test` decodes both edge sets with
  * sigmoid=True, copies every score to the host and calls sklearn's roc_auc_score / average_precision_score).  Here the ranking stays
  * on the device (csrc/link_metrics.hip): keys -> mgv_sort_pairs(4, n, keys, sorted, order, 32, ...) -> rank.

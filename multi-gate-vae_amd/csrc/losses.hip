@@ -12,6 +12,21 @@ __device__ __forceinline__ void atomic_add4(float* p, const float4& v) {
     atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
+// The dot product of the loss's FORWARD, wherever it is formed (k_recon, the one-walk kernels): four products rounded one by one and
+// added left to right, never contracted into fmas — every kernel that decides `p > 0.5` for a pair then decides on the same bits.
+__device__ __forceinline__ float dot4_plain(const float4& a, const float4& b) {
+#pragma clang fp contract(off)
+    return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+}
+
+// The same row as a value the optimiser cannot trace back to it.  The one-walk kernels form two scores of one pair from the same
+// registers; left alone, the compiler merges the products the two share into one instruction that may no longer be contracted, and
+// the gradient's score — which must keep the bits it has in the kernels without loss terms — comes out rounded differently.
+__device__ __forceinline__ float4 opaque4(float4 v) {
+    asm("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
+    return v;
+}
+
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
     // 64-lane shuffle reduction on the two 32-bit halves is not available for doubles: go through LDS
     const int tid = threadIdx.x;
@@ -86,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs a) {
             x = ld4(a.s + u * a.ld + 4 * lr);
             y = ld4(a.t + v * a.ld + 4 * lr);
         }
-        const float val = group_sum<LPR>(dot4(x, y));
+        const float val = group_sum<LPR>(dot4_plain(x, y));
         const float p = sigmoidf_(val);
         if (!BWD) {
             if (ok && lr == 0) {
@@ -157,15 +172,25 @@ __global__ __launch_bounds__(kThreads) void k_recon_bwd_pull(int64_t N, const fl
 //     memory round trip per four partners instead of one per partner: the lists average 1.6-2.6 entries each, 8 per node).
 //   * Workgroups are dealt round-robin over the 8 XCDs (observed placement, speed only): XCD x takes the x-th CONTIGUOUS eighth of
 //     the nodes, so the partners of the positive lists (neighbours in the same circuit, nearby ids) are served by the XCD's own L2.
-template <int H>
+// STEP: the loss's forward in the same walk.  The out-list entries are every pair exactly once, with both rows in registers: their
+// loss terms and hits are k_recon's, bit for bit — from a score of their own, dot4_plain's (the walk's gradient score contracts its dot
+// product into fmas, k_recon's does not: the two differ in the last bits and one of config 2's 13.1 M pairs then falls on the other
+// side of p > 0.5).  The terms are summed per thread in double and leave as this workgroup's slab row [2] (added in index order
+// afterwards: the same bits from run to run), the four counters as integer atomics.  The upstream gradient is not known yet:
+// the rows are formed for the by-value `gval` (mgv_rows_rescale_unless mends them if the backward brings another).
+template <int H, bool STEP>
 __global__ __launch_bounds__(kThreads) void k_recon_bwd_pull2(int64_t N, const float* s, const float* t, int ld,
                                                               const int32_t* pout_ptr, const int32_t* pout_dst, const int32_t* pin_ptr,
                                                               const int32_t* pin_src, int64_t Ep, const int32_t* nout_ptr,
                                                               const int32_t* nout_dst, const int32_t* nin_ptr, const int32_t* nin_src,
-                                                              int64_t En, const float* gscale, float* ds, float* dt, int skip_len) {
+                                                              int64_t En, const float* gscale, float gval, float* ds, float* dt, int skip_len,
+                                                              double* slab, unsigned long long* cnt) {
     constexpr int LPR = H / 4, RPB = kThreads / LPR, K = 4;
     const int lr = threadIdx.x % LPR, slot = threadIdx.x / LPR;
-    const float wp = Ep > 0 ? -(*gscale) / (float)Ep : 0.f, wn = En > 0 ? (*gscale) / (float)En : 0.f;
+    const float g = STEP ? gval : *gscale;
+    const float wp = Ep > 0 ? -g / (float)Ep : 0.f, wn = En > 0 ? g / (float)En : 0.f;
+    double lp = 0, ln = 0;
+    unsigned int tp = 0, fp = 0, tn = 0, fn = 0;
     // node range of this workgroup: XCD-contiguous when the grid is a multiple of 8
     int64_t first, end, stride;
     if ((gridDim.x & 7) == 0) {
@@ -219,6 +244,14 @@ __global__ __launch_bounds__(kThreads) void k_recon_bwd_pull2(int64_t N, const f
                     const float p = sigmoidf_(group_sum<LPR>(dot4(out ? su : tu, v[k])));
                     const float c = pos ? wp * p * (1.0f - p) / (p + 1e-15f) : wn * p * (1.0f - p) / ((1.0f - p) + 1e-15f);
                     if (out) gs = fma4(c, v[k], gs); else gt = fma4(c, v[k], gt);
+                    if (STEP && out) {
+                        const float q = sigmoidf_(group_sum<LPR>(dot4_plain(opaque4(su), v[k])));       // k_recon's p of this pair
+                        const bool hit = q > 0.5f;
+                        if (lr == 0) {
+                            if (pos) { lp -= (double)logf(q + 1e-15f); tp += hit; fn += !hit; }
+                            else     { ln -= (double)logf((1.0f - q) + 1e-15f); fp += hit; tn += !hit; }
+                        }
+                    }
                 }
             }
 #pragma unroll
@@ -227,19 +260,36 @@ __global__ __launch_bounds__(kThreads) void k_recon_bwd_pull2(int64_t N, const f
         st4(ds + u * ld + 4 * lr, gs);
         st4(dt + u * ld + 4 * lr, gt);
     }
+    if (STEP) {
+        __shared__ double red[kThreads];
+        const double sp = block_sum_d(lp, red), sn = block_sum_d(ln, red);
+        const double c0 = block_sum_d((double)tp, red), c1 = block_sum_d((double)fp, red);
+        const double c2 = block_sum_d((double)tn, red), c3 = block_sum_d((double)fn, red);
+        if (threadIdx.x == 0) {
+            slab[2 * blockIdx.x + 0] = sp; slab[2 * blockIdx.x + 1] = sn;
+            atomicAdd(cnt + 0, (unsigned long long)c0); atomicAdd(cnt + 1, (unsigned long long)c1);
+            atomicAdd(cnt + 2, (unsigned long long)c2); atomicAdd(cnt + 3, (unsigned long long)c3);
+        }
+    }
 }
 
 // One segment of a heavy positive list per workgroup: sum over the segment's partners p of c(own, p) * row(p), c from the own row's
 // dot product with the partner (which = 0: own s[u], partners t[.], result for ds[u]; which = 1: own t[u], partners s[.], for dt[u]).
 // The 16 lane groups take partners strided, their partial sums meet in LDS in group order: deterministic.
-template <int H>
+// STEP (see k_recon_bwd_pull2): with which = 0 the segments' pairs also leave their loss terms (k_recon's, from dot4_plain: slab
+// row [1]) and TP / FN counts.
+template <int H, bool STEP>
 __global__ __launch_bounds__(256) void k_recon_heavy_seg(int S, const int32_t* seg_node, const int32_t* seg_e0, const int32_t* seg_e1,
                                                          const int32_t* nodes, const float* s, const float* t, int ld, const int32_t* list,
-                                                         int which, int64_t Ep, const float* gscale, float* partial) {
+                                                         int which, int64_t Ep, const float* gscale, float gval, float* partial,
+                                                         double* slab, unsigned long long* cnt) {
     constexpr int LPR = H / 4, G = 256 / LPR;
+    static_assert(kThreads == 256, "block_sum_d reduces kThreads values");
     __shared__ __attribute__((aligned(16))) float s_p[G][H];
     const int lr = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    const float wp = -(*gscale) / (float)Ep;
+    const float wp = -(STEP ? gval : *gscale) / (float)Ep;
+    double lp = 0;
+    unsigned int tp = 0, fn = 0;
     for (int sg = blockIdx.x; sg < S; sg += gridDim.x) {
         const int64_t u = nodes[seg_node[sg]];
         const float4 own = ld4((which ? t : s) + u * ld + 4 * lr);
@@ -249,6 +299,11 @@ __global__ __launch_bounds__(256) void k_recon_heavy_seg(int S, const int32_t* s
             const float4 v = ld4(other + (int64_t)list[e] * ld + 4 * lr);
             const float p = sigmoidf_(group_sum<LPR>(dot4(own, v)));
             acc = fma4(wp * p * (1.0f - p) / (p + 1e-15f), v, acc);
+            if (STEP && which == 0) {
+                const float q = sigmoidf_(group_sum<LPR>(dot4_plain(opaque4(own), v)));       // k_recon's p of this pair
+                const bool hit = q > 0.5f;
+                if (lr == 0) { lp -= (double)logf(q + 1e-15f); tp += hit; fn += !hit; }
+            }
         }
         __syncthreads();
         st4(&s_p[grp][4 * lr], acc);
@@ -259,6 +314,26 @@ __global__ __launch_bounds__(256) void k_recon_heavy_seg(int S, const int32_t* s
             st4(partial + (int64_t)sg * H + 4 * lr, tot);
         }
     }
+    if (STEP && which == 0) {
+        __shared__ double red[kThreads];
+        const double sp = block_sum_d(lp, red);
+        const double c0 = block_sum_d((double)tp, red), c3 = block_sum_d((double)fn, red);
+        if (threadIdx.x == 0) {
+            slab[blockIdx.x] = sp;
+            atomicAdd(cnt + 0, (unsigned long long)c0); atomicAdd(cnt + 3, (unsigned long long)c3);
+        }
+    }
+}
+
+// rows *= *g / expect unless *g == expect (the upstream gradient the rows were formed for): then every workgroup returns at once
+__global__ __launch_bounds__(kThreads) void k_rows_rescale_unless(int64_t n, float* rows, const float* g_dev, float expect) {
+    const float g = *g_dev;
+    if (g == expect) return;
+    const float f = g / expect;
+    const int64_t n4 = n / 4;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kThreads)
+        st4(rows + 4 * i, scale4(f, ld4(rows + 4 * i)));
+    if (blockIdx.x == 0 && threadIdx.x < n - 4 * n4) rows[4 * n4 + threadIdx.x] *= f;
 }
 
 // Arbitrary edge lists (the sampled negatives): one edge per H-lane group, one float per lane, so every
@@ -574,9 +649,30 @@ extern "C" int mgv_recon_loss_bwd_csr(int H, int64_t N, const float* s, const fl
     MGV_CHECK_ARG(Eneg == 0 || (neg_out_ptr && neg_out_dst && neg_in_ptr && neg_in_src));
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull2<HH>), dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
+    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull2<HH, false>), dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
                                          N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst,
-                                         neg_in_ptr, neg_in_src, Eneg, gscale, ds, dt, skip_pos_longer_than));
+                                         neg_in_ptr, neg_in_src, Eneg, gscale, 0.f, ds, dt, skip_pos_longer_than, nullptr, nullptr));
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_recon_step_csr(int H, int64_t N, const float* s, const float* t, int ld, const int32_t* pos_out_ptr,
+                                  const int32_t* pos_out_dst, const int32_t* pos_in_ptr, const int32_t* pos_in_src, int64_t Epos,
+                                  const int32_t* neg_out_ptr, const int32_t* neg_out_dst, const int32_t* neg_in_ptr,
+                                  const int32_t* neg_in_src, int64_t Eneg, float expect_scale, double* sums, uint64_t* counts, float* ds,
+                                  float* dt, int skip_pos_longer_than, double* workspace, int64_t workspace_doubles, void* stream) {
+    MGV_CHECK_ARG(s && t && sums && counts && ds && dt && Epos >= 0 && Eneg >= 0 && N >= 0 && ld >= H && ld % 4 == 0 && skip_pos_longer_than >= 0);
+    MGV_CHECK_ARG(Epos == 0 || (pos_out_ptr && pos_out_dst && pos_in_ptr && pos_in_src));
+    MGV_CHECK_ARG(Eneg == 0 || (neg_out_ptr && neg_out_dst && neg_in_ptr && neg_in_src));
+    if (N == 0) return MGV_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int grid = 0;
+    MGV_DISPATCH_H(H, grid = mgv::items_grid(N, mgv::kThreads / (HH / 4)));
+    MGV_CHECK_ARG(workspace && workspace_doubles >= 2 * (int64_t)grid);
+    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull2<HH, true>), dim3(grid), dim3(mgv::kThreads), 0, st,
+                                         N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst,
+                                         neg_in_ptr, neg_in_src, Eneg, nullptr, expect_scale, ds, dt, skip_pos_longer_than, workspace,
+                                         reinterpret_cast<unsigned long long*>(counts)));
+    mgv::launch_slab_sum<double, double>(workspace, grid, 2, 2, sums, st);
     MGV_LAUNCH_RET();
 }
 
@@ -587,9 +683,38 @@ extern "C" int mgv_recon_heavy_lists(int H, const float* s, const float* t, int 
     if (K == 0 || S == 0) return MGV_OK;
     MGV_CHECK_ARG(nodes && node_seg_ptr && seg_node && seg_e0 && seg_e1 && list && partial_ws);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_heavy_seg<HH>), dim3(S < 4096 ? S : 4096), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
-                                         s, t, ld, list, which, Epos, gscale, partial_ws));
+    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_heavy_seg<HH, false>), dim3(S < 4096 ? S : 4096), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
+                                         s, t, ld, list, which, Epos, gscale, 0.f, partial_ws, nullptr, nullptr));
     hipLaunchKernelGGL(mgv::k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial_ws, out, ld, 1);
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_recon_step_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, float expect_scale, int K,
+                                          const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node,
+                                          const int32_t* seg_e0, const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws,
+                                          float* out, double* sums, uint64_t* counts, double* workspace, int64_t workspace_doubles,
+                                          void* stream) {
+    MGV_CHECK_ARG(K >= 0 && S >= 0 && Epos > 0 && s && t && out && ld >= H && ld % 4 == 0 && (which == 0 || which == 1));
+    MGV_CHECK_ARG(which == 1 || (sums && counts));
+    if (K == 0 || S == 0) return MGV_OK;
+    MGV_CHECK_ARG(nodes && node_seg_ptr && seg_node && seg_e0 && seg_e1 && list && partial_ws);
+    const int grid = S < 4096 ? S : 4096;
+    MGV_CHECK_ARG(which == 1 || (workspace && workspace_doubles >= (int64_t)grid));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_heavy_seg<HH, true>), dim3(grid), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
+                                         s, t, ld, list, which, Epos, nullptr, expect_scale, partial_ws, workspace,
+                                         reinterpret_cast<unsigned long long*>(counts)));
+    if (which == 0) mgv::launch_slab_sum<double, double>(workspace, grid, 1, 1, sums, st);
+    hipLaunchKernelGGL(mgv::k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial_ws, out, ld, 1);
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_rows_rescale_unless(int64_t n_floats, float* rows, const float* g_dev, float expect_scale, void* stream) {
+    MGV_CHECK_ARG(n_floats >= 0 && g_dev && expect_scale != 0.f && expect_scale == expect_scale);
+    if (n_floats == 0) return MGV_OK;
+    MGV_CHECK_ARG(rows && (reinterpret_cast<uintptr_t>(rows) & 15) == 0);
+    hipLaunchKernelGGL(mgv::k_rows_rescale_unless, dim3(mgv::items_grid(n_floats, 4 * mgv::kThreads)), dim3(mgv::kThreads), 0,
+                       static_cast<hipStream_t>(stream), n_floats, rows, g_dev, expect_scale);
     MGV_LAUNCH_RET();
 }
 

@@ -235,11 +235,13 @@ class FunctionalModel(nn.Module):
         A never-updated node (hf = 0) has cosine 0 with everything."""
         return ops.sim_at(hf, pair_index)
 
-    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False):
+    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False,
+                   expect_scale=1.0):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the
         hs_decompose node, in `self._hs_pass` for the level sweep (see forward).  `want_rank`: also rank the very pairs the loss
-        uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`."""
+        uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`.  `expect_scale`: the
+        upstream gradient this loss will meet in backward (its weight in the step's total), see ops.ReconLossFn."""
         if pass_hs and hs.requires_grad:
             st, self._hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         else:
@@ -261,7 +263,7 @@ class FunctionalModel(nn.Module):
             neg_edge_index = cache[2]
         if isinstance(neg_edge_index, NegativeEdges):
             neg_csr, neg_edge_index = neg_edge_index.csr, neg_edge_index.edge_index
-        loss, counts, pred_bin = ops.ReconLossFn.apply(st, pos_edge_index, neg_edge_index, want_pred, plan, neg_csr)
+        loss, counts, pred_bin = ops.ReconLossFn.apply(st, pos_edge_index, neg_edge_index, want_pred, plan, neg_csr, expect_scale)
         self.last_confusion = counts        # {TP, FP, TN, FN} on device, no host copy needed for metrics
         self.last_link_metrics = ops.link_record(st, None, pos_edge_index, neg_edge_index) if want_rank else None
         Ep, En = pos_edge_index.shape[1], neg_edge_index.shape[1]

@@ -4,13 +4,13 @@ backward kernels into the reference's Python operator surface.  PyTorch supplies
 streams and the autograd tape; all arithmetic on [N,*] data happens in libmgvae_hip.so.
 """
 from collections import namedtuple
+import math
+import os
 
 import torch
 
 from . import _hip
 from ._hip import HipLibraryError, check, ptr
-
-import os
 
 F32 = torch.float32
 I32 = torch.int32
@@ -1704,16 +1704,39 @@ def sim_classes(x, graph_ptr=None, threshold=SIM_THRESHOLD, min_size=2, route='w
         return (label,) + _class_table(label, min_size, status, 'sim_classes')
 
 
+def _recon_heavy(plan):
+    """((which, segments, list), ...) of the plan's heavy positive lists and the list length from which the per-node walk leaves
+    them to the segment kernels (0: no heavy list)."""
+    heavy = [(0, plan.heavy_segments(True), plan.out_dst), (1, plan.heavy_segments(False), plan.in_src)]
+    return heavy, (plan.HEAVY_ROW if any(hv is not None for _, hv, _ in heavy) else 0)
+
+
 class ReconLossFn(torch.autograd.Function):
     """-mean log(sigma(<s_u,t_v>)+1e-15) over positives - mean log(1-sigma+1e-15) over negatives
     (dg_ae_model_aig.py:108-130) on st = hs_decompose(hs) [N,2H]; also the confusion counters and,
-    on request, pred_bin."""
+    on request, pred_bin.
+    Two routes.  The pair pass (mgv_recon_loss_fwd) with the gradient walk in backward; and, for a training step (plan and neg_csr
+    given, st requires grad, grad mode on at `apply`, no pred_bin wanted), ONE walk of the lists in forward that leaves the loss
+    sums, the counters and the gradient rows for the upstream gradient `expect_scale` (mgv_recon_step_csr).  backward then only
+    compares the upstream gradient it is given with expect_scale on the device and rescales the rows if they differ.
+    MGV_RECON_ONE_PASS=0 keeps every call on the pair pass."""
+
+    @classmethod
+    def apply(cls, st, pos_edge_index, neg_edge_index, want_pred, plan=None, neg_csr=None, expect_scale=1.0):
+        """`expect_scale`: the upstream gradient the caller will bring to backward (Trainer: the loss's weight).  A hint: any other
+        upstream gradient is served as well, by one more pass over the rows."""
+        # (grad mode is off inside forward: whether this call will ever see a backward is decided here)
+        expect_scale = float(expect_scale)
+        one_pass = bool(plan is not None and neg_csr is not None and not want_pred and torch.is_grad_enabled() and st.requires_grad
+                        and st.is_cuda and expect_scale != 0.0 and math.isfinite(expect_scale)
+                        and os.environ.get('MGV_RECON_ONE_PASS', '1') != '0')
+        return super().apply(st, pos_edge_index, neg_edge_index, want_pred, plan, neg_csr, expect_scale if one_pass else None)
 
     @staticmethod
-    def forward(ctx, st, pos_edge_index, neg_edge_index, want_pred, plan=None, neg_csr=None):
+    def forward(ctx, st, pos_edge_index, neg_edge_index, want_pred, plan=None, neg_csr=None, expect_scale=None):
         """`plan`: GraphPlan whose edges are exactly pos_edge_index (any order) -> atomic-free positive half;
         `neg_csr`: (out_ptr, out_dst, in_ptr, in_src) over neg_edge_index (sampling.NegativeEdges) -> atomic-free
-        negative half as well."""
+        negative half as well; `expect_scale` not None: the one-walk route (see `apply`)."""
         std = check(st.detach().contiguous(), F32, 'st')
         N, H2 = std.shape
         H = H2 // 2
@@ -1725,8 +1748,23 @@ class ReconLossFn(torch.autograd.Function):
         counts = torch.zeros(4, dtype=torch.int64, device=dev)
         pred = torch.empty(Ep + En, dtype=torch.int32, device=dev) if want_pred else None
         t_view = std[:, H:]
-        _hip.call('mgv_recon_loss_fwd', H, ptr(std), ptr(t_view), H2, ptr(ps), ptr(pd), Ep, ptr(ns), ptr(nd), En,
-                  ptr(sums), ptr(counts), ptr(pred), *_sw(std.device))
+        ctx.dst_ = ctx.expect_scale = None
+        if expect_scale is not None:
+            dst_ = torch.empty_like(std)
+            heavy, skip = _recon_heavy(plan)
+            _hip.call('mgv_recon_step_csr', H, N, ptr(std), ptr(t_view), H2, ptr(plan.out_ptr), ptr(plan.out_dst), ptr(plan.in_ptr),
+                      ptr(plan.in_src), Ep, *[ptr(c) for c in neg_csr], En, expect_scale, ptr(sums), ptr(counts), ptr(dst_),
+                      ptr(dst_[:, H:]), skip, *_sw(dev))
+            for which, hv, lst in heavy:
+                if hv is not None:
+                    pw = workspace(hv['S'] * H, dev)
+                    _hip.call('mgv_recon_step_heavy_lists', H, ptr(std), ptr(t_view), H2, Ep, expect_scale, hv['K'], ptr(hv['nodes']),
+                              ptr(hv['node_seg_ptr']), hv['S'], ptr(hv['seg_node']), ptr(hv['seg_e0']), ptr(hv['seg_e1']), ptr(lst), which,
+                              ptr(pw), ptr(dst_[:, H:]) if which else ptr(dst_), ptr(sums), ptr(counts), *_sw(dev))
+            ctx.dst_, ctx.expect_scale = dst_, expect_scale      # lives until backward: one more [N, 2H] beside std
+        else:
+            _hip.call('mgv_recon_loss_fwd', H, ptr(std), ptr(t_view), H2, ptr(ps), ptr(pd), Ep, ptr(ns), ptr(nd), En,
+                      ptr(sums), ptr(counts), ptr(pred), *_sw(std.device))
         loss = (sums[0] / max(Ep, 1) + sums[1] / max(En, 1)).to(F32)
         ctx.save_for_backward(std, ps, pd, ns, nd)
         ctx.plan, ctx.neg_csr = plan, neg_csr
@@ -1747,11 +1785,16 @@ class ReconLossFn(torch.autograd.Function):
         H = H2 // 2
         g = gloss.detach().to(F32).reshape(1).contiguous()
         pl = ctx.plan
+        if ctx.dst_ is not None:
+            # the rows the forward's walk left, formed for expect_scale: mended on the device if the upstream gradient is another
+            # (no host read).  They are handed over: a second backward through the same graph takes the walk below.
+            dst_, ctx.dst_ = ctx.dst_, None
+            _hip.call('mgv_rows_rescale_unless', dst_.numel(), ptr(dst_), ptr(g), ctx.expect_scale)
+            return dst_, None, None, None, None, None, None
         if pl is not None and ctx.neg_csr is not None:
             dst_ = torch.empty_like(std)
             # positive lists of high fan-out / fan-in nodes: skipped by the per-node pull, summed per segment by whole workgroups
-            heavy = [(0, pl.heavy_segments(True), pl.out_dst), (1, pl.heavy_segments(False), pl.in_src)]
-            skip = pl.HEAVY_ROW if any(hv is not None for _, hv, _ in heavy) else 0
+            heavy, skip = _recon_heavy(pl)
             _hip.call('mgv_recon_loss_bwd_csr', H, std.shape[0], ptr(std), ptr(std[:, H:]), H2, ptr(pl.out_ptr), ptr(pl.out_dst),
                       ptr(pl.in_ptr), ptr(pl.in_src), ps.numel(), *[ptr(c) for c in ctx.neg_csr], ns.numel(), ptr(g), ptr(dst_),
                       ptr(dst_[:, H:]), skip)
@@ -1761,12 +1804,12 @@ class ReconLossFn(torch.autograd.Function):
                     _hip.call('mgv_recon_heavy_lists', H, ptr(std), ptr(std[:, H:]), H2, ps.numel(), ptr(g), hv['K'], ptr(hv['nodes']),
                               ptr(hv['node_seg_ptr']), hv['S'], ptr(hv['seg_node']), ptr(hv['seg_e0']), ptr(hv['seg_e1']), ptr(lst), which,
                               ptr(pw), ptr(dst_[:, H:]) if which else ptr(dst_))
-            return dst_, None, None, None, None, None
+            return dst_, None, None, None, None, None, None
         dst_ = torch.zeros_like(std)
         csr = (pl.out_ptr, pl.out_dst, pl.in_ptr, pl.in_src) if pl is not None else (None, None, None, None)
         _hip.call('mgv_recon_loss_bwd', H, std.shape[0], ptr(std), ptr(std[:, H:]), H2, ptr(ps), ptr(pd), ps.numel(),
                   *[ptr(c) for c in csr], ptr(ns), ptr(nd), ns.numel(), ptr(g), ptr(dst_), ptr(dst_[:, H:]))
-        return dst_, None, None, None, None, None
+        return dst_, None, None, None, None, None, None
 
 
 def confusion_counts(pred_bin, gt_bin):

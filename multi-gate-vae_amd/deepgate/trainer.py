@@ -169,6 +169,8 @@ class Trainer():
         dev_is_cuda = next(self.model.parameters()).is_cuda
         if getattr(self, '_has_after_hs', None) is None:
             self._has_after_hs = 'after_hs' in inspect.signature(self.model.forward).parameters
+            # weighted_loss(...).backward() brings the reconstruction loss exactly its weight as upstream gradient
+            self._has_expect_scale = 'expect_scale' in inspect.signature(self.model.recon_loss).parameters
         side = self._side_stream() if (self.overlap and dev_is_cuda and self._has_after_hs) else None
 
         def recon(hs, pass_hs=False):
@@ -180,12 +182,15 @@ class Trainer():
                     k = batch._mgv_edge_keys = sorted_edge_keys(batch.edge_index, batch.num_nodes)
             return self.model.recon_loss(hs, batch.train_pos_edge_index, neg, want_pred=want_pred, edge_keys=k,
                                          plan=getattr(batch, '_mgv_plan', None), **({'pass_hs': True} if pass_hs else {}),
-                                         **({'want_rank': True} if want_rank else {}))
+                                         **({'want_rank': True} if want_rank else {}),
+                                         **({'expect_scale': self.rc_prob_func_weight[0]} if self._has_expect_scale else {}))
 
         def recon_on_side(hs):
             # reconstruction branch (hs_decompose -> decoder loss) on a second HIP stream, recorded BEFORE the level sweep: it
-            # runs beside the sweep forward, and its backward (replayed on this stream, enqueued after the sweep backward
-            # because its nodes are older) beside the latency-bound sweep backward
+            # runs beside the sweep forward — on a training step including the walk that forms the loss AND its gradient rows
+            # (ops.ReconLossFn's one-walk route) — and its backward (replayed on this stream, enqueued after the sweep backward
+            # because its nodes are older) beside the latency-bound sweep backward: there the loss's part is one early-return
+            # launch and what is left is hs_decompose's backward (on the two-kernel route the gradient walk runs there as well)
             side.wait_event(self.model._hs_ready)
             hs.record_stream(side)
             with torch.cuda.stream(side):

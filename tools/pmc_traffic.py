@@ -23,7 +23,7 @@ LAUNCHER = {'k_struct_stage_fwd_x3': 'mgv_struct_stage_fwd_x3', 'k_struct_stage_
             'k_struct_stage_bwd_x3': 'mgv_struct_stage_bwd_x3',
             'k_level_fwd_x3': 'mgv_func_sweep_fwd_x3 (one level)', 'k_level_bwd_x3': 'mgv_func_sweep_bwd_x3 (one level)',
             'k_sweep_fwd_x3': 'mgv_func_sweep_fwd_x3', 'k_sweep_bwd_x3': 'mgv_func_sweep_bwd_x3',
-            'k_sweep_wgrad_x3': 'mgv_func_sweep_bwd_x3 (weight gradient, one slot)', 'k_recon_bwd_pull2': 'mgv_recon_loss_bwd_csr',
+            'k_sweep_wgrad_x3': 'mgv_func_sweep_bwd_x3 (weight gradient, one slot)', 'k_recon_bwd_pull2': 'mgv_recon_step_csr / mgv_recon_loss_bwd_csr',
             'k_recon<': 'mgv_recon_loss_fwd', 'k_seg_sum': 'mgv_seg_sum', 'k_class_pull_sum': 'mgv_class_pull_sum', 'k_linear_fwd_x3': 'mgv_linear_fwd_x3'}
 
 
