@@ -9,7 +9,11 @@
  *   - every pointer is a DEVICE pointer unless said otherwise; the library allocates nothing, keeps
  *     no state between calls and only enqueues work on `stream` (a hipStream_t passed as void*);
  *   - return value: 0 = enqueued, MGV_EINVAL (-1) = bad argument, MGV_EUNSUPPORTED (-2) = unsupported
- *     size (hidden width H must be 16, 32 or 64), > 0 = hipError_t of the failed launch;
+ *     size, > 0 = hipError_t of the failed launch.  The hidden widths H an entry serves are one of four sets, stated with
+ *     the entry (csrc/mgv_launch.h names them): {16, 32, 64, 128} the float4-per-lane gather / reduction kernels, {16, 32, 64}
+ *     the one-float-per-lane and the exact-fp32 stage / level kernels, {32, 64} the bf16x3 stage / level kernels,
+ *     {32, 64, 128} the attention pool.  Any other H is MGV_EUNSUPPORTED; where in the order of an entry's refusals
+ *     (before or after its MGV_EINVAL checks and its MGV_OK for an empty problem) is stated with the entry;
  *   - matrices are row-major fp32, node indices int32, all "gradient accumulator" outputs (dW..,
  *     db..) are ADDED to: the caller zeroes them.  On the default path (H = 64, bf16x3) the sums go through per-workgroup
  *     slabs and a fixed-order reduction kernel (bit-identical from run to run); the exact-fp32 family, H = 32 and the
@@ -303,7 +307,8 @@ int mgv_attn_pool_bwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in
                       void* stream);
 
 /* ghs rows of the heavy never-updated nodes (primary inputs driving thousands of gates): consumer lists in segments, one workgroup
- * each (GraphPlan.heavy_segments(reverse=True, inactive_only=True)); partial_ws: S * H floats */
+ * each (GraphPlan.heavy_segments(reverse=True, inactive_only=True)); partial_ws: S * H floats.  H in {32, 64}: any other is
+ * MGV_EUNSUPPORTED after the argument checks and after K = 0 or S = 0 returned MGV_OK. */
 int mgv_sweep_pull_heavy(int H, int K, const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_e0,
                          const int32_t* seg_e1, const int32_t* out_dst, const int32_t* out_slot, const uint8_t* gslot,
                          const float* alpha, const float* dsc, const float* dzb, const float* attn_u, float* partial_ws,
@@ -311,7 +316,11 @@ int mgv_sweep_pull_heavy(int H, int K, const int32_t* nodes, const int32_t* node
 
 /* ---- inner-product decoder and reconstruction loss (digae_layer.py:26-29, dg_ae_model_aig.py:108-130).
  * s, t: row pointers with common row stride ld (the two halves of hs_decompose's output);
- * edge lists are int64 like the reference's edge_index rows. */
+ * edge lists are int64 like the reference's edge_index rows.
+ * Widths of this section (edge_dot, recon_*): H in {16, 32, 64, 128} unless an entry says otherwise.  Every entry checks its
+ * arguments first (MGV_EINVAL, ld >= H among them), returns MGV_OK for an empty problem (E = 0; Epos + Eneg = 0; N = 0; K = 0 or
+ * S = 0) next, and refuses any other H with MGV_EUNSUPPORTED then: before its workspace size is looked at and before anything is
+ * launched. */
 int mgv_edge_dot_fwd(int H, int64_t E, const float* s, const float* t, int ld, const int64_t* src,
                      const int64_t* dst, int sigmoid, float* out, void* stream);
 int mgv_edge_dot_bwd(int H, int64_t E, const float* s, const float* t, int ld, const int64_t* src,
@@ -483,7 +492,8 @@ int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int6
  * When the positive edges are the batch graph's own edges pass its two int32 CSRs (pos_out_* by
  * source, pos_in_* by destination): the positive half then runs as gathers without atomics;
  * NULL CSRs = arbitrary positive list, float atomics (one whole row per wave-instruction).
- * H in {16, 32, 64} (the atomic rows take one float per lane); any other H returns MGV_EUNSUPPORTED with ds / dt untouched. */
+ * H in {16, 32, 64} (the atomic rows take one float per lane); any other H, 128 included, returns MGV_EUNSUPPORTED with ds / dt
+ * untouched — after the argument checks, also when both edge sets are empty. */
 int mgv_recon_loss_bwd(int H, int64_t N, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,
                        int64_t Epos, const int32_t* pos_out_ptr, const int32_t* pos_out_dst, const int32_t* pos_in_ptr,
                        const int32_t* pos_in_src, const int64_t* neg_src, const int64_t* neg_dst, int64_t Eneg,
@@ -530,7 +540,8 @@ int mgv_rows_rescale_unless(int64_t n_floats, float* rows, const float* g_dev, f
  * on the device (csrc/link_metrics.hip): keys -> mgv_sort_pairs(4, n, keys, sorted, order, 32, ...) -> rank.
  * link_keys: keys[P + Q] = the decoder's score sigmoid(<s[u], t[v]>) of every pair (positives first; the arithmetic of
  * mgv_edge_dot_fwd) as a 32-bit key whose ASCENDING unsigned order is the DESCENDING score order; scores[P + Q] (nullable): the
- * scores themselves; status[0] += number of NaN scores.  P == 0 or Q == 0: MGV_EINVAL; P + Q >= 2^31: MGV_EUNSUPPORTED. */
+ * scores themselves; status[0] += number of NaN scores.  P == 0 or Q == 0: MGV_EINVAL; P + Q >= 2^31: MGV_EUNSUPPORTED.
+ * H in {16, 32, 64, 128}: any other is MGV_EUNSUPPORTED after those checks, before anything is launched. */
 int mgv_link_keys(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst, int64_t P,
                   const int64_t* neg_src, const int64_t* neg_dst, int64_t Q, uint32_t* keys, float* scores, int32_t* status,
                   void* stream);
@@ -559,7 +570,9 @@ int mgv_neg_bucket(int64_t E, const int64_t* neg_src, const int64_t* neg_dst, co
 
 /* ---- functional-similarity loss (trainer.py:158-163, utils/utils.py:32-36): dis = 1 - cos(hf[a], hf[b]),
  * L1 between the z-normalised dis and z-normalised tt.  ws[8] doubles (zeroed by the caller):
- * 0 sum dis, 1 sum dis^2, 2 sum tt, 3 sum tt^2, 4 sum |zd-zt| (loss = ws[4]/P), 5-6 backward sums. */
+ * 0 sum dis, 1 sum dis^2, 2 sum tt, 3 sum tt^2, 4 sum |zd-zt| (loss = ws[4]/P), 5-6 backward sums.
+ * fwd: H in {16, 32, 64, 128}; both backwards: H in {16, 32, 64}.  Any other H is MGV_EUNSUPPORTED after the argument checks
+ * (P < 2 or a NULL pointer: MGV_EINVAL; bwd_csr: then N = 0: MGV_OK) and before the forward's workspace size is looked at. */
 int mgv_func_loss_fwd(int H, int64_t P, const float* hf, const int64_t* pair_a, const int64_t* pair_b,
                       const float* tt, float eps, float* dis, double* ws, double* workspace, int64_t workspace_doubles,
                       void* stream);
@@ -730,7 +743,9 @@ int mgv_seg_level_fill(int64_t G, int64_t n_seg, const int32_t* gid, int seg, in
  * exact for an exponent of 0, 0 for a degree of 0. */
 int mgv_digcn_scales(int64_t N, const int32_t* list_ptr, const int32_t* opp_ptr, float alpha, float beta, int self_loops,
                      float* r, float* c, void* stream);
-/* the propagate of :107-114 in exact fp32: out[i] = act(outer[i] * (sum_{j in L(i)} inner[j] y[j] [+ inner[i] y[i]])), H in {16,32,64,128},
+/* the propagate of :107-114 in exact fp32: out[i] = act(outer[i] * (sum_{j in L(i)} inner[j] y[j] [+ inner[i] y[i]])), H in {16,32,64,128}
+ * (gather, class_fwd, class_bwd: any other H is MGV_EUNSUPPORTED after the argument checks and before N = 0 returns MGV_OK;
+ * class_bwd_ws_floats answers 0),
  * act = ReLU when relu != 0 (F.relu of :127,146).  Forward: outer = r, inner = c.  Backward (the pull that replaces autograd's scatter):
  * the opposite CSR with outer = c, inner = r and mask = the forward's output z[N][H] when it went through the ReLU (a term's columns count
  * where mask[j] > 0; NULL: no mask).  heavy_nodes[heavy_n]: every node whose list is longer than 64 (GraphPlan.heavy), summed by one

@@ -6,7 +6,7 @@
 // One lane group (W/4 lanes) per destination node, online softmax (one pass over the sources), fp32 throughout.
 // Backward: d(score_j) in the centred form alpha_j dz . (x_j - zbar); the rows' gradients are scattered with float atomics (this
 // entry is not on the train step: inside a Model the aggregation runs in the sweep kernels, whose backward pulls instead).
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
@@ -75,35 +75,33 @@ __global__ __launch_bounds__(kThreads) void k_attn_pool_bwd(int64_t N, const int
 
 }  // namespace mgv
 
-#define MGV_DISPATCH_W(W, CALL)                          \
-    switch (W) {                                         \
-        case 32: { constexpr int WW = 32; CALL; } break;   \
-        case 64: { constexpr int WW = 64; CALL; } break;   \
-        case 128: { constexpr int WW = 128; CALL; } break; \
-        default: return MGV_EUNSUPPORTED;                \
-    }
+template <int W>
+static int attn_pool_grid(int64_t N) {
+    constexpr int rows_per_block = mgv::kThreads / (W / 4);
+    return mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
+}
 
 extern "C" int mgv_attn_pool_fwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,
                                  float* zbar, float* mstat, float* inv, void* stream) {
-    if (W != 32 && W != 64 && W != 128) return MGV_EUNSUPPORTED;      // before W / 4 divides anything: refused before anything is launched
-    MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv);
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rows_per_block = mgv::kThreads / (W / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
-    MGV_DISPATCH_W(W, hipLaunchKernelGGL((mgv::k_attn_pool_fwd<WW>), dim3(grid), dim3(mgv::kThreads), 0, st, N, in_ptr, in_src, x, u, zbar, mstat, inv));
-    MGV_LAUNCH_RET();
+    return mgv::dispatch_width(mgv::PoolWidths{}, W, [&](auto w) {      // the width is refused before anything else
+        constexpr int WW = w;
+        MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv);
+        if (N == 0) return MGV_OK;
+        hipLaunchKernelGGL(mgv::k_attn_pool_fwd<WW>, dim3(attn_pool_grid<WW>(N)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           N, in_ptr, in_src, x, u, zbar, mstat, inv);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_attn_pool_bwd(int W, int64_t N, const int32_t* in_ptr, const int32_t* in_src, const float* x, const float* u,
                                  const float* zbar, const float* mstat, const float* inv, const float* dzbar, float* dx, float* du,
                                  void* stream) {
-    if (W != 32 && W != 64 && W != 128) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv && dzbar && dx && du);
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rows_per_block = mgv::kThreads / (W / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
-    MGV_DISPATCH_W(W, hipLaunchKernelGGL((mgv::k_attn_pool_bwd<WW>), dim3(grid), dim3(mgv::kThreads), 0, st, N, in_ptr, in_src, x, u, zbar, mstat, inv, dzbar, dx, du));
-    MGV_LAUNCH_RET();
+    return mgv::dispatch_width(mgv::PoolWidths{}, W, [&](auto w) {
+        constexpr int WW = w;
+        MGV_CHECK_ARG(N >= 0 && in_ptr && x && u && zbar && mstat && inv && dzbar && dx && du);
+        if (N == 0) return MGV_OK;
+        hipLaunchKernelGGL(mgv::k_attn_pool_bwd<WW>, dim3(attn_pool_grid<WW>(N)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           N, in_ptr, in_src, x, u, zbar, mstat, inv, dzbar, dx, du);
+        MGV_LAUNCH_RET();
+    });
 }

@@ -1,7 +1,7 @@
 // Row-streaming dense operators on [N, *] node matrices: Linear forward (also used for dgrad with the
 // transposed weight), Linear weight/bias gradient, CSR gather-sum.  HBM-bound: every row is read once
 // and written once; the small weight matrix is streamed from L2 as MFMA B fragments.
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "mgv_slab.h"
 #include "../../include/mgvae_hip.h"
 
@@ -308,8 +308,7 @@ template <int M>
 int launch_linear_fwd(const LinArgs& a, hipStream_t st) {
     const int K = a.K1 + a.K2;
     const size_t shm = (size_t)kTileRows * ((K + 4) + (M + 4)) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_fwd<M>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    allow_lds<k_linear_fwd<M>>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     hipLaunchKernelGGL(k_linear_fwd<M>, dim3(grid_for(ntiles, 8)), dim3(kThreads), shm, st, a);
     MGV_LAUNCH_RET();
@@ -318,17 +317,22 @@ int launch_linear_fwd(const LinArgs& a, hipStream_t st) {
 template <int M, int K>
 int launch_linear_wgrad(const LinArgs& a, hipStream_t st) {
     const size_t shm = (size_t)kTileRows * ((K + 4) + (M + 4)) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_wgrad<M, K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    allow_lds<k_linear_wgrad<M, K>>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     hipLaunchKernelGGL((k_linear_wgrad<M, K>), dim3(grid_for(ntiles, 2)), dim3(kThreads), shm, st, a);
     MGV_LAUNCH_RET();
 }
 
-// row widths of the row-sum kernels (one float4 per lane, kThreads / (H / 4) rows per workgroup): checked before anything divides by H / 4
-inline bool row_width_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
+// grid of the row-sum kernels (one float4 per lane, kThreads / (H / 4) rows per workgroup)
+template <int H>
+int row_grid(int64_t rows, int per_cu) {
+    constexpr int rows_per_block = kThreads / (H / 4);
+    return grid_for((rows + rows_per_block - 1) / rows_per_block, per_cu);
+}
 
 }  // namespace mgv
+
+using mgv::dispatch_width;
 
 extern "C" int mgv_linear_fwd(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
                               const float* W, const float* b, int M, float* Y, int ldy, void* stream) {
@@ -338,14 +342,7 @@ extern "C" int mgv_linear_fwd(int64_t N, const float* X1, int K1, int ld1, const
     if (N == 0) return MGV_OK;
     mgv::LinArgs a{};
     a.N = N; a.X1 = X1; a.K1 = K1; a.ld1 = ld1; a.X2 = X2; a.K2 = K2; a.ld2 = ld2; a.W = W; a.b = b; a.Y = Y; a.ldy = ldy;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (M) {
-        case 16: return mgv::launch_linear_fwd<16>(a, st);
-        case 32: return mgv::launch_linear_fwd<32>(a, st);
-        case 64: return mgv::launch_linear_fwd<64>(a, st);
-        case 128: return mgv::launch_linear_fwd<128>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    return dispatch_width(mgv::AllWidths{}, M, [&](auto w) { return mgv::launch_linear_fwd<w>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int mgv_linear_wgrad(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2,
@@ -364,98 +361,72 @@ extern "C" int mgv_linear_wgrad(int64_t N, const float* X1, int K1, int ld1, con
     return MGV_EUNSUPPORTED;
 }
 
+// The row-sum entries refuse the width first, before anything divides by H / 4.
 extern "C" int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                               float* agg, float* deg, void* stream) {
-    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && h && nbr_ptr && agg);
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t rows_per_block = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 16);
-    switch (H) {
-        case 16: hipLaunchKernelGGL(mgv::k_gather_sum<16>, dim3(grid), dim3(mgv::kThreads), 0, st, N, h, nbr_ptr, nbr_idx, agg, deg); break;
-        case 32: hipLaunchKernelGGL(mgv::k_gather_sum<32>, dim3(grid), dim3(mgv::kThreads), 0, st, N, h, nbr_ptr, nbr_idx, agg, deg); break;
-        case 64: hipLaunchKernelGGL(mgv::k_gather_sum<64>, dim3(grid), dim3(mgv::kThreads), 0, st, N, h, nbr_ptr, nbr_idx, agg, deg); break;
-        case 128: hipLaunchKernelGGL(mgv::k_gather_sum<128>, dim3(grid), dim3(mgv::kThreads), 0, st, N, h, nbr_ptr, nbr_idx, agg, deg); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && h && nbr_ptr && agg);
+        if (N == 0) return MGV_OK;
+        MGV_CHECK_ARG(nbr_idx != nullptr);
+        hipLaunchKernelGGL(mgv::k_gather_sum<HH>, dim3(mgv::row_grid<HH>(N, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           N, h, nbr_ptr, nbr_idx, agg, deg);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_seg_sum(int H, int64_t n_seg, const int32_t* seg_ptr, const int32_t* items, const float* direct, const float* agg,
                            const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* out_row, float* out, void* stream) {
-    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(n_seg >= 0 && seg_ptr && direct && out && (!agg || (nbr_ptr && nbr_idx)));
-    if (n_seg == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t rows_per_block = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((n_seg + rows_per_block - 1) / rows_per_block, 16);
-    switch (H) {
-        case 16: hipLaunchKernelGGL(mgv::k_seg_sum<16>, dim3(grid), dim3(mgv::kThreads), 0, st, n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out); break;
-        case 32: hipLaunchKernelGGL(mgv::k_seg_sum<32>, dim3(grid), dim3(mgv::kThreads), 0, st, n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out); break;
-        case 64: hipLaunchKernelGGL(mgv::k_seg_sum<64>, dim3(grid), dim3(mgv::kThreads), 0, st, n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out); break;
-        case 128: hipLaunchKernelGGL(mgv::k_seg_sum<128>, dim3(grid), dim3(mgv::kThreads), 0, st, n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(n_seg >= 0 && seg_ptr && direct && out && (!agg || (nbr_ptr && nbr_idx)));
+        if (n_seg == 0) return MGV_OK;
+        hipLaunchKernelGGL(mgv::k_seg_sum<HH>, dim3(mgv::row_grid<HH>(n_seg, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_class_expand(int H, int64_t N, const float* table, const int32_t* class_id, float* out, void* stream) {
-    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && table && class_id && out);
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rows_per_block = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 16);
-    switch (H) {
-        case 16: hipLaunchKernelGGL(mgv::k_class_expand<16>, dim3(grid), dim3(mgv::kThreads), 0, st, N, table, class_id, out); break;
-        case 32: hipLaunchKernelGGL(mgv::k_class_expand<32>, dim3(grid), dim3(mgv::kThreads), 0, st, N, table, class_id, out); break;
-        case 64: hipLaunchKernelGGL(mgv::k_class_expand<64>, dim3(grid), dim3(mgv::kThreads), 0, st, N, table, class_id, out); break;
-        case 128: hipLaunchKernelGGL(mgv::k_class_expand<128>, dim3(grid), dim3(mgv::kThreads), 0, st, N, table, class_id, out); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
-}
-
-static int class_pull_grid(int H, int64_t N) {
-    const int rows_per_block = mgv::kThreads / (H / 4);
-    return mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && table && class_id && out);
+        if (N == 0) return MGV_OK;
+        hipLaunchKernelGGL(mgv::k_class_expand<HH>, dim3(mgv::row_grid<HH>(N, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           N, table, class_id, out);
+        MGV_LAUNCH_RET();
+    });
 }
 
 // floats of workspace mgv_class_pull_sum needs: one row of C*H partial sums per workgroup
 extern "C" int mgv_class_pull_sum_ws_floats(int H, int64_t N, int C) {
-    if (N <= 0 || C <= 0 || !mgv::row_width_ok(H)) return 0;
-    return class_pull_grid(H, N) * C * H;
+    if (N <= 0 || C <= 0 || !mgv::has_width(mgv::AllWidths{}, H)) return 0;
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) { return mgv::row_grid<w>(N, 8) * C * w; });
 }
+
+namespace mgv {
+template <int H, int CMAX>
+static void launch_class_pull_sum(int grid, size_t shm, hipStream_t st, int64_t N, const float* gy_direct, const float* gy_agg,
+                                  const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* class_id, int C, float* workspace) {
+    allow_lds<k_class_pull_sum<H, CMAX>>();
+    hipLaunchKernelGGL((k_class_pull_sum<H, CMAX>), dim3(grid), dim3(kThreads), shm, st, N, gy_direct, gy_agg, nbr_ptr, nbr_idx, class_id, C, workspace);
+}
+}  // namespace mgv
 
 extern "C" int mgv_class_pull_sum(int H, int64_t N, const float* gy_direct, const float* gy_agg, const int32_t* nbr_ptr,
                                   const int32_t* nbr_idx, const int32_t* class_id, int C, float* out, float* workspace,
                                   int64_t workspace_floats, void* stream) {
-    if (!mgv::row_width_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && gy_direct && class_id && out && C >= 1 && (int64_t)C * H * 4 * 5 <= 160 * 1024 && (!gy_agg || (nbr_ptr && nbr_idx)));
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int grid = class_pull_grid(H, N);
-    MGV_CHECK_ARG(workspace && workspace_floats >= (int64_t)grid * C * H);
-    const size_t shm = (size_t)C * H * sizeof(float) * (C <= 8 ? 1 + mgv::kThreads / 64 : 1);
-#define MGV_CPS(HH) \
-    case HH: { \
-        if (C <= 8) { \
-            static bool set = false; \
-            if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(mgv::k_class_pull_sum<HH, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; } \
-            hipLaunchKernelGGL((mgv::k_class_pull_sum<HH, 8>), dim3(grid), dim3(mgv::kThreads), shm, st, N, gy_direct, gy_agg, nbr_ptr, nbr_idx, class_id, C, workspace); \
-        } else { \
-            static bool set0 = false; \
-            if (!set0) { hipFuncSetAttribute(reinterpret_cast<const void*>(mgv::k_class_pull_sum<HH, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set0 = true; } \
-            hipLaunchKernelGGL((mgv::k_class_pull_sum<HH, 0>), dim3(grid), dim3(mgv::kThreads), shm, st, N, gy_direct, gy_agg, nbr_ptr, nbr_idx, class_id, C, workspace); \
-        } \
-        break; }
-    switch (H) {
-        MGV_CPS(16) MGV_CPS(32) MGV_CPS(64) MGV_CPS(128)
-        default: return MGV_EUNSUPPORTED;
-    }
-#undef MGV_CPS
-    mgv::launch_slab_sum<float, float>(workspace, grid, (int64_t)C * H, C * H, out, st);
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && gy_direct && class_id && out && C >= 1 && (int64_t)C * HH * 4 * 5 <= 160 * 1024 && (!gy_agg || (nbr_ptr && nbr_idx)));
+        if (N == 0) return MGV_OK;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const int grid = mgv::row_grid<HH>(N, 8);
+        MGV_CHECK_ARG(workspace && workspace_floats >= (int64_t)grid * C * HH);
+        const size_t shm = (size_t)C * HH * sizeof(float) * (C <= 8 ? 1 + mgv::kThreads / 64 : 1);
+        if (C <= 8) mgv::launch_class_pull_sum<HH, 8>(grid, shm, st, N, gy_direct, gy_agg, nbr_ptr, nbr_idx, class_id, C, workspace);
+        else        mgv::launch_class_pull_sum<HH, 0>(grid, shm, st, N, gy_direct, gy_agg, nbr_ptr, nbr_idx, class_id, C, workspace);
+        mgv::launch_slab_sum<float, float>(workspace, grid, (int64_t)C * HH, C * HH, out, st);
+        MGV_LAUNCH_RET();
+    });
 }

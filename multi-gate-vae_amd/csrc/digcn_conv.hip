@@ -5,7 +5,7 @@
 // byte per neighbour.  (A fused gather + bf16x3 product + store tile kernel was built and measured: it tied Linear + sum per layer and
 // lost 3-5 % over the encoder, NOTEBOOK 2026-10-17, and was removed.)
 // Every sum has a fixed order: no float atomics, cross-workgroup sums go through slab rows (mgv_slab.h).
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "mgv_slab.h"
 #include "mgvae_hip.h"
 
@@ -197,40 +197,35 @@ extern "C" int mgv_digcn_gather(int H, int64_t N, const float* y, const int32_t*
                                 const float* inner, const float* mask, int self_loops, int relu, int heavy_n, const int32_t* heavy_nodes,
                                 float* out, void* stream) {
     MGV_CHECK_ARG(N >= 0 && y && nbr_ptr && outer && inner && out && out != y && heavy_n >= 0 && (heavy_n == 0 || heavy_nodes));
-    if (H != 16 && H != 32 && H != 64 && H != 128) return MGV_EUNSUPPORTED;
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int grid = mgv::digcn_grid(N, H, 16), hgrid = heavy_n < 4096 ? heavy_n : 4096, sl = self_loops ? 1 : 0, rl = relu ? 1 : 0;
-#define MGV_DG(HH) case HH: \
-        hipLaunchKernelGGL(mgv::k_digcn_gather<HH>, dim3(grid), dim3(mgv::kThreads), 0, st, N, y, nbr_ptr, nbr_idx, outer, inner, mask, sl, rl, \
-                           heavy_n > 0 ? 1 : 0, out); \
-        if (heavy_n > 0) hipLaunchKernelGGL(mgv::k_digcn_gather_heavy<HH>, dim3(hgrid), dim3(mgv::kThreads), 0, st, heavy_n, heavy_nodes, y, nbr_ptr, \
-                                            nbr_idx, outer, inner, mask, sl, rl, out); \
-        break;
-    switch (H) { MGV_DG(16) MGV_DG(32) MGV_DG(64) MGV_DG(128) }
-#undef MGV_DG
-    MGV_LAUNCH_RET();
+    return mgv::dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        if (N == 0) return MGV_OK;
+        MGV_CHECK_ARG(nbr_idx != nullptr);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const int sl = self_loops ? 1 : 0, rl = relu ? 1 : 0;
+        hipLaunchKernelGGL(mgv::k_digcn_gather<HH>, dim3(mgv::digcn_grid(N, HH, 16)), dim3(mgv::kThreads), 0, st, N, y, nbr_ptr, nbr_idx, outer, inner,
+                           mask, sl, rl, heavy_n > 0 ? 1 : 0, out);
+        if (heavy_n > 0) hipLaunchKernelGGL(mgv::k_digcn_gather_heavy<HH>, dim3(mgv::heavy_seg_grid(heavy_n)), dim3(mgv::kThreads), 0, st, heavy_n,
+                                            heavy_nodes, y, nbr_ptr, nbr_idx, outer, inner, mask, sl, rl, out);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_digcn_class_fwd(int H, int64_t N, const uint8_t* xcls, const float* T, int C, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                                    const float* outer, const float* inner, int self_loops, int relu, float* out, void* stream) {
     MGV_CHECK_ARG(N >= 0 && xcls && T && nbr_ptr && outer && inner && out && C >= 1 && C <= mgv::kDigcnClasses);
-    if (H != 16 && H != 32 && H != 64 && H != 128) return MGV_EUNSUPPORTED;
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx != nullptr);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int grid = mgv::digcn_grid(N, H, 16), sl = self_loops ? 1 : 0, rl = relu ? 1 : 0;
-#define MGV_DG(HH) case HH: \
-        hipLaunchKernelGGL(mgv::k_digcn_class_fwd<HH>, dim3(grid), dim3(mgv::kThreads), 0, st, N, xcls, T, C, nbr_ptr, nbr_idx, outer, inner, sl, rl, out); \
-        break;
-    switch (H) { MGV_DG(16) MGV_DG(32) MGV_DG(64) MGV_DG(128) }
-#undef MGV_DG
-    MGV_LAUNCH_RET();
+    return mgv::dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        if (N == 0) return MGV_OK;
+        MGV_CHECK_ARG(nbr_idx != nullptr);
+        hipLaunchKernelGGL(mgv::k_digcn_class_fwd<HH>, dim3(mgv::digcn_grid(N, HH, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           N, xcls, T, C, nbr_ptr, nbr_idx, outer, inner, self_loops ? 1 : 0, relu ? 1 : 0, out);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_digcn_class_bwd_ws_floats(int H, int64_t N) {
-    if (N <= 0 || (H != 16 && H != 32 && H != 64 && H != 128)) return 0;
+    if (N <= 0 || !mgv::has_width(mgv::AllWidths{}, H)) return 0;
     return mgv::digcn_grid(N, H, 4) * mgv::kDigcnClasses * H;
 }
 
@@ -238,17 +233,16 @@ extern "C" int mgv_digcn_class_bwd(int H, int64_t N, const uint8_t* xcls, int C,
                                    const float* inner, int self_loops, const float* z, const float* dz, float* dT, float* workspace,
                                    int64_t workspace_floats, void* stream) {
     MGV_CHECK_ARG(N >= 0 && xcls && nbr_ptr && outer && inner && dz && dT && C >= 1 && C <= mgv::kDigcnClasses);
-    if (H != 16 && H != 32 && H != 64 && H != 128) return MGV_EUNSUPPORTED;
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(nbr_idx && workspace && workspace_floats >= mgv_digcn_class_bwd_ws_floats(H, N));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int grid = mgv::digcn_grid(N, H, 4), sl = self_loops ? 1 : 0;
-#define MGV_DG(HH) case HH: \
-        hipLaunchKernelGGL(mgv::k_digcn_class_bwd<HH>, dim3(grid), dim3(mgv::kThreads), 0, st, N, xcls, nbr_ptr, nbr_idx, outer, inner, sl, z, dz, workspace); \
-        break;
-    switch (H) { MGV_DG(16) MGV_DG(32) MGV_DG(64) MGV_DG(128) }
-#undef MGV_DG
-    // only the C rows the caller's table has are added (class ids >= C never occur: GraphPlan.xcls indexes the table's rows)
-    mgv::launch_slab_sum<float, float>(workspace, grid, mgv::kDigcnClasses * H, C * H, dT, st);
-    MGV_LAUNCH_RET();
+    return mgv::dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        if (N == 0) return MGV_OK;
+        MGV_CHECK_ARG(nbr_idx && workspace && workspace_floats >= mgv_digcn_class_bwd_ws_floats(HH, N));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const int grid = mgv::digcn_grid(N, HH, 4);
+        hipLaunchKernelGGL(mgv::k_digcn_class_bwd<HH>, dim3(grid), dim3(mgv::kThreads), 0, st, N, xcls, nbr_ptr, nbr_idx, outer, inner,
+                           self_loops ? 1 : 0, z, dz, workspace);
+        // only the C rows the caller's table has are added (class ids >= C never occur: GraphPlan.xcls indexes the table's rows)
+        mgv::launch_slab_sum<float, float>(workspace, grid, mgv::kDigcnClasses * HH, C * HH, dT, st);
+        MGV_LAUNCH_RET();
+    });
 }

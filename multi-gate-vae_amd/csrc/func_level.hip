@@ -12,7 +12,7 @@
 //
 // Backward walks the levels in reverse.  No scatter: a node PULLS the gradient of its hf/hs rows from
 // its consumers (out-CSR), which left alpha, d(score) per in-edge and d(zbar) per node behind.
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
@@ -446,12 +446,10 @@ int launch_level_v(bool bwd, const LevelArgs& a, int ntiles, hipStream_t st) {
     using M = LevelSmem<H>;
     const size_t shm = (bwd ? (size_t)M::bwd_floats : (size_t)LevelSmem<H, false>::fwd_floats) * sizeof(float);
     if (bwd) {
-        static bool set_b = false;
-        if (!set_b) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_level_bwd<H, HID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set_b = true; }
+        allow_lds<k_level_bwd<H, HID>>();
         hipLaunchKernelGGL((k_level_bwd<H, HID>), dim3(ntiles), dim3(kThreads), shm, st, a);
     } else {
-        static bool set_f = false;
-        if (!set_f) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_level_fwd<H, HID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set_f = true; }
+        allow_lds<k_level_fwd<H, HID>>();
         hipLaunchKernelGGL((k_level_fwd<H, HID>), dim3(ntiles), dim3(kThreads), shm, st, a);
     }
     MGV_LAUNCH_RET();
@@ -464,36 +462,31 @@ int launch_level(bool bwd, const LevelArgs& a, int ntiles, hipStream_t st) {
 
 }  // namespace mgv
 
-// Runs levels [1, L) forward.  level_tile_ptr is a HOST array of L+1 tile offsets.
+// Runs levels [1, L) forward.  level_tile_ptr is a HOST array of L+1 tile offsets.  The width is refused first.
 extern "C" int mgv_func_sweep_fwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                                   const int32_t* order, const int32_t* tile_start, const int32_t* tile_count,
                                   const int32_t* tile_slot, const int32_t* in_ptr, const int32_t* in_src, const float* hs,
                                   float* hf, const float* attn_u, const float* Wvc, const float* bvc, const float* bih,
                                   const float* bhh, const float* gh, const float* h_prev, void* stream) {
-    // the width first: an empty sweep never reaches the level loop's switch, and the backward divides by H / 4 behind its loop
-    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && bvc && bih && bhh && in_ptr);
-    MGV_CHECK_ARG((gh == nullptr) == (h_prev == nullptr));
-    mgv::LevelArgs a{};
-    a.gh = gh; a.hprev = h_prev;
-    a.N = N; a.T = T; a.order = order; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
-    a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = hf; a.attn_u = attn_u; a.Wvc = Wvc; a.bvc = bvc; a.bih = bih; a.bhh = bhh;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int lv = 1; lv < num_levels; ++lv) {
-        const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
-        if (t1 <= t0) continue;
-        MGV_CHECK_ARG(order && tile_start && tile_count && tile_slot && in_src);
-        a.tile_begin = t0;
-        int rc;
-        switch (H) {
-            case 16: rc = mgv::launch_level<16>(false, a, t1 - t0, st); break;
-            case 32: rc = mgv::launch_level<32>(false, a, t1 - t0, st); break;
-            case 64: rc = mgv::launch_level<64>(false, a, t1 - t0, st); break;
-            default: return MGV_EUNSUPPORTED;
+    return mgv::dispatch_width(mgv::LaneWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && bvc && bih && bhh && in_ptr);
+        MGV_CHECK_ARG((gh == nullptr) == (h_prev == nullptr));
+        mgv::LevelArgs a{};
+        a.gh = gh; a.hprev = h_prev;
+        a.N = N; a.T = T; a.order = order; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
+        a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = hf; a.attn_u = attn_u; a.Wvc = Wvc; a.bvc = bvc; a.bih = bih; a.bhh = bhh;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        for (int lv = 1; lv < num_levels; ++lv) {
+            const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
+            if (t1 <= t0) continue;
+            MGV_CHECK_ARG(order && tile_start && tile_count && tile_slot && in_src);
+            a.tile_begin = t0;
+            const int rc = mgv::launch_level<HH>(false, a, t1 - t0, st);
+            if (rc != MGV_OK) return rc;
         }
-        if (rc != MGV_OK) return rc;
-    }
-    return MGV_OK;
+        return MGV_OK;
+    });
 }
 
 extern "C" int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
@@ -505,41 +498,32 @@ extern "C" int mgv_func_sweep_bwd(int H, int64_t N, int T, int num_levels, const
                                   const float* ghf, float* ghs, float* dzb, float* alpha, float* dsc, float* d_attn_u,
                                   float* dWvc, float* dbvc, float* dbih, float* dbhh, const float* gh, const float* h_prev,
                                   float* d_gh, float* g_hprev, void* stream) {
-    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && WvcT && bvc && bih && bhh);
-    MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);
-    MGV_CHECK_ARG(gh == nullptr ? (!h_prev && !d_gh && !g_hprev) : (h_prev && d_gh && g_hprev));
-    if (N == 0) return MGV_OK;
-    mgv::LevelArgs a{};
-    a.gh = gh; a.hprev = h_prev; a.dgh = d_gh; a.ghprev = g_hprev;
-    a.N = N; a.T = T; a.order = order; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
-    a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = const_cast<float*>(hf); a.attn_u = attn_u; a.Wvc = Wvc; a.bvc = bvc;
-    a.bih = bih; a.bhh = bhh; a.WvcT = WvcT; a.out_ptr = out_ptr; a.out_dst = out_dst; a.out_slot = out_slot; a.gslot = gslot;
-    a.ghf = ghf; a.ghs = ghs; a.dzb = dzb; a.alpha = alpha; a.dsc = dsc; a.d_attn_u = d_attn_u; a.dWvc = dWvc; a.dbvc = dbvc;
-    a.dbih = dbih; a.dbhh = dbhh;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int lv = num_levels - 1; lv >= 1; --lv) {
-        const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
-        if (t1 <= t0) continue;
-        MGV_CHECK_ARG(order && tile_start && tile_count && tile_slot && in_src && out_dst && out_slot && alpha && dsc);
-        a.tile_begin = t0;
-        int rc;
-        switch (H) {
-            case 16: rc = mgv::launch_level<16>(true, a, t1 - t0, st); break;
-            case 32: rc = mgv::launch_level<32>(true, a, t1 - t0, st); break;
-            case 64: rc = mgv::launch_level<64>(true, a, t1 - t0, st); break;
-            default: return MGV_EUNSUPPORTED;
+    return mgv::dispatch_width(mgv::LaneWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && T >= 1 && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && Wvc && WvcT && bvc && bih && bhh);
+        MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);
+        MGV_CHECK_ARG(gh == nullptr ? (!h_prev && !d_gh && !g_hprev) : (h_prev && d_gh && g_hprev));
+        if (N == 0) return MGV_OK;
+        mgv::LevelArgs a{};
+        a.gh = gh; a.hprev = h_prev; a.dgh = d_gh; a.ghprev = g_hprev;
+        a.N = N; a.T = T; a.order = order; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
+        a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = const_cast<float*>(hf); a.attn_u = attn_u; a.Wvc = Wvc; a.bvc = bvc;
+        a.bih = bih; a.bhh = bhh; a.WvcT = WvcT; a.out_ptr = out_ptr; a.out_dst = out_dst; a.out_slot = out_slot; a.gslot = gslot;
+        a.ghf = ghf; a.ghs = ghs; a.dzb = dzb; a.alpha = alpha; a.dsc = dsc; a.d_attn_u = d_attn_u; a.dWvc = dWvc; a.dbvc = dbvc;
+        a.dbih = dbih; a.dbhh = dbhh;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        for (int lv = num_levels - 1; lv >= 1; --lv) {
+            const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
+            if (t1 <= t0) continue;
+            MGV_CHECK_ARG(order && tile_start && tile_count && tile_slot && in_src && out_dst && out_slot && alpha && dsc);
+            a.tile_begin = t0;
+            const int rc = mgv::launch_level<HH>(true, a, t1 - t0, st);
+            if (rc != MGV_OK) return rc;
         }
-        if (rc != MGV_OK) return rc;
-    }
-    // hs rows of nodes the sweep never updates
-    const int rows_per_block = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
-    switch (H) {
-        case 16: hipLaunchKernelGGL(mgv::k_level_pull_inactive<16>, dim3(grid), dim3(mgv::kThreads), 0, st, a); break;
-        case 32: hipLaunchKernelGGL(mgv::k_level_pull_inactive<32>, dim3(grid), dim3(mgv::kThreads), 0, st, a); break;
-        case 64: hipLaunchKernelGGL(mgv::k_level_pull_inactive<64>, dim3(grid), dim3(mgv::kThreads), 0, st, a); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+        // hs rows of nodes the sweep never updates
+        constexpr int rows_per_block = mgv::kThreads / (HH / 4);
+        hipLaunchKernelGGL(mgv::k_level_pull_inactive<HH>, dim3(mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8)), dim3(mgv::kThreads),
+                           0, st, a);
+        MGV_LAUNCH_RET();
+    });
 }

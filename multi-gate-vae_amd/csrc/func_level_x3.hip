@@ -11,6 +11,7 @@
 //     scalars (alpha, d score, consumer gate slot) in LDS with one thread per edge, and only then gathers
 //     rows, all of a row's loads in flight together.  8 waves per workgroup, two rows per 16-lane group.
 #include "func_level_x3_common.h"
+#include "mgv_launch.h"
 
 namespace mgv {
 
@@ -563,12 +564,10 @@ template <int H, bool HID>
 int launch_level_x3_v(bool bwd, const LevelX3Args& a, int ntiles, hipStream_t st) {
     using M = LvlSmem<H>;
     if (bwd) {
-        static bool set_b = false;
-        if (!set_b) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_level_bwd_x3<H, HID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set_b = true; }
+        allow_lds<k_level_bwd_x3<H, HID>>();
         hipLaunchKernelGGL((k_level_bwd_x3<H, HID>), dim3(ntiles), dim3(kLT), M::bwd_bytes, st, a);
     } else {
-        static bool set_f = false;
-        if (!set_f) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_level_fwd_x3<H, HID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set_f = true; }
+        allow_lds<k_level_fwd_x3<H, HID>>();
         hipLaunchKernelGGL((k_level_fwd_x3<H, HID>), dim3(ntiles), dim3(kLT), M::fwd_bytes, st, a);
     }
     MGV_LAUNCH_RET();
@@ -582,8 +581,7 @@ int launch_level_x3(bool bwd, const LevelX3Args& a, int ntiles, hipStream_t st) 
 template <int H>
 int launch_sweep_wgrad(const LevelX3Args& a, const int32_t* tile_list, int ntiles, float* dW, float* wgrad_slab, hipStream_t st) {
     using G = WgradGeom<H>;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_wgrad_x3<H>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_sweep_wgrad_x3<H>>();
     const int grid = std::min(ntiles, kWgradGrid);
     hipLaunchKernelGGL(k_sweep_wgrad_x3<H>, dim3(grid), dim3(G::NT), G::smem_bytes, st, a.dgrows, a.zrows, tile_list, ntiles,
                        a.tile_start, a.tile_count, wgrad_slab);
@@ -602,7 +600,7 @@ extern "C" int mgv_diag_set_level_stamps(void* p) { g_lvl_stamps = static_cast<u
 #endif
 
 extern "C" int mgv_sweep_zero_inactive(int H, int64_t N, const uint8_t* gslot, float* hf, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && (H == 16 || H == 32 || H == 64) && (N == 0 || (gslot && hf)));
+    MGV_CHECK_ARG(N >= 0 && mgv::has_width(mgv::LaneWidths{}, H) && (N == 0 || (gslot && hf)));
     if (N == 0) return MGV_OK;
     const int rows_per_block = mgv::kThreads / (H / 4);
     hipLaunchKernelGGL(mgv::k_zero_inactive_rows, dim3(mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8)), dim3(mgv::kThreads), 0,
@@ -610,37 +608,35 @@ extern "C" int mgv_sweep_zero_inactive(int H, int64_t N, const uint8_t* gslot, f
     MGV_LAUNCH_RET();
 }
 
+// The width is refused first, also for a sweep without a tile.
 extern "C" int mgv_func_sweep_fwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
                                      const int32_t* order, const int32_t* order_span, int order_span_ints, const int32_t* tile_start,
                                      const int32_t* tile_count, const int32_t* tile_slot, const int32_t* in_ptr,
                                      const int32_t* in_src, const float* hs, float* hf, const float* attn_u,
                                      const void* wpack_bf16, const float* bvc, const float* bih, const float* bhh,
                                      const float* gh, const float* h_prev, void* stream) {
-    if (H != 32 && H != 64) return MGV_EUNSUPPORTED;      // the width first, also for a sweep without a tile
-    MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && wpack_bf16 && bvc && bih && bhh && in_ptr);
-    MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
-    mgv::LevelX3Args a{};
-    MGV_SET_LVL_STAMPS(a);
-    a.N = N; a.T = T; a.order = order; a.order_span = order_span; a.span_ints = order_span_ints; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
-    a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = hf; a.attn_u = attn_u; a.wpack = static_cast<const __bf16*>(wpack_bf16);
-    a.bvc = bvc; a.bih = bih; a.bhh = bhh;
-    MGV_CHECK_ARG((gh == nullptr) == (h_prev == nullptr));
-    a.gh = gh; a.hprev = h_prev;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int lv = 1; lv < num_levels; ++lv) {
-        const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
-        if (t1 <= t0) continue;
-        MGV_CHECK_ARG(order && order_span && tile_start && tile_count && tile_slot && in_src);
-        a.tile_begin = t0;
-        int rc;
-        switch (H) {
-            case 32: rc = mgv::launch_level_x3<32>(false, a, t1 - t0, st); break;
-            case 64: rc = mgv::launch_level_x3<64>(false, a, t1 - t0, st); break;
-            default: return MGV_EUNSUPPORTED;
+    return mgv::dispatch_width(mgv::X3Widths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && level_tile_ptr_host && hs && hf && attn_u && wpack_bf16 && bvc && bih && bhh && in_ptr);
+        MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
+        mgv::LevelX3Args a{};
+        MGV_SET_LVL_STAMPS(a);
+        a.N = N; a.T = T; a.order = order; a.order_span = order_span; a.span_ints = order_span_ints; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
+        a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = hf; a.attn_u = attn_u; a.wpack = static_cast<const __bf16*>(wpack_bf16);
+        a.bvc = bvc; a.bih = bih; a.bhh = bhh;
+        MGV_CHECK_ARG((gh == nullptr) == (h_prev == nullptr));
+        a.gh = gh; a.hprev = h_prev;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        for (int lv = 1; lv < num_levels; ++lv) {
+            const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
+            if (t1 <= t0) continue;
+            MGV_CHECK_ARG(order && order_span && tile_start && tile_count && tile_slot && in_src);
+            a.tile_begin = t0;
+            const int rc = mgv::launch_level_x3<HH>(false, a, t1 - t0, st);
+            if (rc != MGV_OK) return rc;
         }
-        if (rc != MGV_OK) return rc;
-    }
-    return MGV_OK;
+        return MGV_OK;
+    });
 }
 
 extern "C" int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, const int32_t* level_tile_ptr_host,
@@ -657,85 +653,71 @@ extern "C" int mgv_func_sweep_bwd_x3(int H, int64_t N, int T, int num_levels, co
                                      const int32_t* heavy_seg_e1, const int32_t* heavy_lvl_k_ptr_host,
                                      const int32_t* heavy_lvl_seg_ptr_host, float* heavy_ws, int skip_active_longer_than,
                                      const float* gh, const float* h_prev, float* d_gh, float* g_hprev, void* stream) {
-    // the width first: the heavy pre-pass in front of a level is launched for H = 64 whenever H != 32, and H / 4 divides behind the loops
-    if (H != 32 && H != 64) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && n_active >= 0 && level_tile_ptr_host && hs && hf &&
-                  attn_u && wpack_bf16 && bvc && bih && bhh);
-    MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);
-    MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
-    if (N == 0) return MGV_OK;
-    mgv::LevelX3Args a{};
-    MGV_SET_LVL_STAMPS(a);
-    a.N = N; a.T = T; a.order = order; a.order_span = order_span; a.span_ints = order_span_ints; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
-    a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = const_cast<float*>(hf); a.attn_u = attn_u;
-    a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bvc = bvc; a.bih = bih; a.bhh = bhh;
-    a.out_ptr = out_ptr; a.out_dst = out_dst; a.out_slot = out_slot; a.gslot = gslot;
-    a.ghf = ghf; a.ghs = ghs; a.dzb = dzb; a.alpha = alpha; a.dsc = dsc; a.d_attn_u = d_attn_u; a.dWvc = dWvc; a.dbvc = dbvc;
-    a.dbih = dbih; a.dbhh = dbhh; a.skip_inactive = skip_inactive_longer_than;
-    MGV_CHECK_ARG(gh == nullptr ? (!h_prev && !d_gh && !g_hprev) : (h_prev && d_gh && g_hprev));
-    a.gh = gh; a.hprev = h_prev; a.dgh = d_gh; a.ghprev = g_hprev;
-    MGV_CHECK_ARG(heavy_active_n >= 0 && (heavy_active_n == 0 || (heavy_nodes && heavy_node_seg_ptr && heavy_seg_e0 && heavy_seg_e1 &&
-                                                                heavy_lvl_k_ptr_host && heavy_lvl_seg_ptr_host && heavy_ws && skip_active_longer_than > 0)));
-    a.skip_active = skip_active_longer_than; a.heavy_nodes = heavy_nodes; a.heavy_pull = heavy_ws;      // [K][2H], then the segment partials
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int nslab = 0;
-    for (int lv = 1; lv < num_levels; ++lv) nslab = std::max(nslab, level_tile_ptr_host[lv + 1] - level_tile_ptr_host[lv]);
-    const int64_t slab_elems = (int64_t)nslab * T * 11 * H;
-    float* wgrad_slab = nullptr;
-    if (nslab > 0) {
-        MGV_CHECK_ARG(scratch && scratch_elems >= n_active * 5 * H + slab_elems + (int64_t)mgv::kWgradGrid * 6 * H * H && slot_tiles && slot_tile_ptr_host);
-        a.dgrows = scratch; a.zrows = scratch + n_active * 3 * H; a.wslab = a.zrows + n_active * 2 * H;
-        wgrad_slab = a.wslab + slab_elems;
-        const hipError_t e = hipMemsetAsync(a.wslab, 0, slab_elems * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    for (int lv = num_levels - 1; lv >= 1; --lv) {
-        const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
-        if (t1 <= t0) continue;
-        MGV_CHECK_ARG(order && order_span && tile_start && tile_count && tile_slot && in_src && out_dst && out_slot && alpha && dsc);
-        a.tile_begin = t0;
-        a.heavy_k0 = a.heavy_k1 = 0;
-        if (heavy_active_n > 0 && heavy_lvl_k_ptr_host[lv + 1] > heavy_lvl_k_ptr_host[lv]) {
-            // this level's gates with very long consumer lists: their pulls by whole workgroups, one per list segment, before the level kernel
-            const int k0 = heavy_lvl_k_ptr_host[lv], k1 = heavy_lvl_k_ptr_host[lv + 1];
-            const int s0 = heavy_lvl_seg_ptr_host[lv], s1 = heavy_lvl_seg_ptr_host[lv + 1];
-            float* partial = heavy_ws + (int64_t)heavy_active_n * 2 * H;
-            const int grid = (s1 - s0) < 4096 ? (s1 - s0) : 4096;
-            if (H == 32) hipLaunchKernelGGL((mgv::k_pull_heavy_seg<32, true>), dim3(grid), dim3(256), 0, st, s0, s1 - s0, heavy_seg_e0, heavy_seg_e1, out_dst, out_slot, gslot, alpha, dsc, dzb, attn_u, partial);
-            else hipLaunchKernelGGL((mgv::k_pull_heavy_seg<64, true>), dim3(grid), dim3(256), 0, st, s0, s1 - s0, heavy_seg_e0, heavy_seg_e1, out_dst, out_slot, gslot, alpha, dsc, dzb, attn_u, partial);
-            hipLaunchKernelGGL(mgv::k_heavy_add_range, dim3(((k1 - k0) * 2 + 15) / 16), dim3(256), 0, st, k0, k1, 2 * H, heavy_node_seg_ptr, partial, heavy_ws);
-            a.heavy_k0 = k0; a.heavy_k1 = k1;
+    return mgv::dispatch_width(mgv::X3Widths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(N >= 0 && T >= 1 && T <= mgv::kMaxSlots && num_levels >= 0 && n_active >= 0 && level_tile_ptr_host && hs && hf &&
+                      attn_u && wpack_bf16 && bvc && bih && bhh);
+        MGV_CHECK_ARG(in_ptr && out_ptr && gslot && ghf && ghs && dzb && d_attn_u && dWvc && dbvc && dbih && dbhh);
+        MGV_CHECK_ARG(order_span_ints == 4 || order_span_ints == mgv::kRowInts);
+        if (N == 0) return MGV_OK;
+        mgv::LevelX3Args a{};
+        MGV_SET_LVL_STAMPS(a);
+        a.N = N; a.T = T; a.order = order; a.order_span = order_span; a.span_ints = order_span_ints; a.tile_start = tile_start; a.tile_count = tile_count; a.tile_slot = tile_slot;
+        a.in_ptr = in_ptr; a.in_src = in_src; a.hs = hs; a.hf = const_cast<float*>(hf); a.attn_u = attn_u;
+        a.wpack = static_cast<const __bf16*>(wpack_bf16); a.bvc = bvc; a.bih = bih; a.bhh = bhh;
+        a.out_ptr = out_ptr; a.out_dst = out_dst; a.out_slot = out_slot; a.gslot = gslot;
+        a.ghf = ghf; a.ghs = ghs; a.dzb = dzb; a.alpha = alpha; a.dsc = dsc; a.d_attn_u = d_attn_u; a.dWvc = dWvc; a.dbvc = dbvc;
+        a.dbih = dbih; a.dbhh = dbhh; a.skip_inactive = skip_inactive_longer_than;
+        MGV_CHECK_ARG(gh == nullptr ? (!h_prev && !d_gh && !g_hprev) : (h_prev && d_gh && g_hprev));
+        a.gh = gh; a.hprev = h_prev; a.dgh = d_gh; a.ghprev = g_hprev;
+        MGV_CHECK_ARG(heavy_active_n >= 0 && (heavy_active_n == 0 || (heavy_nodes && heavy_node_seg_ptr && heavy_seg_e0 && heavy_seg_e1 &&
+                                                                    heavy_lvl_k_ptr_host && heavy_lvl_seg_ptr_host && heavy_ws && skip_active_longer_than > 0)));
+        a.skip_active = skip_active_longer_than; a.heavy_nodes = heavy_nodes; a.heavy_pull = heavy_ws;      // [K][2H], then the segment partials
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        int nslab = 0;
+        for (int lv = 1; lv < num_levels; ++lv) nslab = std::max(nslab, level_tile_ptr_host[lv + 1] - level_tile_ptr_host[lv]);
+        const int64_t slab_elems = (int64_t)nslab * T * 11 * HH;
+        float* wgrad_slab = nullptr;
+        if (nslab > 0) {
+            MGV_CHECK_ARG(scratch && scratch_elems >= n_active * 5 * HH + slab_elems + (int64_t)mgv::kWgradGrid * 6 * HH * HH && slot_tiles && slot_tile_ptr_host);
+            a.dgrows = scratch; a.zrows = scratch + n_active * 3 * HH; a.wslab = a.zrows + n_active * 2 * HH;
+            wgrad_slab = a.wslab + slab_elems;
+            const hipError_t e = hipMemsetAsync(a.wslab, 0, slab_elems * sizeof(float), st);
+            if (e != hipSuccess) return (int)e;
         }
-        int rc;
-        switch (H) {
-            case 32: rc = mgv::launch_level_x3<32>(true, a, t1 - t0, st); break;
-            case 64: rc = mgv::launch_level_x3<64>(true, a, t1 - t0, st); break;
-            default: return MGV_EUNSUPPORTED;
-        }
-        if (rc != MGV_OK) return rc;
-    }
-    if (nslab > 0) {
-        switch (H) {
-            case 32: hipLaunchKernelGGL(mgv::k_level_small_reduce<32>, dim3(T, (11 * 32 + 255) / 256), dim3(256), 0, st, a.wslab, nslab, T, d_attn_u, dbvc, dbih, dbhh); break;
-            case 64: hipLaunchKernelGGL(mgv::k_level_small_reduce<64>, dim3(T, (11 * 64 + 255) / 256), dim3(256), 0, st, a.wslab, nslab, T, d_attn_u, dbvc, dbih, dbhh); break;
-            default: return MGV_EUNSUPPORTED;
-        }
-        for (int g = 0; g < T; ++g) {
-            const int nt = slot_tile_ptr_host[g + 1] - slot_tile_ptr_host[g];
-            if (nt <= 0) continue;
-            const int rc = H == 32 ? mgv::launch_sweep_wgrad<32>(a, slot_tiles + slot_tile_ptr_host[g], nt, dWvc + (int64_t)g * 3 * H * 2 * H, wgrad_slab, st)
-                                   : mgv::launch_sweep_wgrad<64>(a, slot_tiles + slot_tile_ptr_host[g], nt, dWvc + (int64_t)g * 3 * H * 2 * H, wgrad_slab, st);
+        for (int lv = num_levels - 1; lv >= 1; --lv) {
+            const int t0 = level_tile_ptr_host[lv], t1 = level_tile_ptr_host[lv + 1];
+            if (t1 <= t0) continue;
+            MGV_CHECK_ARG(order && order_span && tile_start && tile_count && tile_slot && in_src && out_dst && out_slot && alpha && dsc);
+            a.tile_begin = t0;
+            a.heavy_k0 = a.heavy_k1 = 0;
+            if (heavy_active_n > 0 && heavy_lvl_k_ptr_host[lv + 1] > heavy_lvl_k_ptr_host[lv]) {
+                // this level's gates with very long consumer lists: their pulls by whole workgroups, one per list segment, before the level kernel
+                const int k0 = heavy_lvl_k_ptr_host[lv], k1 = heavy_lvl_k_ptr_host[lv + 1];
+                const int s0 = heavy_lvl_seg_ptr_host[lv], s1 = heavy_lvl_seg_ptr_host[lv + 1];
+                float* partial = heavy_ws + (int64_t)heavy_active_n * 2 * HH;
+                hipLaunchKernelGGL((mgv::k_pull_heavy_seg<HH, true>), dim3(mgv::heavy_seg_grid(s1 - s0)), dim3(256), 0, st, s0, s1 - s0, heavy_seg_e0,
+                                   heavy_seg_e1, out_dst, out_slot, gslot, alpha, dsc, dzb, attn_u, partial);
+                hipLaunchKernelGGL(mgv::k_heavy_add_range, dim3(((k1 - k0) * 2 + 15) / 16), dim3(256), 0, st, k0, k1, 2 * HH, heavy_node_seg_ptr, partial, heavy_ws);
+                a.heavy_k0 = k0; a.heavy_k1 = k1;
+            }
+            const int rc = mgv::launch_level_x3<HH>(true, a, t1 - t0, st);
             if (rc != MGV_OK) return rc;
         }
-    }
-    const int rows_per_block = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8);
-    switch (H) {
-        case 32: hipLaunchKernelGGL(mgv::k_level_pull_inactive_x3<32>, dim3(grid), dim3(mgv::kThreads), 0, st, a); break;
-        case 64: hipLaunchKernelGGL(mgv::k_level_pull_inactive_x3<64>, dim3(grid), dim3(mgv::kThreads), 0, st, a); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+        if (nslab > 0) {
+            hipLaunchKernelGGL(mgv::k_level_small_reduce<HH>, dim3(T, (11 * HH + 255) / 256), dim3(256), 0, st, a.wslab, nslab, T, d_attn_u, dbvc, dbih, dbhh);
+            for (int g = 0; g < T; ++g) {
+                const int nt = slot_tile_ptr_host[g + 1] - slot_tile_ptr_host[g];
+                if (nt <= 0) continue;
+                const int rc = mgv::launch_sweep_wgrad<HH>(a, slot_tiles + slot_tile_ptr_host[g], nt, dWvc + (int64_t)g * 3 * HH * 2 * HH, wgrad_slab, st);
+                if (rc != MGV_OK) return rc;
+            }
+        }
+        constexpr int rows_per_block = mgv::kThreads / (HH / 4);
+        hipLaunchKernelGGL(mgv::k_level_pull_inactive_x3<HH>, dim3(mgv::grid_for((N + rows_per_block - 1) / rows_per_block, 8)), dim3(mgv::kThreads),
+                           0, st, a);
+        MGV_LAUNCH_RET();
+    });
 }
 
 // ghs[nodes[k]] = the pull of heavy never-updated nodes (skipped by mgv_func_sweep_bwd_x3 when skip_inactive_longer_than > 0), their
@@ -748,12 +730,10 @@ extern "C" int mgv_sweep_pull_heavy(int H, int K, const int32_t* nodes, const in
     if (K == 0 || S == 0) return MGV_OK;
     MGV_CHECK_ARG(nodes && node_seg_ptr && seg_e0 && seg_e1 && out_dst && out_slot && gslot && alpha && dsc && dzb && attn_u && partial_ws);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int grid = S < 4096 ? S : 4096;
-    switch (H) {
-        case 32: hipLaunchKernelGGL((mgv::k_pull_heavy_seg<32, false>), dim3(grid), dim3(256), 0, st, 0, S, seg_e0, seg_e1, out_dst, out_slot, gslot, alpha, dsc, dzb, attn_u, partial_ws); break;
-        case 64: hipLaunchKernelGGL((mgv::k_pull_heavy_seg<64, false>), dim3(grid), dim3(256), 0, st, 0, S, seg_e0, seg_e1, out_dst, out_slot, gslot, alpha, dsc, dzb, attn_u, partial_ws); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    hipLaunchKernelGGL(mgv::k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial_ws, ghs, H, 0);
-    MGV_LAUNCH_RET();
+    return mgv::launch_width(mgv::X3Widths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        hipLaunchKernelGGL((mgv::k_pull_heavy_seg<HH, false>), dim3(mgv::heavy_seg_grid(S)), dim3(256), 0, st, 0, S, seg_e0, seg_e1, out_dst, out_slot,
+                           gslot, alpha, dsc, dzb, attn_u, partial_ws);
+        mgv::launch_heavy_add(K, HH, nodes, node_seg_ptr, partial_ws, ghs, HH, 0, st);
+    });
 }

@@ -6,6 +6,7 @@
 // row-major planes, and the next tile's rows are in flight (registers) while the current tile is multiplied.  The whole backward
 // of a layer (k_linear_bwd_x3) is the weight-gradient kernel with the input gradient formed from the dY planes it already holds.
 #include "mgv_x3.h"
+#include "mgv_launch.h"
 #include "mgv_slab.h"
 #include "../../include/mgvae_hip.h"
 
@@ -392,8 +393,7 @@ __global__ __launch_bounds__(256) void k_wpack_bf16x3(const float* W, int R, int
 template <int M, int K, bool GROUPED = false>
 int launch_linear_fwd_x3(const LinX3Args& a, hipStream_t st) {
     using G = LinFwdGeom<M, K>;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_fwd_x3<M, K, GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_linear_fwd_x3<M, K, GROUPED>>();
     const int64_t ntiles = a.order ? a.g_ntiles : (a.N + kTileRows - 1) / kTileRows;
     int per_cu = 160 * 1024 / G::smem_bytes;
     per_cu = per_cu > 4 ? 4 : per_cu;
@@ -404,8 +404,7 @@ int launch_linear_fwd_x3(const LinX3Args& a, hipStream_t st) {
 template <int M, int K, int NW, int WI, bool GROUPED = false>
 int launch_linear_wgrad_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st) {
     using G = LinWgGeom<M, K, NW, WI>;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_wgrad_x3<M, K, NW, WI, GROUPED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_linear_wgrad_x3<M, K, NW, WI, GROUPED>>();
     const int64_t ntiles = a.order ? a.g_ntiles : (a.N + kTileRows - 1) / kTileRows;
     int per_cu = 160 * 1024 / G::smem_bytes;
     const int cap = 1024 / G::NT;                    // 16 waves per CU
@@ -422,8 +421,7 @@ int launch_linear_wgrad_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st
 template <int M, int K, int NW, int WI, int KSR>
 int launch_linear_bwd_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st) {
     using G = LinWgGeom<M, K, NW, WI>;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_linear_bwd_x3<M, K, NW, WI, KSR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_linear_bwd_x3<M, K, NW, WI, KSR>>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     int per_cu = 160 * 1024 / G::smem_bytes;
     const int cap = 1024 / G::NT;

@@ -10,7 +10,7 @@
 //      summed per workgroup in a fixed order, one slab row per workgroup, rows added in index order by k_slab_sum).  Tie
 //      groups of any length cost the same: a group's head travels in the scan's carry, nothing walks a group.  Two runs give
 //      the same bits.
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "mgv_slab.h"
 #include "../../include/mgvae_hip.h"
 
@@ -262,24 +262,16 @@ inline int64_t rank_tiles(int64_t n) { return (n + kRankTile - 1) / kRankTile; }
 
 }  // namespace mgv
 
-#define MGV_LINK_DISPATCH_H(H, CALL)                      \
-    switch (H) {                                          \
-        case 16: { constexpr int HH = 16; CALL; } break;  \
-        case 32: { constexpr int HH = 32; CALL; } break;  \
-        case 64: { constexpr int HH = 64; CALL; } break;  \
-        case 128: { constexpr int HH = 128; CALL; } break; \
-        default: return MGV_EUNSUPPORTED;                 \
-    }
-
 extern "C" int mgv_link_keys(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst, int64_t P,
                              const int64_t* neg_src, const int64_t* neg_dst, int64_t Q, uint32_t* keys, float* scores, int32_t* status,
                              void* stream) {
     MGV_CHECK_ARG(P > 0 && Q > 0 && s && t && pos_src && pos_dst && neg_src && neg_dst && keys && status && ld >= H && ld % 4 == 0);
     if (P + Q >= (int64_t(1) << 31)) return MGV_EUNSUPPORTED;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_LINK_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_link_keys<HH>), dim3(mgv::grid_for((P + Q + mgv::kThreads / (HH / 4) - 1) / (mgv::kThreads / (HH / 4)), 8)),
-                                              dim3(mgv::kThreads), 0, st, P, Q, s, t, ld, pos_src, pos_dst, neg_src, neg_dst, keys, scores, status));
-    MGV_LAUNCH_RET();
+    return mgv::launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w, per_block = mgv::kThreads / (HH / 4);
+        hipLaunchKernelGGL(mgv::k_link_keys<HH>, dim3(mgv::grid_for((P + Q + per_block - 1) / per_block, 8)), dim3(mgv::kThreads), 0,
+                           static_cast<hipStream_t>(stream), P, Q, s, t, ld, pos_src, pos_dst, neg_src, neg_dst, keys, scores, status);
+    });
 }
 
 extern "C" int mgv_link_rank_work_ints(int64_t n) {

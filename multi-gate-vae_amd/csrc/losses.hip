@@ -1,8 +1,9 @@
 // Edge / pair reductions of the DG_AE train step: inner-product decoder, reconstruction loss with
 // confusion counters, functional-similarity loss (cosine distance -> z-normalisation -> L1),
 // reparameterisation sampler + KL.  All HBM/gather bound: H/4 lanes read one 4H-byte row as float4s,
-// reductions go wave -> block -> one double atomic per block.
-#include "mgv_common.h"
+// reductions go wave -> block -> this workgroup's row of a slab, added in a fixed order afterwards (mgv_slab.h); only the integer
+// confusion counters and the KL sum leave as one atomic per block.
+#include "mgv_launch.h"
 #include "mgv_slab.h"
 #include "../../include/mgvae_hip.h"
 
@@ -73,12 +74,10 @@ struct ReconArgs {
     double* sums;               // [2]: sum -log(p+eps) over positives, sum -log(1-p+eps) over negatives
     unsigned long long* cnt;    // [4]: TP, FP, TN, FN
     int32_t* pred_bin;          // [Ep+En] or null
-    const float* gscale;        // bwd: device scalar, upstream gradient of the loss
-    float* ds; float* dt;       // bwd accumulators (same ld)
-    double* slab;               // fwd: [gridDim][2] per-workgroup loss sums
+    double* slab;               // [gridDim][2] per-workgroup loss sums
 };
 
-template <int H, bool BWD>
+template <int H>
 __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs a) {
     constexpr int LPR = H / 4, EPB = kThreads / LPR;
     __shared__ double red[kThreads];
@@ -86,9 +85,6 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs a) {
     const int64_t E = a.Ep + a.En;
     float lp = 0.f, ln = 0.f;
     unsigned int tp = 0, fp = 0, tn = 0, fn = 0;
-    float g = 0.f;
-    if (BWD) g = *a.gscale;
-    const float wpos = BWD ? g / (float)a.Ep : 0.f, wneg = BWD ? g / (float)a.En : 0.f;
     for (int64_t e0 = (int64_t)blockIdx.x * EPB; e0 < E; e0 += (int64_t)gridDim.x * EPB) {
         const int64_t e = e0 + slot;
         const bool ok = e < E;
@@ -103,31 +99,21 @@ __global__ __launch_bounds__(kThreads) void k_recon(ReconArgs a) {
         }
         const float val = group_sum<LPR>(dot4_plain(x, y));
         const float p = sigmoidf_(val);
-        if (!BWD) {
-            if (ok && lr == 0) {
-                const bool hit = p > 0.5f;
-                if (pos) { lp -= logf(p + 1e-15f); tp += hit; fn += !hit; }
-                else     { ln -= logf((1.0f - p) + 1e-15f); fp += hit; tn += !hit; }
-                if (a.pred_bin) a.pred_bin[e] = hit ? 1 : 0;
-            }
-        } else if (ok) {
-            // d/dval of -log(p+eps) = -p(1-p)/(p+eps);  of -log(1-p+eps) = p(1-p)/(1-p+eps)
-            const float dp = p * (1.0f - p);
-            const float c = pos ? -wpos * dp / (p + 1e-15f) : wneg * dp / ((1.0f - p) + 1e-15f);
-            atomic_add4(a.ds + u * a.ld + 4 * lr, scale4(c, y));
-            atomic_add4(a.dt + v * a.ld + 4 * lr, scale4(c, x));
+        if (ok && lr == 0) {
+            const bool hit = p > 0.5f;
+            if (pos) { lp -= logf(p + 1e-15f); tp += hit; fn += !hit; }
+            else     { ln -= logf((1.0f - p) + 1e-15f); fp += hit; tn += !hit; }
+            if (a.pred_bin) a.pred_bin[e] = hit ? 1 : 0;
         }
     }
-    if (!BWD) {
-        const double sp = block_sum_d((double)lp, red);
-        const double sn = block_sum_d((double)ln, red);
-        const double c0 = block_sum_d((double)tp, red), c1 = block_sum_d((double)fp, red);
-        const double c2 = block_sum_d((double)tn, red), c3 = block_sum_d((double)fn, red);
-        if (threadIdx.x == 0) {
-            a.slab[2 * blockIdx.x + 0] = sp; a.slab[2 * blockIdx.x + 1] = sn;      // this workgroup's row; added in a fixed order afterwards
-            atomicAdd(a.cnt + 0, (unsigned long long)c0); atomicAdd(a.cnt + 1, (unsigned long long)c1);
-            atomicAdd(a.cnt + 2, (unsigned long long)c2); atomicAdd(a.cnt + 3, (unsigned long long)c3);
-        }
+    const double sp = block_sum_d((double)lp, red);
+    const double sn = block_sum_d((double)ln, red);
+    const double c0 = block_sum_d((double)tp, red), c1 = block_sum_d((double)fp, red);
+    const double c2 = block_sum_d((double)tn, red), c3 = block_sum_d((double)fn, red);
+    if (threadIdx.x == 0) {
+        a.slab[2 * blockIdx.x + 0] = sp; a.slab[2 * blockIdx.x + 1] = sn;      // this workgroup's row; added in a fixed order afterwards
+        atomicAdd(a.cnt + 0, (unsigned long long)c0); atomicAdd(a.cnt + 1, (unsigned long long)c1);
+        atomicAdd(a.cnt + 2, (unsigned long long)c2); atomicAdd(a.cnt + 3, (unsigned long long)c3);
     }
 }
 
@@ -558,14 +544,8 @@ inline int items_grid(int64_t items, int per_block) { return grid_for((items + p
 
 }  // namespace mgv
 
-#define MGV_DISPATCH_H(H, CALL)                      \
-    switch (H) {                                     \
-        case 16: { constexpr int HH = 16; CALL; } break;  \
-        case 32: { constexpr int HH = 32; CALL; } break;  \
-        case 64: { constexpr int HH = 64; CALL; } break;  \
-        case 128: { constexpr int HH = 128; CALL; } break; \
-        default: return MGV_EUNSUPPORTED;            \
-    }
+using mgv::dispatch_width;
+using mgv::launch_width;
 
 extern "C" int mgv_edge_dot_fwd(int H, int64_t E, const float* s, const float* t, int ld, const int64_t* src,
                                 const int64_t* dst, int sigmoid, float* out, void* stream) {
@@ -573,9 +553,11 @@ extern "C" int mgv_edge_dot_fwd(int H, int64_t E, const float* s, const float* t
     if (E == 0) return MGV_OK;
     MGV_CHECK_ARG(src && dst);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_edge_dot<HH, false>), dim3(mgv::items_grid(E, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
-                                         E, s, t, ld, src, dst, sigmoid, out, nullptr, nullptr, nullptr));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        hipLaunchKernelGGL((mgv::k_edge_dot<HH, false>), dim3(mgv::items_grid(E, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
+                           E, s, t, ld, src, dst, sigmoid, out, nullptr, nullptr, nullptr);
+    });
 }
 
 extern "C" int mgv_edge_dot_bwd(int H, int64_t E, const float* s, const float* t, int ld, const int64_t* src,
@@ -584,9 +566,11 @@ extern "C" int mgv_edge_dot_bwd(int H, int64_t E, const float* s, const float* t
     if (E == 0) return MGV_OK;
     MGV_CHECK_ARG(src && dst);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_edge_dot<HH, true>), dim3(mgv::items_grid(E, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
-                                         E, s, t, ld, src, dst, sigmoid, nullptr, gout, ds, dt));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        hipLaunchKernelGGL((mgv::k_edge_dot<HH, true>), dim3(mgv::items_grid(E, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
+                           E, s, t, ld, src, dst, sigmoid, nullptr, gout, ds, dt);
+    });
 }
 
 extern "C" int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,
@@ -600,13 +584,15 @@ extern "C" int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld,
     a.s = s; a.t = t; a.ld = ld; a.psrc = pos_src; a.pdst = pos_dst; a.Ep = Epos; a.nsrc = neg_src; a.ndst = neg_dst; a.En = Eneg;
     a.sums = sums; a.cnt = reinterpret_cast<unsigned long long*>(counts); a.pred_bin = pred_bin;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int grid = 0;
-    MGV_DISPATCH_H(H, grid = mgv::items_grid(Epos + Eneg, mgv::kThreads / (HH / 4)));
-    MGV_CHECK_ARG(workspace && workspace_doubles >= 2 * (int64_t)grid);
-    a.slab = workspace;
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon<HH, false>), dim3(grid), dim3(mgv::kThreads), 0, st, a));
-    mgv::launch_slab_sum<double, double>(workspace, grid, 2, 2, sums, st);
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        const int grid = mgv::items_grid(Epos + Eneg, mgv::kThreads / (HH / 4));
+        MGV_CHECK_ARG(workspace && workspace_doubles >= 2 * (int64_t)grid);
+        a.slab = workspace;
+        hipLaunchKernelGGL(mgv::k_recon<HH>, dim3(grid), dim3(mgv::kThreads), 0, st, a);
+        mgv::launch_slab_sum<double, double>(workspace, grid, 2, 2, sums, st);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_recon_loss_bwd(int H, int64_t N, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,
@@ -617,42 +603,81 @@ extern "C" int mgv_recon_loss_bwd(int H, int64_t N, const float* s, const float*
     MGV_CHECK_ARG((Epos == 0 || (pos_src && pos_dst)) && (Eneg == 0 || (neg_src && neg_dst)));
     const bool pull = pos_out_ptr != nullptr;
     MGV_CHECK_ARG(!pull || (pos_in_ptr && (Epos == 0 || (pos_out_dst && pos_in_src))));
-    if (H != 16 && H != 32 && H != 64) return MGV_EUNSUPPORTED;      // the atomic rows need one float per lane: refused before anything is launched
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (Epos > 0 && pull) {
-        MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull<HH>), dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
-                                             N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, gscale, ds, dt));
-    }
-    for (int neg = (Epos > 0 && pull) ? 1 : 0; neg < 2; ++neg) {
-        const int64_t E = neg ? Eneg : Epos;
-        if (E == 0) continue;
-        const int64_t* es = neg ? neg_src : pos_src;
-        const int64_t* ed = neg ? neg_dst : pos_dst;
-        const float wsc = 1.0f / (float)E;
-        switch (H) {     // one float per lane: the row must fit a wave
-            case 16: hipLaunchKernelGGL((mgv::k_recon_bwd_rows<16>), dim3(mgv::items_grid(E, mgv::kThreads / 16)), dim3(mgv::kThreads), 0, st, E, s, t, ld, es, ed, neg, wsc, gscale, ds, dt); break;
-            case 32: hipLaunchKernelGGL((mgv::k_recon_bwd_rows<32>), dim3(mgv::items_grid(E, mgv::kThreads / 32)), dim3(mgv::kThreads), 0, st, E, s, t, ld, es, ed, neg, wsc, gscale, ds, dt); break;
-            case 64: hipLaunchKernelGGL((mgv::k_recon_bwd_rows<64>), dim3(mgv::items_grid(E, mgv::kThreads / 64)), dim3(mgv::kThreads), 0, st, E, s, t, ld, es, ed, neg, wsc, gscale, ds, dt); break;
-            default: return MGV_EUNSUPPORTED;
+    // the atomic rows need one float per lane (the row must fit a wave): H = 128 is refused before anything is launched
+    return launch_width(mgv::LaneWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        if (Epos > 0 && pull) {
+            hipLaunchKernelGGL(mgv::k_recon_bwd_pull<HH>, dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
+                               N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, gscale, ds, dt);
         }
-    }
-    MGV_LAUNCH_RET();
+        for (int neg = (Epos > 0 && pull) ? 1 : 0; neg < 2; ++neg) {
+            const int64_t E = neg ? Eneg : Epos;
+            if (E == 0) continue;
+            hipLaunchKernelGGL(mgv::k_recon_bwd_rows<HH>, dim3(mgv::items_grid(E, mgv::kThreads / HH)), dim3(mgv::kThreads), 0, st, E, s, t, ld,
+                               neg ? neg_src : pos_src, neg ? neg_dst : pos_dst, neg, 1.0f / (float)E, gscale, ds, dt);
+        }
+    });
 }
+
+namespace mgv {
+
+// The per-node walk of the four lists.  STEP: with the loss's forward (slab [grid][2] -> sums, counters), rows formed for `gval`;
+// otherwise the gradient alone, for the device scalar `gscale`.
+template <bool STEP>
+static int recon_csr(int H, int64_t N, const float* s, const float* t, int ld, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
+                     const int32_t* pos_in_ptr, const int32_t* pos_in_src, int64_t Epos, const int32_t* neg_out_ptr,
+                     const int32_t* neg_out_dst, const int32_t* neg_in_ptr, const int32_t* neg_in_src, int64_t Eneg, const float* gscale,
+                     float gval, double* sums, uint64_t* counts, float* ds, float* dt, int skip_len, double* workspace,
+                     int64_t workspace_doubles, void* stream) {
+    MGV_CHECK_ARG(s && t && (STEP ? sums && counts : gscale != nullptr) && ds && dt && Epos >= 0 && Eneg >= 0 && N >= 0 && ld >= H && ld % 4 == 0 && skip_len >= 0);
+    MGV_CHECK_ARG(Epos == 0 || (pos_out_ptr && pos_out_dst && pos_in_ptr && pos_in_src));
+    MGV_CHECK_ARG(Eneg == 0 || (neg_out_ptr && neg_out_dst && neg_in_ptr && neg_in_src));
+    if (N == 0) return MGV_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return dispatch_width(AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        const int grid = items_grid(N, kThreads / (HH / 4));
+        if (STEP) MGV_CHECK_ARG(workspace && workspace_doubles >= 2 * (int64_t)grid);
+        hipLaunchKernelGGL((k_recon_bwd_pull2<HH, STEP>), dim3(grid), dim3(kThreads), 0, st,
+                           N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst,
+                           neg_in_ptr, neg_in_src, Eneg, gscale, gval, ds, dt, skip_len, workspace, reinterpret_cast<unsigned long long*>(counts));
+        if (STEP) launch_slab_sum<double, double>(workspace, grid, 2, 2, sums, st);
+        MGV_LAUNCH_RET();
+    });
+}
+
+// The heavy positive lists, one segment per workgroup.  STEP as above; its loss terms (slab [grid]) leave with which = 0 only.
+template <bool STEP>
+static int recon_heavy(int H, const float* s, const float* t, int ld, int64_t Epos, const float* gscale, float gval, int K,
+                       const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node, const int32_t* seg_e0,
+                       const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws, float* out, double* sums,
+                       uint64_t* counts, double* workspace, int64_t workspace_doubles, void* stream) {
+    MGV_CHECK_ARG(K >= 0 && S >= 0 && Epos > 0 && s && t && (STEP || gscale) && out && ld >= H && ld % 4 == 0 && (which == 0 || which == 1));
+    if (STEP) MGV_CHECK_ARG(which == 1 || (sums && counts));
+    if (K == 0 || S == 0) return MGV_OK;
+    MGV_CHECK_ARG(nodes && node_seg_ptr && seg_node && seg_e0 && seg_e1 && list && partial_ws);
+    const int grid = heavy_seg_grid(S);
+    if (STEP) MGV_CHECK_ARG(which == 1 || (workspace && workspace_doubles >= (int64_t)grid));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return launch_width(AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        hipLaunchKernelGGL((k_recon_heavy_seg<HH, STEP>), dim3(grid), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
+                           s, t, ld, list, which, Epos, gscale, gval, partial_ws, workspace, reinterpret_cast<unsigned long long*>(counts));
+        if (STEP && which == 0) launch_slab_sum<double, double>(workspace, grid, 1, 1, sums, st);
+        launch_heavy_add(K, HH, nodes, node_seg_ptr, partial_ws, out, ld, 1, st);
+    });
+}
+
+}  // namespace mgv
 
 extern "C" int mgv_recon_loss_bwd_csr(int H, int64_t N, const float* s, const float* t, int ld, const int32_t* pos_out_ptr,
                                       const int32_t* pos_out_dst, const int32_t* pos_in_ptr, const int32_t* pos_in_src, int64_t Epos,
                                       const int32_t* neg_out_ptr, const int32_t* neg_out_dst, const int32_t* neg_in_ptr,
                                       const int32_t* neg_in_src, int64_t Eneg, const float* gscale, float* ds, float* dt,
                                       int skip_pos_longer_than, void* stream) {
-    MGV_CHECK_ARG(s && t && gscale && ds && dt && Epos >= 0 && Eneg >= 0 && N >= 0 && ld >= H && ld % 4 == 0 && skip_pos_longer_than >= 0);
-    MGV_CHECK_ARG(Epos == 0 || (pos_out_ptr && pos_out_dst && pos_in_ptr && pos_in_src));
-    MGV_CHECK_ARG(Eneg == 0 || (neg_out_ptr && neg_out_dst && neg_in_ptr && neg_in_src));
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull2<HH, false>), dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st,
-                                         N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst,
-                                         neg_in_ptr, neg_in_src, Eneg, gscale, 0.f, ds, dt, skip_pos_longer_than, nullptr, nullptr));
-    MGV_LAUNCH_RET();
+    return mgv::recon_csr<false>(H, N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst, neg_in_ptr,
+                                 neg_in_src, Eneg, gscale, 0.f, nullptr, nullptr, ds, dt, skip_pos_longer_than, nullptr, 0, stream);
 }
 
 extern "C" int mgv_recon_step_csr(int H, int64_t N, const float* s, const float* t, int ld, const int32_t* pos_out_ptr,
@@ -660,33 +685,16 @@ extern "C" int mgv_recon_step_csr(int H, int64_t N, const float* s, const float*
                                   const int32_t* neg_out_ptr, const int32_t* neg_out_dst, const int32_t* neg_in_ptr,
                                   const int32_t* neg_in_src, int64_t Eneg, float expect_scale, double* sums, uint64_t* counts, float* ds,
                                   float* dt, int skip_pos_longer_than, double* workspace, int64_t workspace_doubles, void* stream) {
-    MGV_CHECK_ARG(s && t && sums && counts && ds && dt && Epos >= 0 && Eneg >= 0 && N >= 0 && ld >= H && ld % 4 == 0 && skip_pos_longer_than >= 0);
-    MGV_CHECK_ARG(Epos == 0 || (pos_out_ptr && pos_out_dst && pos_in_ptr && pos_in_src));
-    MGV_CHECK_ARG(Eneg == 0 || (neg_out_ptr && neg_out_dst && neg_in_ptr && neg_in_src));
-    if (N == 0) return MGV_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int grid = 0;
-    MGV_DISPATCH_H(H, grid = mgv::items_grid(N, mgv::kThreads / (HH / 4)));
-    MGV_CHECK_ARG(workspace && workspace_doubles >= 2 * (int64_t)grid);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_bwd_pull2<HH, true>), dim3(grid), dim3(mgv::kThreads), 0, st,
-                                         N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst,
-                                         neg_in_ptr, neg_in_src, Eneg, nullptr, expect_scale, ds, dt, skip_pos_longer_than, workspace,
-                                         reinterpret_cast<unsigned long long*>(counts)));
-    mgv::launch_slab_sum<double, double>(workspace, grid, 2, 2, sums, st);
-    MGV_LAUNCH_RET();
+    return mgv::recon_csr<true>(H, N, s, t, ld, pos_out_ptr, pos_out_dst, pos_in_ptr, pos_in_src, Epos, neg_out_ptr, neg_out_dst, neg_in_ptr,
+                                neg_in_src, Eneg, nullptr, expect_scale, sums, counts, ds, dt, skip_pos_longer_than, workspace,
+                                workspace_doubles, stream);
 }
 
 extern "C" int mgv_recon_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, const float* gscale, int K,
                                      const int32_t* nodes, const int32_t* node_seg_ptr, int S, const int32_t* seg_node, const int32_t* seg_e0,
                                      const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws, float* out, void* stream) {
-    MGV_CHECK_ARG(K >= 0 && S >= 0 && Epos > 0 && s && t && gscale && out && ld >= H && ld % 4 == 0 && (which == 0 || which == 1));
-    if (K == 0 || S == 0) return MGV_OK;
-    MGV_CHECK_ARG(nodes && node_seg_ptr && seg_node && seg_e0 && seg_e1 && list && partial_ws);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_heavy_seg<HH, false>), dim3(S < 4096 ? S : 4096), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
-                                         s, t, ld, list, which, Epos, gscale, 0.f, partial_ws, nullptr, nullptr));
-    hipLaunchKernelGGL(mgv::k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial_ws, out, ld, 1);
-    MGV_LAUNCH_RET();
+    return mgv::recon_heavy<false>(H, s, t, ld, Epos, gscale, 0.f, K, nodes, node_seg_ptr, S, seg_node, seg_e0, seg_e1, list, which, partial_ws,
+                                   out, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int mgv_recon_step_heavy_lists(int H, const float* s, const float* t, int ld, int64_t Epos, float expect_scale, int K,
@@ -694,19 +702,8 @@ extern "C" int mgv_recon_step_heavy_lists(int H, const float* s, const float* t,
                                           const int32_t* seg_e0, const int32_t* seg_e1, const int32_t* list, int which, float* partial_ws,
                                           float* out, double* sums, uint64_t* counts, double* workspace, int64_t workspace_doubles,
                                           void* stream) {
-    MGV_CHECK_ARG(K >= 0 && S >= 0 && Epos > 0 && s && t && out && ld >= H && ld % 4 == 0 && (which == 0 || which == 1));
-    MGV_CHECK_ARG(which == 1 || (sums && counts));
-    if (K == 0 || S == 0) return MGV_OK;
-    MGV_CHECK_ARG(nodes && node_seg_ptr && seg_node && seg_e0 && seg_e1 && list && partial_ws);
-    const int grid = S < 4096 ? S : 4096;
-    MGV_CHECK_ARG(which == 1 || (workspace && workspace_doubles >= (int64_t)grid));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_recon_heavy_seg<HH, true>), dim3(grid), dim3(256), 0, st, S, seg_node, seg_e0, seg_e1, nodes,
-                                         s, t, ld, list, which, Epos, nullptr, expect_scale, partial_ws, workspace,
-                                         reinterpret_cast<unsigned long long*>(counts)));
-    if (which == 0) mgv::launch_slab_sum<double, double>(workspace, grid, 1, 1, sums, st);
-    hipLaunchKernelGGL(mgv::k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial_ws, out, ld, 1);
-    MGV_LAUNCH_RET();
+    return mgv::recon_heavy<true>(H, s, t, ld, Epos, nullptr, expect_scale, K, nodes, node_seg_ptr, S, seg_node, seg_e0, seg_e1, list, which,
+                                  partial_ws, out, sums, counts, workspace, workspace_doubles, stream);
 }
 
 extern "C" int mgv_rows_rescale_unless(int64_t n_floats, float* rows, const float* g_dev, float expect_scale, void* stream) {
@@ -723,15 +720,16 @@ extern "C" int mgv_func_loss_fwd(int H, int64_t P, const float* hf, const int64_
                                  void* stream) {
     MGV_CHECK_ARG(P >= 2 && hf && pair_a && pair_b && tt && dis && ws);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int g1 = 0;
-    MGV_DISPATCH_H(H, g1 = mgv::items_grid(P, mgv::kThreads / (HH / 4)));
-    const int g2 = mgv::items_grid(P, mgv::kThreads);
-    MGV_CHECK_ARG(workspace && workspace_doubles >= 4 * (int64_t)g1 && workspace_doubles >= 3 * (int64_t)g2);
-    MGV_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_func_dist<HH>), dim3(g1), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b, tt, eps, dis, workspace));
-    mgv::launch_slab_sum<double, double>(workspace, g1, 4, 4, ws, st);
-    hipLaunchKernelGGL(mgv::k_func_l1, dim3(g2), dim3(mgv::kThreads), 0, st, P, dis, tt, ws, workspace);
-    mgv::launch_slab_sum<double, double>(workspace, g2, 3, 3, ws + 4, st);
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        const int g1 = mgv::items_grid(P, mgv::kThreads / (HH / 4)), g2 = mgv::items_grid(P, mgv::kThreads);
+        MGV_CHECK_ARG(workspace && workspace_doubles >= 4 * (int64_t)g1 && workspace_doubles >= 3 * (int64_t)g2);
+        hipLaunchKernelGGL(mgv::k_func_dist<HH>, dim3(g1), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b, tt, eps, dis, workspace);
+        mgv::launch_slab_sum<double, double>(workspace, g1, 4, 4, ws, st);
+        hipLaunchKernelGGL(mgv::k_func_l1, dim3(g2), dim3(mgv::kThreads), 0, st, P, dis, tt, ws, workspace);
+        mgv::launch_slab_sum<double, double>(workspace, g2, 3, 3, ws + 4, st);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_func_loss_bwd_csr(int H, int64_t N, int64_t P, const float* hf, const int64_t* pair_a, const int64_t* pair_b, const float* tt,
@@ -740,13 +738,11 @@ extern "C" int mgv_func_loss_bwd_csr(int H, int64_t N, int64_t P, const float* h
     MGV_CHECK_ARG(N >= 0 && P >= 2 && hf && pair_a && pair_b && tt && dis && ws && gscale && a_ptr && a_pair && b_ptr && b_pair && dhf);
     if (N == 0) return MGV_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 16: hipLaunchKernelGGL((mgv::k_func_bwd_pull<16>), dim3(mgv::items_grid(N, mgv::kThreads / 4)), dim3(mgv::kThreads), 0, st, N, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, a_ptr, a_pair, b_ptr, b_pair, add, dhf); break;
-        case 32: hipLaunchKernelGGL((mgv::k_func_bwd_pull<32>), dim3(mgv::items_grid(N, mgv::kThreads / 8)), dim3(mgv::kThreads), 0, st, N, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, a_ptr, a_pair, b_ptr, b_pair, add, dhf); break;
-        case 64: hipLaunchKernelGGL((mgv::k_func_bwd_pull<64>), dim3(mgv::items_grid(N, mgv::kThreads / 16)), dim3(mgv::kThreads), 0, st, N, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, a_ptr, a_pair, b_ptr, b_pair, add, dhf); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::LaneWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        hipLaunchKernelGGL(mgv::k_func_bwd_pull<HH>, dim3(mgv::items_grid(N, mgv::kThreads / (HH / 4))), dim3(mgv::kThreads), 0, st, N, P, hf,
+                           pair_a, pair_b, tt, dis, eps, ws, gscale, a_ptr, a_pair, b_ptr, b_pair, add, dhf);
+    });
 }
 
 extern "C" int mgv_func_loss_bwd(int H, int64_t P, const float* hf, const int64_t* pair_a, const int64_t* pair_b,
@@ -754,13 +750,11 @@ extern "C" int mgv_func_loss_bwd(int H, int64_t P, const float* hf, const int64_
                                  float* dhf, void* stream) {
     MGV_CHECK_ARG(P >= 2 && hf && pair_a && pair_b && tt && dis && ws && gscale && dhf);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {     // one float per lane: the row must fit a wave
-        case 16: hipLaunchKernelGGL((mgv::k_func_bwd<16>), dim3(mgv::items_grid(P, mgv::kThreads / 16)), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, dhf); break;
-        case 32: hipLaunchKernelGGL((mgv::k_func_bwd<32>), dim3(mgv::items_grid(P, mgv::kThreads / 32)), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, dhf); break;
-        case 64: hipLaunchKernelGGL((mgv::k_func_bwd<64>), dim3(mgv::items_grid(P, mgv::kThreads / 64)), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b, tt, dis, eps, ws, gscale, dhf); break;
-        default: return MGV_EUNSUPPORTED;
-    }
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::LaneWidths{}, H, [&](auto w) {     // one float per lane: the row must fit a wave
+        constexpr int HH = w;
+        hipLaunchKernelGGL(mgv::k_func_bwd<HH>, dim3(mgv::items_grid(P, mgv::kThreads / HH)), dim3(mgv::kThreads), 0, st, P, hf, pair_a, pair_b,
+                           tt, dis, eps, ws, gscale, dhf);
+    });
 }
 
 extern "C" int mgv_reparam_fwd(int64_t n, const float* mu, const float* logstd, const float* eps, uint64_t seed,

@@ -66,6 +66,15 @@ static __global__ __launch_bounds__(256) void k_heavy_add(int K, int H, const in
     }
 }
 
+// Launch geometry of the heavy-list kernels: one workgroup per segment up to 4096 (a segment kernel strides over the rest), then
+// k_heavy_add with 16 nodes per workgroup.
+inline int heavy_seg_grid(int S) { return S < 4096 ? S : 4096; }
+static inline void launch_heavy_add(int K, int H, const int32_t* nodes, const int32_t* node_seg_ptr, const float* partial, float* out, int ld,
+                                    int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(k_heavy_add, dim3((K + 15) / 16 < 1024 ? (K + 15) / 16 : 1024), dim3(256), 0, st, K, H, nodes, node_seg_ptr, partial, out,
+                       ld, accumulate);
+}
+
 // out[k][0..W) = sum of node k's segment partials (k in [k0, k1): rows indexed by k, not by node id)
 static __global__ __launch_bounds__(256) void k_heavy_add_range(int k0, int k1, int W, const int32_t* node_seg_ptr, const float* partial, float* out) {
     const int lpr = W / 4, lr = threadIdx.x % lpr;

@@ -10,7 +10,7 @@
 // its thresholded pairs come from the symmetric form of the selection walk (k_pair_select<.., SYM>).
 // The classes of that relation come from the same walk with a union-find in place of the lists (k_sim_union, mgv_unionfind.h).
 // The rank of a true link among all candidates of its node comes from the same walk with a list of thresholds per row (k_pair_rank).
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "mgv_unionfind.h"
 #include "../../include/mgvae_hip.h"
 
@@ -740,22 +740,13 @@ __global__ __launch_bounds__(kThreads) void k_row_unit(int64_t N, const float* x
     }
 }
 
-inline bool pair_h_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
+inline bool pair_h_ok(int H) { return has_width(AllWidths{}, H); }
 inline bool pair_rows_ok(const float* x, int ld, int H) { return x != nullptr && ld >= H && ld % 4 == 0 && ((uintptr_t)x & 15) == 0; }
 
 }  // namespace mgv
 
-#define MGV_PAIR_DISPATCH_H(H, EXPR)                                            \
-    switch (H) {                                                                \
-        case 16: { constexpr int HH = 16; EXPR; } break;                        \
-        case 32: { constexpr int HH = 32; EXPR; } break;                        \
-        case 64: { constexpr int HH = 64; EXPR; } break;                        \
-        default: { constexpr int HH = 128; EXPR; } break;                       \
-    }
-// the same with the walk's form as SYM (true: s = t = unit rows, every unordered pair once)
-#define MGV_PAIR_DISPATCH_H_SYM(H, sym, EXPR)                                   \
-    if (sym) { constexpr bool SYM = true; MGV_PAIR_DISPATCH_H(H, EXPR) }        \
-    else { constexpr bool SYM = false; MGV_PAIR_DISPATCH_H(H, EXPR) }
+using mgv::dispatch_width;
+using mgv::launch_width;
 
 extern "C" int mgv_pair_scores_fwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid,
                                    float* out, int64_t ldo, void* stream) {
@@ -767,9 +758,9 @@ extern "C" int mgv_pair_scores_fwd(int H, int64_t M, int64_t N, const float* s, 
     const int64_t chunks = (nct + mgv::kPairChunk - 1) / mgv::kPairChunk;
     if (nrt > 0x7fffffffLL || chunks > 65535) return MGV_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_fwd<HH>), dim3((unsigned)nrt, (unsigned)chunks), dim3(mgv::kThreads), 0, st,
-                                              M, N, s, lds, t, ldt, sigmoid, out, ldo));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        hipLaunchKernelGGL(mgv::k_pair_fwd<w>, dim3((unsigned)nrt, (unsigned)chunks), dim3(mgv::kThreads), 0, st, M, N, s, lds, t, ldt, sigmoid, out, ldo);
+    });
 }
 
 extern "C" int mgv_pair_scores_bwd(int H, int64_t M, int64_t N, const float* s, int lds, const float* t, int ldt, int sigmoid,
@@ -789,17 +780,15 @@ extern "C" int mgv_pair_scores_bwd(int H, int64_t M, int64_t N, const float* s, 
     const int64_t bs = (M + mgv::kPairTile - 1) / mgv::kPairTile, bt = (N + mgv::kPairTile - 1) / mgv::kPairTile;
     if (bs > 0x7fffffffLL || bt > 0x7fffffffLL) return MGV_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (want_ds) {      // an empty walked dimension leaves zeros
-        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_bwd<HH, false>), dim3((unsigned)bs), dim3(mgv::kThreads), 0, st,
-                                                  M, N, t, ldt, sigmoid, out, ldo, gout, ldg, ds, ldds));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    if (want_dt) {
-        MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_bwd<HH, true>), dim3((unsigned)bt), dim3(mgv::kThreads), 0, st,
-                                                  N, M, s, lds, sigmoid, out, ldo, gout, ldg, dt, lddt));
-    }
-    MGV_LAUNCH_RET();
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        if (want_ds) {      // an empty walked dimension leaves zeros
+            hipLaunchKernelGGL((mgv::k_pair_bwd<w, false>), dim3((unsigned)bs), dim3(mgv::kThreads), 0, st, M, N, t, ldt, sigmoid, out, ldo, gout, ldg, ds, ldds);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+        }
+        if (want_dt) hipLaunchKernelGGL((mgv::k_pair_bwd<w, true>), dim3((unsigned)bt), dim3(mgv::kThreads), 0, st, N, M, s, lds, sigmoid, out, ldo, gout, ldg, dt, lddt);
+        MGV_LAUNCH_RET();
+    });
 }
 
 extern "C" int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, const float* t, int ldt, const int64_t* src,
@@ -810,9 +799,9 @@ extern "C" int mgv_pair_scores_at(int H, int64_t E, const float* s, int lds, con
     MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H) && src != nullptr && dst != nullptr && out != nullptr);
     hipStream_t st = (hipStream_t)stream;
     const int grid = mgv::grid_for((E + mgv::kThreads - 1) / mgv::kThreads, 8);
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_pair_at<HH>), dim3(grid), dim3(mgv::kThreads), 0, st, E, s, lds, t, ldt, src, dst,
-                                              sigmoid, out));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        hipLaunchKernelGGL(mgv::k_pair_at<w>, dim3(grid), dim3(mgv::kThreads), 0, st, E, s, lds, t, ldt, src, dst, sigmoid, out);
+    });
 }
 
 // the arguments every walk entry shares, checked in this order by all of them; *launch = false: nothing to walk
@@ -853,9 +842,9 @@ extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const fl
     const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
     if (rc != MGV_OK || !launch) return rc;
     MGV_CHECK_ARG(idx != nullptr && score != nullptr && n_above != nullptr);
-    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_pair_topk<HH>, N, st, N, s, lds, t, ldt, graph_ptr, G, k, sigmoid, threshold, skip_self,
-                                            idx, score, n_above));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_pair_topk<w>, N, st, N, s, lds, t, ldt, graph_ptr, G, k, sigmoid, threshold, skip_self, idx, score, n_above);
+    });
 }
 
 // the two count entries; sym: s = t = unit rows, and `sigmoid` / `skip_self` come in as 0
@@ -865,9 +854,10 @@ static int select_count_run(int H, int64_t N, const float* s, int lds, const flo
     const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
     if (rc != MGV_OK || !launch) return rc;
     MGV_CHECK_ARG(n_sel != nullptr);
-    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_select<HH, false, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid,
-                                                     threshold, skip_self, n_sel, nullptr, 0, nullptr, nullptr));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_select<w, false, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, n_sel, nullptr, 0, nullptr, nullptr); };
+        if (sym) walk(std::true_type{}); else walk(std::false_type{});
+    });
 }
 
 // the two fill entries, as select_count_run
@@ -881,9 +871,10 @@ static int select_fill_run(int H, int64_t N, const float* s, int lds, const floa
     if (rc != MGV_OK || !launch) return rc;
     if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
     MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
-    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_select<HH, true, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid,
-                                                     threshold, skip_self, nullptr, row_ptr, cap, col, score));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_select<w, true, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, nullptr, row_ptr, cap, col, score); };
+        if (sym) walk(std::true_type{}); else walk(std::false_type{});
+    });
 }
 
 extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
@@ -904,10 +895,10 @@ extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(mgv::pair_rows_ok(x, ldx, H) && mgv::pair_rows_ok(y, ldy, H));
     hipStream_t st = (hipStream_t)stream;
-    const int rows = mgv::kThreads / (H / 4);
-    const int grid = mgv::grid_for((N + rows - 1) / rows, 8);
-    MGV_PAIR_DISPATCH_H(H, hipLaunchKernelGGL((mgv::k_row_unit<HH>), dim3(grid), dim3(mgv::kThreads), 0, st, N, x, ldx, eps, y, ldy, norm));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w, rows = mgv::kThreads / (HH / 4);
+        hipLaunchKernelGGL(mgv::k_row_unit<HH>, dim3(mgv::grid_for((N + rows - 1) / rows, 8)), dim3(mgv::kThreads), 0, st, N, x, ldx, eps, y, ldy, norm);
+    });
 }
 
 extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
@@ -928,8 +919,9 @@ extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const in
     if (rc != MGV_OK) return rc;
     MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
     if (!launch) return MGV_OK;
-    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_sim_union<HH>, N, st, N, y, ldy, graph_ptr, G, threshold, parent, status));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_sim_union<w>, N, st, N, y, ldy, graph_ptr, G, threshold, parent, status);
+    });
 }
 
 // the two profile entries: checks in the order of the selection entries, then the table; *launch = false: hist is zero and nothing is left to do
@@ -954,9 +946,10 @@ static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float*
     int top = 1;                                                          // half the first power of two above B
     while (2 * top <= B) top *= 2;
     unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-    MGV_PAIR_DISPATCH_H_SYM(H, sym, launch_row_tiles(mgv::k_pair_hist<HH, SYM>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self,
-                                                     edges, B, top, h));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_hist<w, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, edges, B, top, h); };
+        if (sym) walk(std::true_type{}); else walk(std::false_type{});
+    });
 }
 
 extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
@@ -991,7 +984,7 @@ extern "C" int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, c
     MGV_CHECK_ARG(mgv::pair_rows_ok(s, lds, H) && mgv::pair_rows_ok(t, ldt, H));
     if (T == 0) return MGV_OK;                                            // nothing is listed: nothing to write
     MGV_CHECK_ARG(thr != nullptr && n_gt != nullptr && n_eq != nullptr);
-    MGV_PAIR_DISPATCH_H(H, launch_row_tiles(mgv::k_pair_rank<HH>, N, st, N, s, lds, t, ldt, graph_ptr, G, skip_self, thr_ptr, T, thr, n_gt,
-                                            n_eq));
-    MGV_LAUNCH_RET();
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_pair_rank<w>, N, st, N, s, lds, t, ldt, graph_ptr, G, skip_self, thr_ptr, T, thr, n_gt, n_eq);
+    });
 }

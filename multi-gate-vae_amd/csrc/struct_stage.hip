@@ -10,7 +10,7 @@
 //
 // HBM traffic per node and half round (fp32): forward  = gather deg*H*4 + read H*4 + write H*4;
 // backward = 2 gathers + 2 reads + 2 writes of H*4.  The dense part runs on v_mfma_f32_16x16x4_f32.
-#include "mgv_common.h"
+#include "mgv_launch.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
@@ -553,8 +553,8 @@ __global__ __launch_bounds__(kThreads) void k_struct_stage_bwd(StageArgs a) {
 
 template <int H>
 int launch_fwd(const StageArgs& a, hipStream_t st) {
-    const size_t shm = StageSmem<H>::fwd_floats * sizeof(float);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_struct_stage_fwd<H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    constexpr size_t shm = StageSmem<H>::fwd_floats * sizeof(float);
+    allow_lds<k_struct_stage_fwd<H>, (int)shm>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     const int per_cu = (int)(160 * 1024 / shm) < 4 ? (int)(160 * 1024 / shm) : 4;
     hipLaunchKernelGGL(k_struct_stage_fwd<H>, dim3(grid_for(ntiles, per_cu < 1 ? 1 : per_cu)), dim3(kThreads), shm, st, a);
@@ -562,8 +562,8 @@ int launch_fwd(const StageArgs& a, hipStream_t st) {
 }
 template <int H>
 int launch_bwd(const StageArgs& a, hipStream_t st) {
-    const size_t shm = StageSmem<H>::bwd_floats * sizeof(float);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_struct_stage_bwd<H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    constexpr size_t shm = StageSmem<H>::bwd_floats * sizeof(float);
+    allow_lds<k_struct_stage_bwd<H>, (int)shm>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     hipLaunchKernelGGL(k_struct_stage_bwd<H>, dim3(grid_for(ntiles, 1)), dim3(kThreads), shm, st, a);
     MGV_LAUNCH_RET();
@@ -598,18 +598,7 @@ static int stage_run(int H, const StageArgs& a, bool bwd, void* stream) {
     if (a.N == 0) return MGV_OK;
     MGV_CHECK_ARG(a.idx != nullptr);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!bwd) switch (H) {
-        case 16: return launch_fwd<16>(a, st);
-        case 32: return launch_fwd<32>(a, st);
-        case 64: return launch_fwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
-    switch (H) {
-        case 16: return launch_bwd<16>(a, st);
-        case 32: return launch_bwd<32>(a, st);
-        case 64: return launch_bwd<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    return dispatch_width(LaneWidths{}, H, [&](auto w) { return bwd ? launch_bwd<w>(a, st) : launch_fwd<w>(a, st); });
 }
 
 }  // namespace mgv

@@ -23,6 +23,7 @@
 #include <cstddef>
 #include <type_traits>
 #include "struct_stage_x3_common.h"
+#include "mgv_launch.h"
 
 namespace mgv {
 
@@ -601,10 +602,7 @@ int launch_stage_slab_reduce(const StageX3Args& s, float* workspace, int grid, h
 }
 
 int launch_bwd2_x3(const StageX3Args& s, float* workspace, int64_t workspace_floats, hipStream_t st) {
-    static bool set[64] = {false};      // per device: each device loads its own copy of the code object
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (!set[dev & 63]) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_struct_stage_bwd2_x3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set[dev & 63] = true; }
+    allow_lds<k_struct_stage_bwd2_x3>();
     const int64_t ntiles = (s.N + kTileRows - 1) / kTileRows;
     const int grid = grid_for(ntiles, 1);
     if (workspace == nullptr || workspace_floats < (int64_t)grid * B2::SLAB) return MGV_EINVAL;
@@ -624,7 +622,7 @@ extern "C" int mgv_diag_set_stamps2(void* p) { g_stamps2 = static_cast<unsigned 
 #endif
 
 extern "C" int mgv_struct_stage_bwd2_ws_floats(int H, int64_t N) {
-    if (H != 64 || N < 0) return 0;
+    if (H != mgv::B2::H || N < 0) return 0;
     const int64_t ntiles = (N + mgv::kTileRows - 1) / mgv::kTileRows;
     return mgv::grid_for(ntiles, 1) * mgv::B2::SLAB;      // <= 256 workgroups x 28,800 floats
 }
@@ -640,7 +638,7 @@ extern "C" int mgv_struct_stage_bwd2_x3(int H, int64_t N, const float* h_in, con
     mgv::StageX3Args a{};
     if (int rc = mgv::stage_x3_args(a, N, h_in, nbr_ptr, nbr_idx, xcls, xtab, C, wpack_bf16, bc, bhh, ln_w, ln_b, ln_eps, table_own_idx, nbr_tagged, const_cast<float*>(ln_stats))) return rc;
     if (int rc = mgv::stage_x3_bwd_args(a, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, dxtab, dln_w, dln_b)) return rc;
-    if (H != 64) return MGV_EUNSUPPORTED;
+    if (H != mgv::B2::H) return MGV_EUNSUPPORTED;      // the kernel is written for one width
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
     if (int rc = mgv::stage_x3_lists(N, heavy_n, heavy_nodes, heavy_ws, table_own_idx, nbr_tagged)) return rc;

@@ -10,6 +10,7 @@
 // Timing ablations of the forward kernel (builds without its MFMAs, GRU epilogue, row gathers or output stores, wrong by design) priced its
 // parts in round 3: row gathers expose 0.37 ms of 1.26 ms (NOTEBOOK r3 §4.3); they are no longer in this source.
 #include "struct_stage_x3_common.h"
+#include "mgv_launch.h"
 
 namespace mgv {
 
@@ -593,8 +594,7 @@ __global__ __launch_bounds__(kThreadsX3) void k_struct_stage_bwd_x3(StageX3Args 
 template <int H>
 int launch_fwd_x3(const StageX3Args& a, hipStream_t st) {
     const size_t shm = X3Smem<H>::fwd_bytes;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_struct_stage_fwd_x3<H>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_struct_stage_fwd_x3<H>>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     int per_cu = (int)(160 * 1024 / shm);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
@@ -604,8 +604,7 @@ int launch_fwd_x3(const StageX3Args& a, hipStream_t st) {
 template <int H>
 int launch_bwd_x3(const StageX3Args& a, hipStream_t st) {
     const size_t shm = X3Smem<H>::bwd_bytes;
-    static bool set = false;
-    if (!set) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_struct_stage_bwd_x3<H>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = true; }
+    allow_lds<k_struct_stage_bwd_x3<H>>();
     const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
     hipLaunchKernelGGL(k_struct_stage_bwd_x3<H>, dim3(grid_for(ntiles, 1)), dim3(kThreadsX3), shm, st, a);
     MGV_LAUNCH_RET();
@@ -635,11 +634,10 @@ extern "C" int mgv_struct_stage_fwd_x3(int H, int64_t N, const float* h_in, cons
     a.h_out = h_out;
     MGV_SET_STAMPS(a);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (H) {
-        case 32: mgv::launch_heavy_sums<32>(a, heavy_n, heavy_nodes, heavy_ws, false, st); return mgv::launch_fwd_x3<32>(a, st);
-        case 64: mgv::launch_heavy_sums<64>(a, heavy_n, heavy_nodes, heavy_ws, false, st); return mgv::launch_fwd_x3<64>(a, st);
-        default: return MGV_EUNSUPPORTED;
-    }
+    return mgv::dispatch_width(mgv::X3Widths{}, H, [&](auto w) {
+        mgv::launch_heavy_sums<w>(a, heavy_n, heavy_nodes, heavy_ws, false, st);
+        return mgv::launch_fwd_x3<w>(a, st);
+    });
 }
 
 // H = 32 only: at H = 64 the backward is mgv_struct_stage_bwd2_x3 (struct_stage_bwd2_x3.hip)
@@ -656,8 +654,9 @@ extern "C" int mgv_struct_stage_bwd_x3(int H, int64_t N, const float* h_in, cons
     if (int rc = mgv::stage_x3_bwd_args(a, gy_direct, gy_agg, g_direct_out, g_agg_out, dWc, dbc, dWhh, dbhh, dxtab, dln_w, dln_b)) return rc;
     if (N == 0) return MGV_OK;
     MGV_CHECK_ARG(nbr_idx != nullptr);
-    if (H != 32) return MGV_EUNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    mgv::launch_heavy_sums<32>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, st);
-    return mgv::launch_bwd_x3<32>(a, st);
+    return mgv::dispatch_width(mgv::Widths<32>{}, H, [&](auto w) {
+        mgv::launch_heavy_sums<w>(a, heavy_n, heavy_nodes, heavy_ws, gy_agg != nullptr, st);
+        return mgv::launch_bwd_x3<w>(a, st);
+    });
 }

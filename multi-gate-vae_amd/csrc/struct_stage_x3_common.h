@@ -435,7 +435,8 @@ __device__ __forceinline__ void wgrad_blk_flush_x3(const f32x4 (&acc)[4], float*
 }
 
 // ---- host side: the one place that validates and fills the arguments the three bf16x3 entries share (struct_stage_x3.hip: forward and
-// first backward; struct_stage_bwd2_x3.hip).  An entry runs: these checks (MGV_EINVAL), then N == 0 (MGV_OK), then nbr_idx, then the width.
+// first backward; struct_stage_bwd2_x3.hip).  An entry runs: these checks (MGV_EINVAL), then N == 0 (MGV_OK), then nbr_idx, then the width
+// (mgv_struct_stage_bwd2_x3: the width right behind its checks, in front of N == 0).
 inline int stage_x3_args(StageX3Args& a, int64_t N, const float* h_in, const int32_t* nbr_ptr, const int32_t* nbr_idx, const uint8_t* xcls,
                          const float* xtab, int C, const void* wpack_bf16, const float* bc, const float* bhh, const float* ln_w,
                          const float* ln_b, float ln_eps, const int32_t* table_own_idx, int nbr_tagged, float* ln_stats) {

@@ -26,7 +26,7 @@ FIRST_STAGE_TABLE = True          # first half round per (degree, class) pair / 
 
 
 def use_x3(H):
-    return PRECISION == 'x3' and H in (32, 64)
+    return PRECISION == 'x3' and H in (32, 64)          # csrc/mgv_launch.h X3Widths
 
 
 def split_bf16(w):
@@ -613,7 +613,7 @@ def gather_sum(h, nbr_ptr=None, nbr_idx=None, plan=None, reverse=False):
 # ------------------------------------------------------------------------------------------------
 # DiGAE baseline layer (DirectedGCNConv, digae_layer.py:73-114)
 # ------------------------------------------------------------------------------------------------
-DIGCN_WIDTHS = (16, 32, 64, 128)
+DIGCN_WIDTHS = (16, 32, 64, 128)          # csrc/mgv_launch.h AllWidths
 
 
 def digcn_scales(plan, reverse, alpha, beta, self_loops):
@@ -939,7 +939,7 @@ def _pair_operands(s, t):
     return sd, lds, td, ldt, sd.shape[1]
 
 
-_PAIR_WIDTHS = (16, 32, 64, 128)
+_PAIR_WIDTHS = (16, 32, 64, 128)          # csrc/mgv_launch.h AllWidths
 
 
 def _pair_width(x, name):

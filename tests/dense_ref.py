@@ -59,10 +59,10 @@ GEOMETRY = {
                       'linear_x3.hip launch_linear_fwd_x3: per_cu = min(4, 160 KiB / smem_bytes)'),
     'linear_wgrad_x3': (lambda s: min(1024 // (64 * X3_WGRAD_WAVES[s]), LDS_BYTES // x3_wgrad_smem(*s)), lambda s: TILE,
                         'linear_x3.hip launch_linear_wgrad_x3: per_cu = min(1024 / NT, 160 KiB / smem_bytes)'),
-    'gather_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_gather_sum: grid_for(ceil(N / rows_per_block), 16)'),
-    'seg_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_seg_sum: grid_for(ceil(n_seg / rows_per_block), 16)'),
-    'class_expand': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_class_expand: grid_for(ceil(N / rows_per_block), 16)'),
-    'class_pull_sum': (lambda H: 8, lambda H: THREADS // (H // 4), 'dense.hip class_pull_grid: grid_for(ceil(N / rows_per_block), 8); U = 4'),
+    'gather_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_gather_sum: row_grid<H>(N, 16) = grid_for(ceil(N / rows_per_block), 16)'),
+    'seg_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_seg_sum: row_grid<H>(n_seg, 16) = grid_for(ceil(n_seg / rows_per_block), 16)'),
+    'class_expand': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_class_expand: row_grid<H>(N, 16) = grid_for(ceil(N / rows_per_block), 16)'),
+    'class_pull_sum': (lambda H: 8, lambda H: THREADS // (H // 4), 'dense.hip mgv_class_pull_sum: row_grid<H>(N, 8) = grid_for(ceil(N / rows_per_block), 8); U = 4'),
 }
 
 

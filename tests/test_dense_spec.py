@@ -227,7 +227,7 @@ def test_lists_hold_the_designed_lengths(H):
 
 
 def test_both_class_count_paths():
-    """dense.hip MGV_CPS: register sums up to 8 classes, LDS atomics above; the cases hold every class but the absent one."""
+    """dense.hip mgv_class_pull_sum (launch_class_pull_sum<H, 8> / <H, 0>): register sums up to 8 classes, LDS atomics above; the cases hold every class but the absent one."""
     for C in (8, 9, 40):
         q = DR.class_case(64, 1000, C)
         assert set(q['class_id'].tolist()) == set(range(C)) - {q['absent']} and 40 * 128 * 20 <= 160 * 1024
