@@ -184,7 +184,7 @@ int mgv_linear_bwd_x3(int64_t N, const float* X1, int K1, int ld1, const float* 
                       int M, const void* wtpack_bf16, float* dW, float* db, float* dX1, int ldx1, float* dX2, int ldx2,
                       const float* R, int ldr, float* workspace, int64_t workspace_floats, void* stream);
 /* agg[i] = sum_{j in nbr(i)} h[j] added in list order, deg[i] = |nbr(i)| (deg may be NULL): the scatter-add half of
- * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34).  H in {16, 32, 64, 128} here and in the three
+ * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34).  H in {16, 32, 64, 128} here and in the
  * row-sum entries below; any other H (0 and other non-multiples of 4 included) returns MGV_EUNSUPPORTED before anything is computed. */
 int mgv_gather_sum(int H, int64_t N, const float* h, const int32_t* nbr_ptr, const int32_t* nbr_idx,
                    float* agg, float* deg, void* stream);
@@ -205,6 +205,16 @@ int mgv_class_expand(int H, int64_t N, const float* table, const int32_t* class_
  * with more members than that leave partial rows behind the C final ones for the next level (most colours have a few members). */
 int mgv_seg_sum(int H, int64_t n_seg, const int32_t* seg_ptr, const int32_t* items, const float* direct, const float* agg,
                 const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* out_row, float* out, void* stream);
+/* The same sums over a flat entry list, bit for bit (the additions of mgv_seg_sum in its order: a member's own row, + its pulled rows left
+ * to right, then the member into the segment's sum, members in list order, from zero): seg_ptr[n_seg + 1] counts ENTRIES; entry >= 0 is row
+ * `entry` of direct and starts a new member, entry < 0 is row ~entry of agg and continues the member (mgv_seg_entries writes such a list once
+ * per plan; an items-only table is one as it stands).  entries NULL: the identity list (entry p = row p of direct: the levels above the
+ * first); agg may be NULL when no entry is negative, and needs a list.  A lane group loads 8 entries at a time (4 at H = 16) and has their
+ * rows in flight together; entry positions are int and a batch is formed as p + 8, so seg_ptr[n_seg] <= 2^31 - 9 (the caller's to keep:
+ * mgv_seg_entries writes no longer list).  Refusals in this order: H outside {16, 32, 64, 128} MGV_EUNSUPPORTED; n_seg < 0, NULL seg_ptr / direct / out, or
+ * agg without entries MGV_EINVAL; n_seg == 0 MGV_OK with nothing launched. */
+int mgv_seg_sum_entries(int H, int64_t n_seg, const int32_t* seg_ptr, const int32_t* entries, const float* direct, const float* agg,
+                        const int32_t* out_row, float* out, void* stream);
 
 int mgv_class_pull_sum_ws_floats(int H, int64_t N, int C);
 int mgv_class_pull_sum(int H, int64_t N, const float* gy_direct, const float* gy_agg, const int32_t* nbr_ptr,
@@ -735,6 +745,15 @@ int mgv_seg_level_work_ints(int64_t G);                                         
 int mgv_seg_level_scan(int64_t G, const int32_t* counts, int seg, int32_t* work, int64_t work_ints, void* stream);
 int mgv_seg_level_fill(int64_t G, int64_t n_seg, const int32_t* gid, int seg, int base, const int32_t* work, int32_t* seg_ptr, int32_t* out_row,
                        int32_t* gid_next, int32_t* counts_next, void* stream);
+/* the flat entry list of mgv_seg_sum_entries for a level-1 table whose members pull their lists: per member position m of items[n_items], in
+ * order, items[m] and then ~nbr_idx[e] over items[m]'s list; ent_seg_ptr[s] = entry position of member seg_ptr[s] for s in [0, n_seg]
+ * (ent_seg_ptr[n_seg] = entries the tables ask for).  entries[n_entries]: nothing is written behind it (a list of every node once: N + E).
+ * Refusals: negative sizes, n_entries < n_items or > 2^31 - 9 (what mgv_seg_sum_entries can walk), NULL seg_ptr / ent_seg_ptr MGV_EINVAL; then n_items == 0 returns MGV_OK with
+ * nothing written or launched (every pointer of such a table is 0: the caller's to set); then NULL items / nbr_ptr / nbr_idx / entries /
+ * scratch, or scratch_ints below mgv_seg_entries_scratch_ints(n_items) (0 for a size it does not serve) MGV_EINVAL. */
+int mgv_seg_entries_scratch_ints(int64_t n_items);                                                  /* a size */
+int mgv_seg_entries(int64_t n_items, const int32_t* items, const int32_t* nbr_ptr, const int32_t* nbr_idx, int64_t n_seg, const int32_t* seg_ptr,
+                    int64_t n_entries, int32_t* entries, int32_t* ent_seg_ptr, int32_t* scratch, int64_t scratch_ints, void* stream);
 
 /* ---- DiGAE baseline layer, DirectedGCNConv (digae_layer.py:73-114; csrc/digcn_conv.hip).  The lists L(i) a node sums over arrive as a
  * CSR (GraphPlan.csr(reverse): the in-CSR for edge_index as given, the out-CSR for torch.flip(edge_index, [0]), :131,146); with

@@ -304,6 +304,81 @@ __global__ __launch_bounds__(kThreads) void k_seg_sum(int64_t n_seg, const int32
     }
 }
 
+// The same sums over a FLAT entry list (GraphPlan.seg_entries, csrc/plan_build.hip mgv_seg_entries): what k_seg_sum resolves per call
+// through items -> nbr_ptr -> nbr_idx is static per plan, so the plan builder writes it once, in member order:
+//     entry >= 0: row `entry` of direct, starts a new member;    entry < 0: row ~entry of agg, continues the member
+// and seg_ptr counts entries.  A lane group walks its segments as one stream of BATCHES of kSegBatch consecutive entries: the lanes
+// fetch a batch with one load and hand it round by shuffles, and all rows of a batch are in flight before the first addition.  What
+// the batch after this one needs is issued in FRONT of this batch's rows — its entries (the next ones of this segment, or the first
+// ones of the group's next segment), and at a segment's end the pointers and output row of the segment after the next — so a batch
+// waits for one round of row loads and for nothing else.
+// The additions are k_seg_sum's, in its order: v = the member's own row, + its pulled rows left to right, then acc = acc + v, members
+// in list order, acc from zero — bit for bit the same sums.  No branches on the entries (the lane groups of a wave hold different
+// segments): selects on the entry's sign.
+// entries == nullptr: the identity list (entry p = row p of direct), what the levels above the first read.
+constexpr int kSegBatch = 8;     // entries (= rows in flight) per lane group and batch; a group of fewer lanes (H = 16) takes its lane count
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_seg_sum_ent(int64_t n_seg, const int32_t* seg_ptr, const int32_t* entries, const float* direct,
+                                                         const float* agg, const int32_t* out_row, float* out) {
+    constexpr int LPR = H / 4, B = LPR < kSegBatch ? LPR : kSegBatch;
+    const int lr = threadIdx.x % LPR;
+    const int64_t stride = (int64_t)gridDim.x * (kThreads / LPR);
+    int64_t s = (int64_t)blockIdx.x * (kThreads / LPR) + threadIdx.x / LPR;
+    if (s >= n_seg) return;                                  // (a whole lane group: the shuffles below stay inside one)
+    // this segment: entries [p, p1) left, output row orow;  the group's next segment: [np0, np1), nrow (an empty range behind the last)
+    // (orow / nrow: the loaded out_row values, kept as loaded until the store needs one — a conversion here would wait for the load)
+    int p = seg_ptr[s], p1 = seg_ptr[s + 1], np0 = 0, np1 = 0, orow = 0, nrow = 0;
+    if (out_row) orow = out_row[s];
+    if (s + stride < n_seg) {
+        np0 = seg_ptr[s + stride]; np1 = seg_ptr[s + stride + 1];
+        if (out_row) nrow = out_row[s + stride];
+    }
+    int mine = 0;                                            // lane lr < B: entry p + lr
+    if (lr < B && p + lr < p1) mine = entries ? entries[p + lr] : p + lr;
+    float4 acc = zero4(), v = zero4();
+    bool open = false;                                       // v holds a member that has not been added to acc yet
+    while (s < n_seg) {
+        const bool ends = p + B >= p1;                       // the segment's last batch (an empty segment: its only one, with no row)
+        const int fp = ends ? np0 : p + B, fp1 = ends ? np1 : p1;
+        int next = 0, nn0 = 0, nn1 = 0, nnrow = 0;
+        if (lr < B && fp + lr < fp1) next = entries ? entries[fp + lr] : fp + lr;
+        const int64_t s2 = s + 2 * stride;
+        if (ends && s2 < n_seg) {
+            nn0 = seg_ptr[s2]; nn1 = seg_ptr[s2 + 1];
+            if (out_row) nnrow = out_row[s2];
+        }
+        int e[B];
+        f32x4 row[B];
+#pragma unroll
+        for (int k = 0; k < B; ++k) e[k] = __shfl(mine, k, LPR);
+#pragma unroll
+        for (int k = 0; k < B; ++k)
+            if (p + k < p1) {
+                const float* src = e[k] >= 0 ? direct + (int64_t)e[k] * H : agg + (int64_t)(~e[k]) * H;
+                row[k] = *reinterpret_cast<const f32x4*>(src + 4 * lr);
+            } else {
+                row[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+        for (int k = 0; k < B; ++k) {
+            const bool live = p + k < p1, starts = live && e[k] >= 0;
+            const float4 r = make_float4(row[k][0], row[k][1], row[k][2], row[k][3]);
+            const float4 sum = add4(acc, v), more = add4(v, r);
+            if (starts && open) acc = sum;
+            if (live) v = starts ? r : more;
+            open = open || starts;
+        }
+        if (ends) {
+            if (open) acc = add4(acc, v);
+            st4(out + (out_row ? (int64_t)orow : s) * H + 4 * lr, acc);
+            acc = v = zero4();
+            open = false;
+            s += stride; orow = nrow; nrow = nnrow; np0 = nn0; np1 = nn1;
+        }
+        p = fp; p1 = fp1; mine = next;
+    }
+}
+
 template <int M>
 int launch_linear_fwd(const LinArgs& a, hipStream_t st) {
     const int K = a.K1 + a.K2;
@@ -383,6 +458,18 @@ extern "C" int mgv_seg_sum(int H, int64_t n_seg, const int32_t* seg_ptr, const i
         if (n_seg == 0) return MGV_OK;
         hipLaunchKernelGGL(mgv::k_seg_sum<HH>, dim3(mgv::row_grid<HH>(n_seg, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
                            n_seg, seg_ptr, items, direct, agg, nbr_ptr, nbr_idx, out_row, out);
+        MGV_LAUNCH_RET();
+    });
+}
+
+extern "C" int mgv_seg_sum_entries(int H, int64_t n_seg, const int32_t* seg_ptr, const int32_t* entries, const float* direct, const float* agg,
+                                   const int32_t* out_row, float* out, void* stream) {
+    return dispatch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w;
+        MGV_CHECK_ARG(n_seg >= 0 && seg_ptr && direct && out && (!agg || entries));
+        if (n_seg == 0) return MGV_OK;
+        hipLaunchKernelGGL(mgv::k_seg_sum_ent<HH>, dim3(mgv::row_grid<HH>(n_seg, 16)), dim3(mgv::kThreads), 0, static_cast<hipStream_t>(stream),
+                           n_seg, seg_ptr, entries, direct, agg, out_row, out);
         MGV_LAUNCH_RET();
     });
 }

@@ -532,6 +532,26 @@ __global__ __launch_bounds__(256) void k_seg_level_fill(int64_t G, int64_t n_seg
     }
     if (t < G && nseg[t] > 1 && gid_next) { gid_next[midx[t]] = gid ? gid[t] : (int32_t)t; counts_next[midx[t]] = nseg[t]; }
 }
+// flat entry list of mgv_seg_sum_entries for a level-1 table with a neighbour pull: member m = items[m] takes 1 + its list length entries
+__global__ __launch_bounds__(256) void k_seg_entry_counts(int64_t n, const int32_t* items, const int32_t* ptr, int32_t* cnt) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= n) return;
+    const int i = items[m];
+    cnt[m] = 1 + ptr[i + 1] - ptr[i];
+}
+// entries[off[m]] = items[m], then ~idx[e] over the member's list; segment pointers re-expressed in entry positions.  Nothing is written
+// at or behind `cap` (the caller's buffer), whatever the tables say.
+__global__ __launch_bounds__(256) void k_seg_entry_fill(int64_t n, const int32_t* items, const int32_t* ptr, const int32_t* idx, const int32_t* off,
+                                                        int64_t cap, int64_t n_seg, const int32_t* seg_ptr, int32_t* entries, int32_t* ent_seg_ptr) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m < n) {
+        const int i = items[m], e0 = ptr[i], d = ptr[i + 1] - e0;
+        const int64_t o = off[m];
+        if (o < cap) entries[o] = i;
+        for (int k = 0; k < d; ++k) if (o + 1 + k < cap) entries[o + 1 + k] = ~idx[e0 + k];
+    }
+    if (m <= n_seg) ent_seg_ptr[m] = off[seg_ptr[m]];
+}
 
 }  // namespace mgv
 
@@ -854,5 +874,35 @@ extern "C" int mgv_seg_level_fill(int64_t G, int64_t n_seg, const int32_t* gid, 
     const int64_t threads = n_seg > G ? n_seg : G;
     hipLaunchKernelGGL(k_seg_level_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), G, n_seg, gid, seg, base, nseg,
                        first, start, pfirst, midx, seg_ptr, out_row, gid_next, counts_next);
+    MGV_LAUNCH_RET();
+}
+
+/* The flat entry list of mgv_seg_sum_entries for a level-1 segment table whose members pull their neighbour lists (GraphPlan.seg_entries):
+ * per member position m of items[n_items], in order, the entry items[m] and then ~nbr_idx[e] over items[m]'s list; ent_seg_ptr[s] = the entry
+ * position of member seg_ptr[s] (= seg_ptr[s] + the list lengths of the members before it), s in [0, n_seg], so ent_seg_ptr[n_seg] = entries
+ * written.  Three steps: entries per member, their exclusive scan, the fill.  `entries` holds n_entries ints and nothing is written behind it.
+ * n_items == 0 writes nothing at all.  scratch: mgv_seg_entries_scratch_ints(n_items) ints. */
+// (the sum kernel forms entry positions p + batch in int: a list ends at least one batch of 8 below 2^31)
+constexpr int64_t kSegEntriesMax = (1LL << 31) - 1 - 8;
+extern "C" int mgv_seg_entries_scratch_ints(int64_t n_items) {
+    const int64_t need = 2 * n_items + 1 + n_items / kScanItems + 66;
+    return n_items < 0 || n_items >= (1LL << 31) || need >= (1LL << 31) ? 0 : (int)need;          // 0: no such table (the entry refuses it)
+}
+extern "C" int mgv_seg_entries(int64_t n_items, const int32_t* items, const int32_t* nbr_ptr, const int32_t* nbr_idx, int64_t n_seg, const int32_t* seg_ptr,
+                               int64_t n_entries, int32_t* entries, int32_t* ent_seg_ptr, int32_t* scratch, int64_t scratch_ints, void* stream) {
+    MGV_CHECK_ARG(n_items >= 0 && n_seg >= 0 && n_entries >= n_items && n_entries <= kSegEntriesMax && seg_ptr && ent_seg_ptr);
+    if (n_items == 0) return MGV_OK;                      // no member, no entry: nothing is written (every pointer of such a table is 0)
+    const int need = mgv_seg_entries_scratch_ints(n_items);
+    MGV_CHECK_ARG(items && nbr_ptr && nbr_idx && entries && scratch && need > 0 && scratch_ints >= need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t* cnt = scratch;
+    int32_t* off = cnt + n_items;
+    int32_t* scan = off + n_items + 1;
+    hipLaunchKernelGGL(k_seg_entry_counts, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, n_items, items, nbr_ptr, cnt);
+    const int rc = scan_exclusive(n_items, cnt, off, scan, st);
+    if (rc != MGV_OK) return rc;
+    const int64_t threads = n_items > n_seg + 1 ? n_items : n_seg + 1;
+    hipLaunchKernelGGL(k_seg_entry_fill, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, n_items, items, nbr_ptr, nbr_idx, off, n_entries, n_seg,
+                       seg_ptr, entries, ent_seg_ptr);
     MGV_LAUNCH_RET();
 }

@@ -145,8 +145,9 @@ class GraphPlan:
 
     def warm(self, xcls=None, quotient_stages=0):
         """Build, on the CURRENT stream, the per-batch caches a train step would otherwise build lazily inside the step (each with a
-        host read-back): the first-stage (degree, class) table and the tagged lists of the half round after it, the heavy-row lists
-        and their segments.  The batch prefetcher calls this on its worker's stream, beside the previous step."""
+        host read-back): the quotient stages with the flat entry list of the boundary's gradient sums (seg_entries), or the first-stage
+        (degree, class) table and the tagged lists of the half round after it; the heavy-row lists and their segments.  The batch
+        prefetcher calls this on its worker's stream, beside the previous step."""
         self.count_self_loops()
         for rev in (False, True):
             self.heavy(rev)
@@ -161,7 +162,12 @@ class GraphPlan:
             return self                      # an encoder without half rounds (DirectedGCNConvEncoder): no colour classes, no first-stage table
         counts = sorted({int(c) for c in (quotient_stages if isinstance(quotient_stages, (tuple, list, set)) else [quotient_stages]) if int(c) > 0})
         if xcls is not None and self.N > 0 and counts and ops.QUOTIENT:
-            if all([len(self.quotient(xcls, c)) > 0 for c in counts]):
+            staged = [self.quotient(xcls, c) for c in counts]
+            if ops.SEG_LISTS:
+                for c, stages in zip(counts, staged):
+                    if 0 < len(stages) < c:  # a per-node half round follows: its gradient is summed per colour over the flat entry list
+                        self.seg_entries(stages[-1]['rev'], *stages[-1]['sum_levels'])
+            if all([len(stages) > 0 for stages in staged]):
                 return self                  # the quotient stages replace the first-stage table and its tagged lists
         if xcls is not None and self.N > 0:
             first = self.first_stage_classes(xcls)
@@ -605,6 +611,46 @@ class GraphPlan:
                 return order, dict(C=C, rows=base, levels=levels, counts=counts0)
             gid, counts = gid[multi], nseg[multi]
             src_row, base = base, base + n_partial
+
+    def seg_entries(self, reverse, order, tables):
+        """The flat entry list of mgv_seg_sum_entries for level 1 of `tables` (class_sum_levels) over the members `order` with the
+        neighbour pull over `csr(reverse)`: (entries int32, ent_seg_ptr int32 [n_seg + 1]); `order` names every node at most once (the
+        nodes sorted by colour), so the list holds at most N + E entries.  In member order, per member position m:
+        the entry order[m] (>= 0: a row of `direct`, starts a new member), then ~idx[e] for e in [ptr[order[m]], ptr[order[m] + 1])
+        (< 0: a row of `agg`, continues the member); ent_seg_ptr[s] = seg_ptr[s] + the list lengths of the members in front of it.
+        Everything the kernel would otherwise resolve per call (order -> ptr -> idx) is static per plan: built once, by the plan
+        builder's kernels (csrc/plan_build.hip mgv_seg_entries) on the device and by the torch composition below on CPU plans, and
+        cached per direction, `order` tensor and level-1 segment-pointer tensor.  The encoders of a model share the plan's quotient stages, so they share the list."""
+        cache = self.__dict__.setdefault('_seg_entries', {})
+        n_seg, seg_ptr = tables['levels'][0][0], tables['levels'][0][1]
+        key = (bool(reverse), id(order), id(seg_ptr))
+        hit = cache.get(key)
+        if hit is not None and hit[0] is order and hit[1] is seg_ptr:      # (the entry holds the tensors themselves, so their ids cannot be reused while it is cached)
+            return hit[2]
+        p, idx = self.csr(reverse)
+        n, dev = int(order.numel()), self.device
+        if self.hip:
+            from . import _hip
+            from ._hip import ptr
+            i32 = dict(dtype=torch.int32, device=dev)
+            cap = n + self.E                              # every node once and every list once
+            entries, esp = torch.empty(max(cap, 1), **i32)[:cap], torch.zeros(n_seg + 1, **i32)
+            n_s = _hip.call_value('mgv_seg_entries_scratch_ints', n)
+            scratch = torch.empty(max(n_s, 1), **i32)
+            _hip.call('mgv_seg_entries', n, ptr(order), ptr(p), ptr(idx), n_seg, ptr(seg_ptr), cap, ptr(entries), ptr(esp), ptr(scratch), n_s)
+        else:
+            o, pl = order.long(), p.long()
+            deg = pl[o + 1] - pl[o]
+            off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            off[1:] = torch.cumsum(deg + 1, 0)
+            entries = torch.empty(int(off[-1].item()), dtype=torch.int64, device=dev)
+            entries[off[:-1]] = o
+            member = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), deg)
+            k = torch.arange(int(member.numel()), dtype=torch.int64, device=dev) - (off[:-1] - torch.arange(n, dtype=torch.int64, device=dev))[member]
+            entries[off[member] + 1 + k] = ~idx.long()[pl[o][member] + k]
+            entries, esp = entries.to(torch.int32).contiguous(), off[seg_ptr.long()].to(torch.int32).contiguous()
+        cache[key] = (order, seg_ptr, (entries, esp))
+        return entries, esp
 
     def _first_stage_classes_hip(self, xcls, max_classes):
         from . import _hip

@@ -192,15 +192,30 @@ def struct_stage_bwd(h_in, nbr_ptr, nbr_idx, xcls, xtab, Wc, bc, Whh, bhh, ln_w,
     return g_direct, g_agg
 
 
-def _seg_sums(H, tables, items, direct, agg=None, nbr_ptr=None, nbr_idx=None):
+# MGV_SEG_LISTS=0 keeps the per-colour gradient sums on mgv_seg_sum (items -> nbr_ptr -> nbr_idx resolved per call) for a same-process
+# A/B; default: mgv_seg_sum_entries over flat entry lists (bit-identical sums).  Tests flip this flag.
+SEG_LISTS = os.environ.get('MGV_SEG_LISTS', '1') != '0'
+
+
+def _seg_sums(H, tables, items, direct, agg=None, nbr_ptr=None, nbr_idx=None, entries=None):
     """Per-group row sums through the segment tables of GraphPlan.class_sum_levels: level 1 reads rows `items` of `direct` (+ the
-    neighbour pull of `agg`), every further level the partial rows the one before left behind the C final rows of the same buffer."""
+    neighbour pull of `agg`), every further level the partial rows the one before left behind the C final rows of the same buffer.
+    `entries` = GraphPlan.seg_entries(...) of the same tables and lists: (flat entry list, level-1 segment pointers in entry positions),
+    what mgv_seg_sum_entries reads for a level 1 with a pull; a level without a pull needs none (its items are an entry list as they
+    stand, the upper levels read the identity list).  A level 1 with a pull and no list runs on mgv_seg_sum."""
     buf = torch.empty(tables['rows'], H, dtype=F32, device=direct.device)
     for li, (n_seg, seg_ptr, out_row, src_row) in enumerate(tables['levels']):
-        if li == 0:
-            _hip.call('mgv_seg_sum', H, n_seg, ptr(seg_ptr), ptr(items), ptr(direct), ptr(agg), ptr(nbr_ptr), ptr(nbr_idx), ptr(out_row), ptr(buf))
+        if li > 0:
+            if SEG_LISTS:
+                _hip.call('mgv_seg_sum_entries', H, n_seg, ptr(seg_ptr), None, ptr(buf[src_row:]), None, ptr(out_row), ptr(buf))
+            else:
+                _hip.call('mgv_seg_sum', H, n_seg, ptr(seg_ptr), None, ptr(buf[src_row:]), None, None, None, ptr(out_row), ptr(buf))
+        elif SEG_LISTS and agg is None:
+            _hip.call('mgv_seg_sum_entries', H, n_seg, ptr(seg_ptr), ptr(items), ptr(direct), None, ptr(out_row), ptr(buf))
+        elif SEG_LISTS and entries is not None:
+            _hip.call('mgv_seg_sum_entries', H, n_seg, ptr(entries[1]), ptr(entries[0]), ptr(direct), ptr(agg), ptr(out_row), ptr(buf))
         else:
-            _hip.call('mgv_seg_sum', H, n_seg, ptr(seg_ptr), None, ptr(buf[src_row:]), None, None, None, ptr(out_row), ptr(buf))
+            _hip.call('mgv_seg_sum', H, n_seg, ptr(seg_ptr), ptr(items), ptr(direct), ptr(agg), ptr(nbr_ptr), ptr(nbr_idx), ptr(out_row), ptr(buf))
     return buf[:tables['C']]
 
 
@@ -316,9 +331,10 @@ class StructEncoderFn(torch.autograd.Function):
                 g_direct, g_agg, h_in = gsum, None, torch.ones(r.rows, H, dtype=F32, device=dev)
             elif r.grad == 'sum_levels':
                 # the last colour stage: per-colour sums of the per-node gradient (g_direct + the pull of g_agg over this stage's
-                # lists), colour runs cut into segments, partial rows summed level by level (mgv_seg_sum: list order, no atomics)
+                # lists), colour runs cut into segments, partial rows summed level by level (_seg_sums: mgv_seg_sum_entries over the plan's flat entry list; list order, no atomics)
                 (order, levels), p, i = r.gsrc
-                g_direct, g_agg = _seg_sums(H, levels, order, g_direct, g_agg, p, i), None
+                flat = plan.seg_entries(r.rev, order, levels) if (SEG_LISTS and g_agg is not None) else None      # (once per plan, beside the stage tables)
+                g_direct, g_agg = _seg_sums(H, levels, order, g_direct, g_agg, p, i, entries=flat), None
             elif r.grad == 'above':
                 # a colour collects the own-row gradients of the representatives above that own it and the aggregate gradients
                 # of those that list it (deterministic gathers over the colour-level lists)
