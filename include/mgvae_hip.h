@@ -597,6 +597,28 @@ int mgv_func_loss_bwd_csr(int H, int64_t N, int64_t P, const float* hf, const in
 int mgv_func_loss_bwd(int H, int64_t P, const float* hf, const int64_t* pair_a, const int64_t* pair_b,
                       const float* tt, const float* dis, float eps, const double* ws, const float* gscale,
                       float* dhf, void* stream);
+/* ---- exact functional ordering accuracy (added functionality; utils/utils.py:111-147 get_function_acc on the `dis` of
+ * trainer.py:158-160; csrc/concordance.hip).  The reference draws 100 comparisons of two listed truth-table pairs per circuit; this
+ * entry counts EVERY unordered comparison {p, q}, p < q, of one segment, as integers.  gt [P] (truth-table distance) and pred [P]
+ * (predicted distance, 1 - mgv_pair_scores_at on unit rows) float32 on the device.  With dd = gt[q] - gt[p] and de = pred[q] - pred[p]
+ * in float32 a comparison is
+ *     eligible at gap j   dd != 0 && fabsf(dd) >= gaps[j]      (the reference's two `continue`s negated; >=, not >)
+ *     concordant          (dd > 0 && de > 0) || (dd < 0 && de < 0)
+ *     tied                de == 0
+ * and out[g][j] = {eligible, eligible and concordant, eligible and tied}.  A NaN in gt makes its comparisons ineligible; a NaN in
+ * pred leaves them eligible and neither concordant nor tied (the reference's `succ` stays False).  Comparisons never cross segments
+ * and p == q is never counted.  seg_ptr [G+1] int32 on the device: segment g is [seg_ptr[g], seg_ptr[g+1]); NULL is one segment of
+ * all P (G is then not looked at beyond its sign, one output row).  Whatever seg_ptr holds, a segment's range is clamped into [0, P)
+ * and no index outside it is read; a table that does not ascend makes only the counts meaningless.  gaps_host [B], 1 <= B <= 8,
+ * floats in HOST memory, copied into the kernel arguments: the entry reads nothing back and never synchronises.  out int64
+ * [max(G, 1)][B][3] is OVERWRITTEN (the launcher zeroes it).  One row of the comparison matrix per thread, column tiles of 256
+ * (gt, pred) pairs broadcast from LDS over the upper triangle, int32 counters per lane, 64-bit per workgroup, one global 64-bit
+ * integer atomic add per non-zero (segment, gap, kind) of a workgroup's first and last segment (segments wholly inside a tile, fewer
+ * than 256 pairs, add once per wave): no floating-point atomics, exact, the same bytes from call to call.
+ * Refused with MGV_EINVAL before anything is launched or zeroed: P < 0 or P > 2^31 - 1; G < 0; B outside [1, 8]; a NULL out; a NULL
+ * gt, pred or gaps_host with P > 0; a NaN or negative gap.  P = 0 zeroes out and launches nothing. */
+int mgv_concord_counts(int64_t P, const float* gt, const float* pred, const int32_t* seg_ptr, int G, const float* gaps_host, int B,
+                       int64_t* out, void* stream);
 
 /* ---- reparameterisation sampler + KL (digvae_model.py:134-142, trainer.py:146-147):
  * z = mu + exp(logstd) * eps; eps given, or NULL = drawn from the counter-based generator (seed) and

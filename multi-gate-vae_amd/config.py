@@ -39,4 +39,7 @@ def get_parse_args(argv=None):
     parser.add_argument('--save_dir', type=str, default='./exp')
     parser.add_argument('--val_auc', action='store_true', help='validation phase: also rank every batch\'s positive edges against its '
                         'sampled negatives on the device and log the mean ROC-AUC and average precision (digvae_model.py:177-189)')
+    parser.add_argument('--val_func_acc', action='store_true', help='validation phase: also count, per circuit, every comparison of two '
+                        'listed truth-table pairs at least 0.05 apart on the device and log the mean share the functional embeddings '
+                        'order correctly (utils/utils.py:111-147, exact where the reference samples 100)')
     return parser.parse_args(argv)

@@ -235,6 +235,15 @@ class FunctionalModel(nn.Module):
         A never-updated node (hf = 0) has cosine 0 with everything."""
         return ops.sim_at(hf, pair_index)
 
+    def function_accuracy(self, hf, tt_pair_index, tt_sim, graph_ptr=None, min_gap=0.05):
+        """(acc float64 [G, B], counts int64 [G, B, 3] = eligible, concordant, tied) on the device: per circuit, the share of ALL
+        comparisons of two listed truth-table pairs — those whose distances differ, and by at least min_gap (a float or up to 8 of
+        them) — that 1 - functional_similarity orders the way the truth-table distance does (ops.function_accuracy, exact integer
+        counts; G = 1 without graph_ptr).  It is what get_function_acc (utils/utils.py:111-147) estimates from 100 random draws per
+        circuit; -1 where no comparison is eligible, as there.  A tie in the prediction is not correct, as there."""
+        gaps = [min_gap] if isinstance(min_gap, (int, float)) else list(min_gap)
+        return ops.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
+
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False,
                    expect_scale=1.0):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any

@@ -2025,6 +2025,103 @@ def func_loss_passthrough(hf, tt_pair_index, tt_sim, cache=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# exact functional ordering accuracy (added functionality: every comparison of get_function_acc, utils/utils.py:111-147, counted;
+# mgv_concord_counts)
+# ------------------------------------------------------------------------------------------------
+CONCORD_TILE = 256              # csrc/concordance.hip kConcordTile: rows of a workgroup and columns of an LDS tile
+CONCORD_MAX_GAPS = 8
+MIN_GAP = 0.05                  # utils/utils.py:112
+
+
+def segment_table(first, graph_ptr, second=None):
+    """(seg_ptr int64 [G + 1], ok bool scalar) in plain torch, on the device of `first`: segment g of the listed pairs are those whose
+    first node lies in graph g, found by searchsorted — which is the pairs of graph g exactly when they come grouped by circuit in
+    circuit order and neither node leaves the circuit; `ok` says so."""
+    gp = torch.as_tensor(graph_ptr).to(device=first.device, dtype=torch.int64).contiguous()
+    G = gp.numel() - 1
+    if G < 1:
+        return torch.zeros(1, dtype=torch.int64, device=first.device), torch.as_tensor(first.numel() == 0, device=first.device)
+    gid = torch.searchsorted(gp[1:].contiguous(), first, right=True)           # the graph of each pair's first node
+    ok = ((first >= gp[0]) & (first < gp[-1])).all()
+    if first.numel() > 1:
+        ok = ok & (gid[1:] >= gid[:-1]).all()
+    if second is not None:
+        ok = ok & (torch.searchsorted(gp[1:].contiguous(), second, right=True) == gid).all() & (second >= gp[0]).all()
+    seg = torch.searchsorted(gid, torch.arange(G + 1, dtype=torch.int64, device=first.device), right=False)
+    return seg, ok
+
+
+def pair_segments(tt_pair_index, graph_ptr, cache=None):
+    """int32 seg_ptr [G + 1] on the device: the listed pairs of circuit g are [seg_ptr[g], seg_ptr[g + 1]).  The pairs must come grouped
+    by circuit in circuit order (synthetic.collate and the parser deliver them so) with both nodes of a pair in one circuit, else
+    ValueError: one small host read when the table is built, which is kept on `cache` (the batch) like pair_lists."""
+    pa, pb = _edge_rows(tt_pair_index)
+    gp = torch.as_tensor(graph_ptr)
+    key = (pa.numel(), gp.numel(), pa.device)
+    if cache is not None:
+        kept = getattr(cache, '_mgv_pair_segments', None)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+    with torch.no_grad():
+        seg, ok = segment_table(pa, gp, pb)
+        if not bool(ok):
+            raise ValueError('tt_pair_index must list its pairs grouped by circuit, in circuit order, both nodes of a pair in one circuit')
+        seg = seg.to(I32)
+    if cache is not None:
+        cache._mgv_pair_segments = (key, seg)
+    return seg
+
+
+def _concord_gaps(gaps):
+    """The gaps as the entry takes them: a ctypes float array on the host, converted to float32 ONCE; NaN or negative: ValueError."""
+    g = torch.as_tensor(gaps, dtype=torch.float64).flatten().to(F32)
+    if not 1 <= g.numel() <= CONCORD_MAX_GAPS:
+        raise ValueError('1 to %d gaps (got %d)' % (CONCORD_MAX_GAPS, g.numel()))
+    vals = g.tolist()
+    if any(not v >= 0.0 for v in vals):
+        raise ValueError('a gap must be >= 0 and not NaN (got %r)' % (vals,))
+    return (_hip.ctypes.c_float * len(vals))(*vals)
+
+
+def concord_counts(gt, pred, seg_ptr=None, gaps=(MIN_GAP,)):
+    """int64 [G, B, 3] on the device (G = 1 without seg_ptr): {eligible, concordant, tied} over EVERY unordered comparison {p, q} of one
+    segment of the listed pairs (mgv_concord_counts).  dd = gt[q] - gt[p], de = pred[q] - pred[p] in float32; eligible at gap j:
+    dd != 0 and |dd| >= gaps[j]; concordant: dd and de both > 0 or both < 0; tied: de == 0.  A NaN in gt: not eligible; a NaN in pred:
+    eligible, neither concordant nor tied.  Integer atomics: exact, the same bytes from call to call; no host read.  No grad."""
+    with torch.no_grad():
+        g = check(torch.as_tensor(gt).detach().to(F32).contiguous().flatten(), F32, 'gt')
+        p = check(torch.as_tensor(pred).detach().to(device=g.device, dtype=F32).contiguous().flatten(), F32, 'pred')
+        if p.numel() != g.numel():
+            raise HipLibraryError('gt and pred list the same pairs (got %d and %d)' % (g.numel(), p.numel()))
+        hg = _concord_gaps(gaps)
+        B = len(hg)
+        sp, G = None, 0
+        if seg_ptr is not None:
+            sp = torch.as_tensor(seg_ptr).to(device=g.device, dtype=I32).contiguous()
+            G = sp.numel() - 1
+            if G < 0:
+                raise HipLibraryError('seg_ptr needs at least one entry')
+        out = torch.empty((max(G, 1), B, 3), dtype=torch.int64, device=g.device)
+        _hip.call('mgv_concord_counts', g.numel(), ptr(g), ptr(p), ptr(sp), G, hg, B, ptr(out))
+        return out if sp is None else out[:G]
+
+
+def function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=None, gaps=(MIN_GAP,), cache=None):
+    """(acc float64 [G, B], counts int64 [G, B, 3]) on the device: per circuit and gap, concordant / eligible over ALL comparisons of two
+    listed truth-table pairs whose distances differ by at least the gap — the quantity get_function_acc (utils/utils.py:111-147)
+    estimates from 100 draws — with pred = 1 - sim_at(hf, tt_pair_index) in float32, the bits Model.functional_similarity reports and
+    the reference's expression.  acc is -1 where nothing is eligible, the reference's return value for that case.  Without graph_ptr:
+    one circuit.  No grad, no host read once the batch's segment table exists (pair_segments, kept on `cache`)."""
+    with torch.no_grad():
+        pred = 1.0 - sim_at(hf.detach(), tt_pair_index)
+        seg = None if graph_ptr is None else pair_segments(tt_pair_index, graph_ptr, cache)
+        counts = concord_counts(tt_sim.detach().to(device=pred.device), pred, seg, gaps)
+        el, co = counts[..., 0], counts[..., 1]
+        acc = torch.where(el > 0, co.double() / el.clamp(min=1).double(), torch.full_like(el, -1, dtype=torch.float64))
+        return acc, counts
+
+
+# ------------------------------------------------------------------------------------------------
 # readout: BatchNorm1d + ReLU + Dropout block, 32 -> 1 head with clamp
 # ------------------------------------------------------------------------------------------------
 class BnReluDropFn(torch.autograd.Function):

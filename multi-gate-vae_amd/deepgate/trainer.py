@@ -62,7 +62,8 @@ class GraphLoader:
 
 
 class Trainer():
-    # the phase line of the reference's log (trainer.py:259-262); --val_auc appends ' |AUC: x.xxxx |AP: x.xxxx' to the val line
+    # the phase line of the reference's log (trainer.py:259-262); --val_auc appends ' |AUC: x.xxxx |AP: x.xxxx' to the val line,
+    # --val_func_acc ' |FuncAcc: x.xxxx' behind it
     LOG_LINE = '{}| Epoch: {:}/{:} |Recon: {:.4f} |ACC: {:.2f} |Prob: {:.4f} |Func: {:.4f}|Net: {:.2f}s'
 
     def __init__(self, args, model, training_id='default', save_dir='./exp', lr=1e-4,
@@ -159,11 +160,13 @@ class Trainer():
             return True
         return False
 
-    def run_batch(self, batch, want_pred=True, want_rank=False):
+    def run_batch(self, batch, want_pred=True, want_rank=False, want_func_acc=False):
         """Forward + the three losses (trainer.py:131-174).  `general_train_test_split_edges` with zero
         val/test ratios only permutes the edges (preprocessing.py:41-50), to which the mean over edges is
         invariant: train_pos_edge_index is the batch's edge_index.  `want_rank`: also rank the loss's own pairs on the device
-        (ROC-AUC / average precision, ops.link_record); the record is returned under 'link_metrics'."""
+        (ROC-AUC / average precision, ops.link_record); the record is returned under 'link_metrics'.  `want_func_acc`: also count
+        every comparison of two listed truth-table pairs per circuit at gap 0.05 (ops.function_accuracy); the int64 [G, 3] counts
+        {eligible, concordant, tied} are returned under 'func_counts', on the device."""
         batch.train_pos_edge_index = batch.edge_index
         neg = getattr(batch, 'neg_edge_index', None)
         dev_is_cuda = next(self.model.parameters()).is_cuda
@@ -220,6 +223,9 @@ class Trainer():
         loss_status['confusion'] = self.model.last_confusion
         if want_rank:
             loss_status['link_metrics'] = self.model.last_link_metrics
+        if want_func_acc:
+            loss_status['func_counts'] = ops.function_accuracy(hf, batch['tt_pair_index'], batch['tt_sim'],
+                                                               graph_ptr=getattr(batch, 'graph_ptr', None), cache=batch)[1][:, 0]
         return loss_status
 
     def _encoder_half_rounds(self):
@@ -309,10 +315,13 @@ class Trainer():
                 stats[k].update(v)
 
         val_auc = bool(getattr(self.args, 'val_auc', False))
+        val_func_acc = bool(getattr(self.args, 'val_func_acc', False))
         for epoch in range(num_epoch):
             for phase in ['train', 'val']:
                 rank = val_auc and phase == 'val'
+                facc = val_func_acc and phase == 'val'
                 records = []             # per-batch link records of the phase, on the device until the phase ends
+                func_counts = []         # per-batch [G, 3] comparison counts of the phase, likewise
                 loader = train_loader if phase == 'train' else val_loader
                 self.model.train() if phase == 'train' else self.model.eval()
                 # collate, host-to-device copy and plan build of the next batches run on worker threads / their own HIP streams
@@ -326,9 +335,12 @@ class Trainer():
                             loss_status = self.train_step(batch)
                         else:
                             with torch.no_grad():
-                                loss_status = self.run_batch(batch, want_pred=False, **({'want_rank': True} if rank else {}))
+                                loss_status = self.run_batch(batch, want_pred=False, **({'want_rank': True} if rank else {}),
+                                                             **({'want_func_acc': True} if facc else {}))
                             if rank:
                                 records.append(loss_status['link_metrics'])
+                            if facc:
+                                func_counts.append(loss_status['func_counts'])
                         # one small device->host copy per step (3 losses + 4 counters), read one step behind so that the host
                         # never waits for the step it has just enqueued
                         account(self.enqueue_metrics(loss_status))
@@ -345,6 +357,12 @@ class Trainer():
                     pairs = ops.read_link_records(records)
                     if pairs:
                         rank_cols = ' |AUC: {:.4f} |AP: {:.4f}'.format(sum(a for a, _ in pairs) / len(pairs), sum(b for _, b in pairs) / len(pairs))
+                if facc and func_counts:
+                    # one host read for the whole phase: the mean of concordant / eligible over the circuits that have a comparison
+                    c = torch.cat(func_counts).cpu()
+                    c = c[c[:, 0] > 0].double()
+                    if c.shape[0] > 0:
+                        rank_cols += ' |FuncAcc: {:.4f}'.format(float((c[:, 1] / c[:, 0]).mean()))
                 if self.local_rank == 0:
                     line = self.LOG_LINE.format(phase, epoch, num_epoch, stats['recon'].avg, stats['acc'].avg * 100, stats['prob'].avg,
                                                 stats['func'].avg, batch_time.avg) + rank_cols + '\n'

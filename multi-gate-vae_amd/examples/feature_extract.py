@@ -13,6 +13,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --similarity_profile 12   # + pairs per graph above 1 - 2^-j, j = 1..12
     python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
     python examples/feature_extract.py --type aig --synthetic 4 --link_ranking 1,10    # + exact MRR / Hits@1 / Hits@10 of the true fan-ins
+    python examples/feature_extract.py --type aig --synthetic 4 --function_acc 0.05,0.1   # + exact functional ordering accuracy per circuit
 """
 import argparse
 import os
@@ -75,7 +76,13 @@ def main(argv=None):
                     'candidates by target — every true fan-in of a gate ranked against all gates of the circuit, the gate\'s other fan-ins '
                     'left out: links ranked, MRR, Hits@K for every K (for the best and the worst place a tie allows) and the mean rank '
                     '(Model.link_ranking; exact, no sampled negatives)')
+    ap.add_argument('--function_acc', nargs='?', const='0.05', default='', metavar='GAP,...', help='also store, per circuit, the share of '
+                    'ALL comparisons of two listed truth-table pairs whose distances differ by at least GAP (up to 8 gaps, default 0.05) '
+                    'that 1 - cos(hf) orders the way the truth-table distance does: name/func_acc [B] (-1 where no comparison is '
+                    'eligible) and name/func_counts [B, 3] = eligible, concordant, tied (Model.function_accuracy; exact counts of what '
+                    'get_function_acc samples)')
     a = ap.parse_args(argv)
+    acc_gaps = [float(g) for g in a.function_acc.split(',') if g.strip()]
     rank_ks = [int(k) for k in a.link_ranking.split(',') if k.strip()]
     sim_thr = [1.0 - 2.0 ** -j for j in range(1, min(a.similarity_profile, 20) + 1)]
     rc_thr = [float(np.float32(i / (a.recon_curve + 1.0))) for i in range(1, a.recon_curve + 1)]
@@ -123,6 +130,9 @@ def main(argv=None):
             if rank_ks:
                 rm = [x.cpu() for x in model.link_ranking(hs, batch.edge_index, batch.graph_ptr, ks=rank_ks, by='dst',
                                                           plan=getattr(batch, '_mgv_plan', None))[0]]
+            if acc_gaps:
+                f_acc, f_cnt = (x.cpu().numpy() for x in model.function_accuracy(hf, batch['tt_pair_index'], batch['tt_sim'],
+                                                                                  graph_ptr=batch.graph_ptr, min_gap=acc_gaps))
             if eq_thr is not None:
                 eq, eq_ptr, eq_cos = model.equivalence_candidates(hf, graph_ptr=batch.graph_ptr, threshold=eq_thr, with_scores=True)
                 eq, eq_cos = eq.cpu().numpy(), eq_cos.cpu().numpy()
@@ -138,6 +148,12 @@ def main(argv=None):
                     hits = ' '.join('Hits@%d %.4f..%.4f' % (K, int(rm[2][k, j]) / n, int(rm[1][k, j]) / n) for j, K in enumerate(rank_ks))
                     print('[INFO] %s: link ranking by target: %d links ranked, MRR %.6f, %s, mean rank %.2f..%.2f'
                           % (name, int(rm[0][k]), float(rm[5][k]), hits, int(rm[3][k]) / n, int(rm[4][k]) / n))
+                if acc_gaps:
+                    out[name + '/func_acc'] = f_acc[k]
+                    out[name + '/func_counts'] = f_cnt[k]
+                    print('[INFO] %s: functional ordering accuracy %s' % (name, ', '.join(
+                        '%.4f at gap %g (%d of %d comparisons, %d tied)' % (f_acc[k, j], gap, f_cnt[k, j, 1], f_cnt[k, j, 0], f_cnt[k, j, 2])
+                        for j, gap in enumerate(acc_gaps))))
                 if a.classes is not None:
                     cp = cl_ptr[cptr[k]:cptr[k + 1] + 1]
                     out[name + '/eq_label'] = (cl_label[ptr[k]:ptr[k + 1]] - ptr[k]).astype(np.int32)
