@@ -732,6 +732,9 @@ int mgv_plan_tiles(int K, int T, int L, int64_t n_active, const int32_t* key_sta
  * their gate slots (plan_build.hip k_order_rows); handed to the level sweeps as order_span with order_span_ints = 32 */
 int mgv_plan_order_rows(int64_t n_active, const int32_t* order, const int32_t* in_ptr, const int32_t* in_src, const int32_t* out_ptr,
                         const int32_t* out_dst, const int32_t* out_slot, const uint8_t* gslot, int32_t* rows, void* stream);
+/* (in-degree, feature class) pairs numbered ascending in degree * 256 + class: cid[N], cls_deg[C] / cls_x[C] (buffers of 65,536; nothing
+ * is written behind C), C = rank[65536]; present / rank: 65,537 ints each, scan_scratch: 34.  status[0] = 3 when an in-degree exceeds 255:
+ * such a node marks no pair and its cid is the number the pair (255, class) has or would have, in [0, C] — the caller falls back */
 int mgv_plan_pairs(int64_t N, const int32_t* in_ptr, const uint8_t* xcls, int32_t* present, int32_t* rank, int32_t* scan_scratch, int32_t* cid,
                    int32_t* cls_deg, uint8_t* cls_x, int32_t* status, void* stream);
 

@@ -705,7 +705,9 @@ extern "C" int mgv_plan_tile_counts(int K, const int32_t* key_start, int32_t* nt
 extern "C" int mgv_plan_tiles(int K, int T, int L, int64_t n_active, const int32_t* key_start, const int32_t* tile_first, const int32_t* order,
                               const int32_t* in_ptr, const int32_t* out_ptr, int32_t* tile_start, int32_t* tile_count, int32_t* tile_slot,
                               int32_t* order_span, int32_t* level_tile_ptr, void* stream) {
-    MGV_CHECK_ARG(K >= 1 && T >= 1 && L >= 1 && K == L * T && key_start && tile_first && level_tile_ptr);
+    MGV_CHECK_ARG(K >= 1 && T >= 1 && L >= 1 && K == L * T && n_active >= 0 && key_start && tile_first && level_tile_ptr);
+    // (no updated node, no tile: the tile arrays and the span may then be empty tensors, which have no address)
+    MGV_CHECK_ARG(n_active == 0 || (order && in_ptr && out_ptr && order_span && tile_start && tile_count && tile_slot));
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_tiles_fill, dim3((K + 255) / 256), dim3(256), 0, st, K, 1, T, key_start, tile_first, tile_start, tile_count, tile_slot);
     if (n_active > 0) hipLaunchKernelGGL(k_order_span, dim3((unsigned)((n_active + 255) / 256)), dim3(256), 0, st, n_active, order, in_ptr, out_ptr,
@@ -756,7 +758,7 @@ extern "C" int mgv_plan_order_rows(int64_t n_active, const int32_t* order, const
                                    const int32_t* out_dst, const int32_t* out_slot, const uint8_t* gslot, int32_t* rows, void* stream) {
     MGV_CHECK_ARG(n_active >= 0);
     if (n_active == 0) return MGV_OK;
-    MGV_CHECK_ARG(order && in_ptr && out_ptr && gslot && rows && (reinterpret_cast<uintptr_t>(rows) & 15) == 0);
+    MGV_CHECK_ARG(order && in_ptr && in_src && out_ptr && out_dst && out_slot && gslot && rows && (reinterpret_cast<uintptr_t>(rows) & 15) == 0);
     hipLaunchKernelGGL(k_order_rows, dim3((unsigned)((n_active * 8 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), n_active, order,
                        in_ptr, in_src, out_ptr, out_dst, out_slot, gslot, reinterpret_cast<int4*>(rows));
     MGV_LAUNCH_RET();
@@ -786,14 +788,14 @@ extern "C" int mgv_plan_pairs(int64_t N, const int32_t* in_ptr, const uint8_t* x
  * entries and were NOT compared (the caller checks those by sorting).  flags must be zeroed by the caller. */
 extern "C" int mgv_colour_keys(int64_t N, const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* prev, const int64_t* f, int64_t fstride,
                                const uint8_t* xcls, int key_bits, int64_t* key, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && nbr_ptr && prev && f && xcls && key && key_bits >= 16 && key_bits <= 63);
+    MGV_CHECK_ARG(N >= 0 && nbr_ptr && nbr_idx && prev && f && xcls && key && key_bits >= 16 && key_bits <= 63);
     if (N == 0) return MGV_OK;
     hipLaunchKernelGGL(k_colour_keys, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), N, nbr_ptr, nbr_idx, prev, f, fstride, xcls, key_bits, key);
     MGV_LAUNCH_RET();
 }
 extern "C" int mgv_colour_check(int64_t N, const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* prev, const uint8_t* xcls, const int32_t* cid,
                                 const int32_t* rep, int32_t* flags, void* stream) {
-    MGV_CHECK_ARG(N >= 0 && nbr_ptr && prev && xcls && cid && rep && flags);
+    MGV_CHECK_ARG(N >= 0 && nbr_ptr && nbr_idx && prev && xcls && cid && rep && flags);
     if (N == 0) return MGV_OK;
     hipLaunchKernelGGL(k_colour_check, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), N, nbr_ptr, nbr_idx, prev, xcls, cid, rep, flags);
     MGV_LAUNCH_RET();
@@ -831,7 +833,7 @@ extern "C" int mgv_colour_rep_rows(int64_t C, const int32_t* rep, const int32_t*
 }
 extern "C" int mgv_colour_rep_lists(int64_t C, const int32_t* rep, const int32_t* nbr_ptr, const int32_t* nbr_idx, const int32_t* prev, const int32_t* rptr,
                                     int32_t* ent, int32_t* row, void* stream) {
-    MGV_CHECK_ARG(C >= 1 && rep && nbr_ptr && prev && rptr && ent && row);
+    MGV_CHECK_ARG(C >= 1 && rep && nbr_ptr && nbr_idx && prev && rptr && ent && row);
     hipLaunchKernelGGL(k_rep_lists, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), C, rep, nbr_ptr, nbr_idx, prev, rptr, ent, row);
     MGV_LAUNCH_RET();
 }

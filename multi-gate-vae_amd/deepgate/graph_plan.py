@@ -757,8 +757,11 @@ class GraphPlan:
             from . import _hip
             from ._hip import ptr
             rows = torch.empty(max(n, 1), self.ROW_INTS, dtype=torch.int32, device=dev)[:n]
-            _hip.call('mgv_plan_order_rows', n, ptr(self.order), ptr(self.in_ptr), ptr(self.in_src), ptr(self.out_ptr), ptr(self.out_dst),
-                      ptr(self.out_slot), ptr(self.gslot), ptr(rows))
+            lists = (self.in_src, self.out_dst, self.out_slot)
+            if self.E == 0:                  # (empty tensors have no address, and the entry insists on its lists: every span is empty)
+                lists = (torch.zeros(1, dtype=torch.int32, device=dev),) * 3
+            _hip.call('mgv_plan_order_rows', n, ptr(self.order), ptr(self.in_ptr), ptr(lists[0]), ptr(self.out_ptr), ptr(lists[1]),
+                      ptr(lists[2]), ptr(self.gslot), ptr(rows))
         else:
             on = self.order.long()
             rows = torch.full((n, self.ROW_INTS), -1, dtype=torch.int32, device=dev)
