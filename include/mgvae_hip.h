@@ -577,6 +577,23 @@ int mgv_neg_sample(int64_t N, int64_t E, uint64_t seed, const int32_t* pos_out_p
 int mgv_neg_bucket(int64_t E, const int64_t* neg_src, const int64_t* neg_dst, const int32_t* out_ptr, const int32_t* in_ptr,
                    const int32_t* rank_out, const int32_t* rank_in, int64_t* srt_src, int64_t* srt_dst, int32_t* out_dst, int32_t* in_src,
                    void* stream);
+/* the same draw and the same five arrays as mgv_neg_sample + mgv_neg_bucket + mgv_sort_lists_i32 on both CSRs, integer for integer, in one
+ * entry (csrc/neg_partition.hip): the pairs are partitioned by blocks of 2^shift consecutive node ids (chunks of 16,384 slots ordered in
+ * LDS, one flat scan of the per-chunk block counts), then every block is finished by one workgroup per side: no global atomic and no
+ * scattered store per pair, no list sort of its own, nothing between its kernels.  Written, every entry once: edge_index [2][E] int64
+ * (the pairs sorted by (src, dst)), out_ptr / in_ptr [N+1], out_dst / in_src [E] (every list ascending).
+ *   shift: 0..12 with ceil(N / 2^shift) <= 2,048 blocks, else MGV_EUNSUPPORTED (the caller then takes the two-entry route); any such
+ *   shift gives the same arrays.  A block holding more than 16,384 pairs is finished in several trips over node sub-ranges, a single
+ *   list above that in its output rows: slower, never different.
+ *   ws: 8-byte aligned, ws_ints >= mgv_neg_partition_ws_ints(N, E) (-1: N < 2, N >= 2^31, E < 0 or E >= 2^28, which the entry answers
+ *   with MGV_EINVAL, like a NULL pointer or a short workspace).  ws[0..3] is a status record for tests (written asynchronously, never
+ *   read by the product): node blocks, the largest block's pairs, finishing trips summed over both sides (2 x blocks when no block
+ *   overflowed), lists finished in their output rows.
+ *   E = 0: both ptr arrays zeroed, the payload pointers may be NULL. */
+int mgv_neg_partition_ws_ints(int64_t N, int64_t E);                                                 /* a size in 4-byte units */
+int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
+                      int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws,
+                      int64_t ws_ints, void* stream);
 
 /* ---- functional-similarity loss (trainer.py:158-163, utils/utils.py:32-36): dis = 1 - cos(hf[a], hf[b]),
  * L1 between the z-normalised dis and z-normalised tt.  ws[8] doubles (zeroed by the caller):

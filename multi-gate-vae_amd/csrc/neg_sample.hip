@@ -7,33 +7,17 @@
 // that a second pass can bucket the pairs by source and by destination: the backward of the loss then gathers
 // instead of adding 2 x 256 bytes per pair with memory-side float atomics.
 #include "mgv_common.h"
+#include "mgv_neg_draw.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 __global__ __launch_bounds__(kThreads) void k_neg_sample(int64_t N, int64_t E, uint64_t seed, const int32_t* out_ptr, const int32_t* out_dst,
                                                         int64_t* neg_src, int64_t* neg_dst, int32_t* cnt_out, int32_t* cnt_in,
                                                         int32_t* rank_out, int32_t* rank_in) {
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < E; i += (int64_t)gridDim.x * kThreads) {
-        uint64_t ctr = seed ^ ((uint64_t)i * 0xD1342543DE82EF95ull);
         int s, d;
-        for (int attempt = 0;; ++attempt) {
-            const uint64_t r = splitmix64(ctr + attempt);
-            s = (int)(((r >> 32) * (uint64_t)N) >> 32);
-            d = (int)(((r & 0xFFFFFFFFull) * (uint64_t)N) >> 32);
-            bool ok = s != d;
-            if (ok)
-                for (int e = out_ptr[s]; e < out_ptr[s + 1]; ++e)
-                    if (out_dst[e] == d) { ok = false; break; }
-            if (ok || attempt >= 64) break;      // 64 straight rejections: the graph is (nearly) complete; keep the pair
-        }
+        neg_draw_slot(N, seed, i, out_ptr, out_dst, s, d);
         neg_src[i] = s; neg_dst[i] = d;
         // the pair's place inside its source's and its destination's bucket: the count it found (the bucket pass then needs no atomics)
         rank_out[i] = atomicAdd(cnt_out + s, 1);

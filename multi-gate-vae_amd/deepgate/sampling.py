@@ -8,6 +8,7 @@ HIP recon-loss kernel), or — when the batch's GraphPlan is at hand — from th
 (`negative_sampling_device`, csrc/neg_sample.hip), which also buckets the pairs by source and by destination so
 that the loss gradient needs no atomics."""
 import itertools
+import os
 
 import torch
 
@@ -15,6 +16,31 @@ from . import _hip
 from ._hip import ptr
 
 _CALLS = itertools.count()
+
+# the block-partition route of negative_sampling_device (csrc/neg_partition.hip); MGV_NEG_PARTITION=0, or PARTITION = False from a test,
+# keeps the two-entry route (mgv_neg_sample, mgv_neg_bucket, two list sorts): the same arrays either way
+PARTITION = os.environ.get('MGV_NEG_PARTITION', '1') != '0'
+PART_MAX_SHIFT = 12          # nodes per block the finishing pass scans in LDS: 4,096
+PART_MAX_BLOCKS = 2048       # blocks the partition pass ranks in LDS
+PART_TARGET = 12288          # expected pairs per block, at the most: a finishing trip holds 16,384 (Poisson: 37 sigma of margin)
+PART_MAX_E = 1 << 28
+
+
+def partition_shift(N, E):
+    """log2 of the node-block size of the partition route for E pairs over N nodes, or None where negative_sampling_device takes
+    the two-entry route: the smallest shift that keeps the block count inside PART_MAX_BLOCKS, raised while the expected pairs per
+    block (E 2^shift / N) stay inside PART_TARGET.  A pure function of (N, E): no device state, no read-back."""
+    N, E = int(N), int(E)
+    if N < 2 or N >= 1 << 31 or E < 1 or E >= PART_MAX_E:
+        return None
+    s = 0
+    while s < PART_MAX_SHIFT and (N + (1 << s) - 1) >> s > PART_MAX_BLOCKS:
+        s += 1
+    if (N + (1 << s) - 1) >> s > PART_MAX_BLOCKS:
+        return None
+    while s < PART_MAX_SHIFT and E << (s + 1) <= PART_TARGET * N:
+        s += 1
+    return s
 
 
 class NegativeEdges:
@@ -53,13 +79,24 @@ def bucket_negatives(neg, N):
 
 def negative_sampling_device(plan, num_neg_samples=None, generator=None):
     """Same distribution as `negative_sampling` (uniform over non-edges that are not self loops, with replacement),
-    drawn by one kernel from a counter-based generator seeded from torch's seed and a call counter (no host sync)."""
+    drawn by one kernel from a counter-based generator seeded from torch's seed and a call counter (no host sync).
+    Bucketed by block partition in the same entry (mgv_neg_partition) where partition_shift allows, else by the two-entry route:
+    NegativeEdges is the same function of (seed, call number, plan) on both."""
     N, dev = plan.N, plan.device
     if getattr(plan, 'num_self_loops', None) is None:
         plan.count_self_loops()              # (one host read-back per plan; GraphPlan.warm does it on the prefetcher's stream for fresh batches)
     E = (plan.E - plan.num_self_loops) + N if num_neg_samples is None else int(num_neg_samples)
     base = generator.initial_seed() if generator is not None else torch.initial_seed()
     seed = (base * 0x9E3779B97F4A7C15 + next(_CALLS) * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF
+    shift = partition_shift(N, E) if PARTITION else None
+    if shift is not None:
+        i32 = dict(dtype=torch.int32, device=dev)
+        srt = torch.empty(2, E, dtype=torch.int64, device=dev)
+        ptrs, out_dst, in_src = torch.empty(2, N + 1, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+        ws = torch.empty(_hip.call_value('mgv_neg_partition_ws_ints', N, E), **i32)
+        _hip.call('mgv_neg_partition', N, E, seed, shift, ptr(plan.out_ptr), ptr(plan.out_dst), ptr(srt), ptr(ptrs[0]), ptr(out_dst),
+                  ptr(ptrs[1]), ptr(in_src), ptr(ws), ws.numel())
+        return NegativeEdges(srt, ptrs[0], out_dst, ptrs[1], in_src)
     scratch = torch.zeros(2, N, dtype=torch.int32, device=dev)          # counts by source / destination
     neg = torch.empty(2, E, dtype=torch.int64, device=dev)
     rank = torch.empty(2, max(E, 1), dtype=torch.int32, device=dev)     # every pair's place inside its two buckets
