@@ -594,6 +594,35 @@ int mgv_neg_partition_ws_ints(int64_t N, int64_t E);                            
 int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
                       int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws,
                       int64_t ws_ints, void* stream);
+/* negative sampling inside each circuit, with a share of reversed links (opt-in; in place of dg_ae_model_aig.py:115-119, whose
+ * torch_geometric negative_sampling draws both ends over the whole batch): the candidates every evaluation entry ranks a link against lie
+ * in the link's own graph, and the hard negative of a directed link (u, v) is (v, u).  Slot i of a call is a pure function of (seed, i, N,
+ * R, graph_ptr, the positive lists) (csrc/mgv_neg_draw.h, neg_draw_slot_local):
+ *   ctr = seed ^ (i * 0xD1342543DE82EF95);  attempt a = 0 .. 64:  r = splitmix64(ctr + a),  hi = r >> 32,  lo = r & 0xFFFFFFFF
+ *     i <  R:  e = (hi * Epos) >> 32,  s = pos_in_dst[e],  d = pos_in_src[e]
+ *     i >= R:  s = (hi * N) >> 32,  g = the largest g < G with graph_ptr[g] <= s,
+ *              d = graph_ptr[g] + ((lo * (graph_ptr[g + 1] - graph_ptr[g])) >> 32)
+ *   accepted when s != d and (s, d) is not in the positive out-CSR; the pair of attempt 64 is kept whatever it is.
+ * graph_ptr [G + 1] int32: non-decreasing from 0 to N, empty graphs allowed; what the kernels read from it is clamped into [0, N], and every
+ * drawn id into [0, N): a wrong table gives wrong pairs, never an access outside the arrays.  Up to 4,096 graphs the table is held in LDS.
+ * (pos_in_src[e], pos_in_dst[e]), e < Epos: the positive edges in any order (GraphPlan.in_src / in_dst), read only when R > 0.
+ * graph_ptr = {0, N} and R = 0 give the draw of mgv_neg_sample / mgv_neg_partition, integer for integer.
+ * Refused with MGV_EINVAL, checked in this order, nothing written: G < 1; R < 0 or R > E; R > 0 with Epos < 1 or Epos >= 2^31; a NULL
+ * graph_ptr; a NULL pos_in_src or pos_in_dst with R > 0; then
+ *   mgv_neg_draw_local: N < 2, N >= 2^31, E < 0, E >= 2^28, a NULL pos_out_ptr; with E > 0 a NULL neg_src or neg_dst.  It writes the
+ *     pairs alone, slot by slot (int64 like edge_index rows): the probe of the tests, and with mgv_plan_csr the host's route where
+ *     mgv_neg_partition_local answers MGV_EUNSUPPORTED.
+ *   mgv_neg_partition_local: everything mgv_neg_partition refuses, the same way (MGV_EINVAL, then MGV_EUNSUPPORTED for the shift).  The
+ *     same five arrays, the same ws contract (mgv_neg_partition_ws_ints), status record and shift rule as mgv_neg_partition: only the
+ *     draw of its first pass differs.  Reversed slots follow the positive out-degrees: a hub's block may take several finishing trips
+ *     and its list the output-row path (slower, never different). */
+int mgv_neg_draw_local(int64_t N, int64_t E, uint64_t seed, int64_t R, int G, const int32_t* graph_ptr, const int32_t* pos_out_ptr,
+                       const int32_t* pos_out_dst, int64_t Epos, const int32_t* pos_in_src, const int32_t* pos_in_dst, int64_t* neg_src,
+                       int64_t* neg_dst, void* stream);
+int mgv_neg_partition_local(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
+                            int64_t R, int G, const int32_t* graph_ptr, int64_t Epos, const int32_t* pos_in_src, const int32_t* pos_in_dst,
+                            int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws,
+                            int64_t ws_ints, void* stream);
 
 /* ---- functional-similarity loss (trainer.py:158-163, utils/utils.py:32-36): dis = 1 - cos(hf[a], hf[b]),
  * L1 between the z-normalised dis and z-normalised tt.  ws[8] doubles (zeroed by the caller):

@@ -42,4 +42,10 @@ def get_parse_args(argv=None):
     parser.add_argument('--val_func_acc', action='store_true', help='validation phase: also count, per circuit, every comparison of two '
                         'listed truth-table pairs at least 0.05 apart on the device and log the mean share the functional embeddings '
                         'order correctly (utils/utils.py:111-147, exact where the reference samples 100)')
+    parser.add_argument('--neg_scope', type=str, default='batch', choices=['batch', 'graph'], help='negative edges of the reconstruction '
+                        'loss: batch = both ends uniform over the nodes of the batch (dg_ae_model_aig.py:115-119, the reference); graph = the '
+                        'destination uniform over the source\'s own circuit, the candidates the link-ranking tools rank against')
+    parser.add_argument('--neg_reverse', type=float, default=0.0, metavar='FRAC', help='share in [0, 1] of the negative edges that are '
+                        'reversals (v, u) of true links (u, v), the hard negatives of the directed decoder; 0 = the draw of '
+                        'dg_ae_model_aig.py:115-119')
     return parser.parse_args(argv)

@@ -12,6 +12,8 @@
 //                      placed per node in LDS, every node's entries sorted ascending, stored coalesced.  A block with more pairs
 //                      than a trip holds (kNpCap) is finished in several trips over node sub-ranges; a single node above kNpCap is
 //                      placed and sorted in its output rows directly.  No host read-back anywhere.
+// mgv_neg_partition_local is the same three passes with the local draw in pass A (negatives inside each graph, a share of reversed
+// links); mgv_neg_draw_local is that draw alone.
 #include "mgv_launch.h"
 #include "mgv_neg_draw.h"
 #include "../../include/mgvae_hip.h"
@@ -71,23 +73,77 @@ __device__ __forceinline__ void np_sort_wide(int32_t* a, int n) {
     }
 }
 
-// ---- A: draw.  hist[(side * nb + block) * nchunks + chunk]
-__global__ __launch_bounds__(kNpDrawThreads) void k_np_draw(int64_t N, int64_t E, uint64_t seed, const int32_t* pos_ptr, const int32_t* pos_dst,
-                                                            int shift, int nb, int nchunks, int32_t* ps, int32_t* pd, int32_t* hist) {
-    __shared__ int s_h[2 * kNpMaxBlocks];
-    for (int b = threadIdx.x; b < 2 * nb; b += kNpDrawThreads) s_h[b] = 0;
-    __syncthreads();
-    const int64_t c0 = (int64_t)blockIdx.x * kNpChunk;
-    const int64_t c1 = c0 + kNpChunk < E ? c0 + kNpChunk : E;
+// the draw of pass A, a compile-time policy: the batch-wide draw (neg_draw_slot: mgv_neg_partition) or the local one (neg_draw_slot_local:
+// mgv_neg_partition_local).  With s uniform over the batch and d uniform inside s's graph every node is still a destination with
+// probability 1 / N per slot, so the header's invariant holds for the local slots; reversed slots follow the positive degrees, and a
+// hub's block or list that outgrows a trip takes pass C's several trips or its output-row path.
+struct NpDrawBatch { static constexpr bool kLocal = false; };
+struct NpDrawLocal {
+    static constexpr bool kLocal = true;
+    int64_t R, Epos;
+    int G;
+    const int32_t *graph_ptr, *in_src, *in_dst;
+};
+
+// the table of a local draw copied into LDS, clamped, where it fits (uniform over the workgroup; the caller's barrier follows)
+__device__ __forceinline__ bool np_stage_graphs(const NpDrawLocal& p, int64_t N, int* s_gp) {
+    if (p.G > kNegGraphLds) return false;
+    for (int g = threadIdx.x; g <= p.G; g += blockDim.x) s_gp[g] = neg_graph_ptr(p.graph_ptr, g, (int)N);
+    return true;
+}
+
+// the slots [c0, c1) of a chunk: slot(i, s, d) draws, the pair is stored and counted per source block and per destination block
+template <class Slot>
+__device__ __forceinline__ void np_draw_chunk(int64_t c0, int64_t c1, int shift, int nb, int32_t* ps, int32_t* pd, int* s_h, Slot slot) {
     for (int64_t i = c0 + threadIdx.x; i < c1; i += kNpDrawThreads) {
         int s, d;
-        neg_draw_slot(N, seed, i, pos_ptr, pos_dst, s, d);
+        slot(i, s, d);
         ps[i] = s; pd[i] = d;
         atomicAdd(&s_h[s >> shift], 1);
         atomicAdd(&s_h[nb + (d >> shift)], 1);
     }
+}
+
+// ---- A: draw.  hist[(side * nb + block) * nchunks + chunk]
+template <class Draw>
+__global__ __launch_bounds__(kNpDrawThreads) void k_np_draw(int64_t N, int64_t E, uint64_t seed, const int32_t* pos_ptr, const int32_t* pos_dst,
+                                                            int shift, int nb, int nchunks, int32_t* ps, int32_t* pd, int32_t* hist, Draw draw) {
+    __shared__ int s_h[2 * kNpMaxBlocks];
+    for (int b = threadIdx.x; b < 2 * nb; b += kNpDrawThreads) s_h[b] = 0;
+    const int64_t c0 = (int64_t)blockIdx.x * kNpChunk;
+    const int64_t c1 = c0 + kNpChunk < E ? c0 + kNpChunk : E;
+    if constexpr (Draw::kLocal) {
+        __shared__ int s_gp[kNegGraphLds + 1];
+        const bool staged = np_stage_graphs(draw, N, s_gp);
+        __syncthreads();
+        if (staged)
+            np_draw_chunk(c0, c1, shift, nb, ps, pd, s_h, [&](int64_t i, int& s, int& d) {
+                neg_draw_slot_local(N, seed, i, pos_ptr, pos_dst, draw.R, draw.G, s_gp, draw.Epos, draw.in_src, draw.in_dst, s, d);
+            });
+        else
+            np_draw_chunk(c0, c1, shift, nb, ps, pd, s_h, [&](int64_t i, int& s, int& d) {
+                neg_draw_slot_local(N, seed, i, pos_ptr, pos_dst, draw.R, draw.G, draw.graph_ptr, draw.Epos, draw.in_src, draw.in_dst, s, d);
+            });
+    } else {
+        __syncthreads();
+        np_draw_chunk(c0, c1, shift, nb, ps, pd, s_h, [&](int64_t i, int& s, int& d) { neg_draw_slot(N, seed, i, pos_ptr, pos_dst, s, d); });
+    }
     __syncthreads();
     for (int b = threadIdx.x; b < 2 * nb; b += kNpDrawThreads) hist[(int64_t)b * nchunks + blockIdx.x] = s_h[b];
+}
+
+// ---- the local draw alone, slot by slot: the pairs as int64, in slot order (the probe of the tests; the two-entry route of the host)
+__global__ __launch_bounds__(kThreads) void k_neg_draw_local(int64_t N, int64_t E, uint64_t seed, const int32_t* pos_ptr, const int32_t* pos_dst,
+                                                            NpDrawLocal draw, int64_t* neg_src, int64_t* neg_dst) {
+    __shared__ int s_gp[kNegGraphLds + 1];
+    const bool staged = np_stage_graphs(draw, N, s_gp);
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < E; i += (int64_t)gridDim.x * kThreads) {
+        int s, d;
+        if (staged) neg_draw_slot_local(N, seed, i, pos_ptr, pos_dst, draw.R, draw.G, s_gp, draw.Epos, draw.in_src, draw.in_dst, s, d);
+        else neg_draw_slot_local(N, seed, i, pos_ptr, pos_dst, draw.R, draw.G, draw.graph_ptr, draw.Epos, draw.in_src, draw.in_dst, s, d);
+        neg_src[i] = s; neg_dst[i] = d;
+    }
 }
 
 // ---- B: partition.  base = the scan of hist (side 1 continues side 0's count: minus E)
@@ -264,9 +320,10 @@ extern "C" int mgv_neg_partition_ws_ints(int64_t N, int64_t E) {
     return (int)np_layout(E, kNpMaxBlocks).total;
 }
 
-extern "C" int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
-                                 int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws,
-                                 int64_t ws_ints, void* stream) {
+// the three passes and the scan under one draw policy: what mgv_neg_partition and mgv_neg_partition_local share, refusals included
+template <class Draw>
+static int np_run(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst, int64_t* edge_index,
+                  int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws, int64_t ws_ints, void* stream, Draw draw) {
     MGV_CHECK_ARG(N >= 2 && N < (1ll << 31) && E >= 0 && E < kNpMaxE && pos_out_ptr && out_ptr && in_ptr && ws);
     MGV_CHECK_ARG((reinterpret_cast<uintptr_t>(ws) & 7) == 0 && ws_ints >= mgv_neg_partition_ws_ints(N, E));
     MGV_CHECK_ARG(E == 0 || (edge_index && out_dst && in_src));     // (the payload arrays of an empty draw have no address)
@@ -286,8 +343,8 @@ extern "C" int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift,
     int32_t* pd = ps + E;
     int2* part0 = reinterpret_cast<int2*>(ws + w.part0);
     int2* part1 = reinterpret_cast<int2*>(ws + w.part1);
-    hipLaunchKernelGGL(k_np_draw, dim3(nchunks), dim3(kNpDrawThreads), 0, st, N, E, seed, pos_out_ptr, pos_out_dst, shift, nb, nchunks, ps, pd,
-                       ws + w.hist);
+    hipLaunchKernelGGL(k_np_draw<Draw>, dim3(nchunks), dim3(kNpDrawThreads), 0, st, N, E, seed, pos_out_ptr, pos_out_dst, shift, nb, nchunks, ps,
+                       pd, ws + w.hist, draw);
     const int rc = mgv_scan_exclusive_i32(2ll * nb * nchunks, ws + w.hist, ws + w.scan, ws + w.scratch, stream);
     if (rc != MGV_OK) return rc;
     const size_t lds_b = (size_t)(2 * kNpChunk + 2 * nb + 1 + kNpScanInts) * sizeof(int);
@@ -298,4 +355,44 @@ extern "C" int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift,
     hipLaunchKernelGGL(k_np_finish, dim3(nb, 2), dim3(kNpThreads), lds_c, st, N, E, shift, nb, nchunks, ws + w.scan, part0, part1, out_ptr, out_dst,
                        in_ptr, in_src, edge_index, edge_index + E, ws + w.status);
     MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_neg_partition(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
+                                 int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr, int32_t* in_src, int32_t* ws,
+                                 int64_t ws_ints, void* stream) {
+    return np_run(N, E, seed, shift, pos_out_ptr, pos_out_dst, edge_index, out_ptr, out_dst, in_ptr, in_src, ws, ws_ints, stream, NpDrawBatch{});
+}
+
+// what both local entries refuse before anything else, in this order
+static int np_check_local(int64_t E, int64_t R, int G, const int32_t* graph_ptr, int64_t Epos, const int32_t* pos_in_src, const int32_t* pos_in_dst) {
+    MGV_CHECK_ARG(G >= 1);
+    MGV_CHECK_ARG(R >= 0 && R <= E);
+    MGV_CHECK_ARG(R == 0 || (Epos >= 1 && Epos < (1ll << 31)));
+    MGV_CHECK_ARG(graph_ptr);
+    MGV_CHECK_ARG(R == 0 || (pos_in_src && pos_in_dst));
+    return MGV_OK;
+}
+
+extern "C" int mgv_neg_draw_local(int64_t N, int64_t E, uint64_t seed, int64_t R, int G, const int32_t* graph_ptr, const int32_t* pos_out_ptr,
+                                  const int32_t* pos_out_dst, int64_t Epos, const int32_t* pos_in_src, const int32_t* pos_in_dst,
+                                  int64_t* neg_src, int64_t* neg_dst, void* stream) {
+    const int rc = np_check_local(E, R, G, graph_ptr, Epos, pos_in_src, pos_in_dst);
+    if (rc != MGV_OK) return rc;
+    MGV_CHECK_ARG(N >= 2 && N < (1ll << 31) && E >= 0 && E < kNpMaxE && pos_out_ptr);
+    if (E == 0) return MGV_OK;              // no slots: the pair arrays of an empty draw have no address
+    MGV_CHECK_ARG(neg_src && neg_dst);
+    const NpDrawLocal draw{R, Epos, G, graph_ptr, pos_in_src, pos_in_dst};
+    hipLaunchKernelGGL(k_neg_draw_local, dim3(grid_for((E + kThreads - 1) / kThreads, 16)), dim3(kThreads), 0, static_cast<hipStream_t>(stream), N, E,
+                       seed, pos_out_ptr, pos_out_dst, draw, neg_src, neg_dst);
+    MGV_LAUNCH_RET();
+}
+
+extern "C" int mgv_neg_partition_local(int64_t N, int64_t E, uint64_t seed, int shift, const int32_t* pos_out_ptr, const int32_t* pos_out_dst,
+                                       int64_t R, int G, const int32_t* graph_ptr, int64_t Epos, const int32_t* pos_in_src,
+                                       const int32_t* pos_in_dst, int64_t* edge_index, int32_t* out_ptr, int32_t* out_dst, int32_t* in_ptr,
+                                       int32_t* in_src, int32_t* ws, int64_t ws_ints, void* stream) {
+    const int rc = np_check_local(E, R, G, graph_ptr, Epos, pos_in_src, pos_in_dst);
+    if (rc != MGV_OK) return rc;
+    return np_run(N, E, seed, shift, pos_out_ptr, pos_out_dst, edge_index, out_ptr, out_dst, in_ptr, in_src, ws, ws_ints, stream,
+                  NpDrawLocal{R, Epos, G, graph_ptr, pos_in_src, pos_in_dst});
 }

@@ -43,6 +43,7 @@ class FunctionalModel(nn.Module):
                                 act_layer='relu')
         self.last_confusion = None
         self.last_link_metrics = None
+        self._neg_scope, self._neg_reverse = 'batch', 0.0      # set_negative_sampling
 
     # ---- forward ---------------------------------------------------------------------------------
     def _sweep_params(self):
@@ -102,14 +103,32 @@ class FunctionalModel(nn.Module):
     def pred_prob(self, hf, seed=None):
         return self.readout_prob(hf, clamp01=True, seed=seed)
 
-    def _draw_negatives(self, hs, pos_edge_index, plan, edge_keys=None):
-        """Negative pairs as recon_loss draws them: with the batch's plan the fused device sampler (pairs bucketed for an atomic-free
-        backward), else the torch rejection sampler."""
-        if plan is not None and hs.is_cuda and hs.shape[0] >= 2 and DEVICE_SAMPLER:
-            return negative_sampling_device(plan)
-        return negative_sampling(pos_edge_index, hs.shape[0], keys=edge_keys)
+    def set_negative_sampling(self, scope='batch', reverse=0.0):
+        """Which negatives recon_loss and link_metrics draw.  scope='batch' (the default, the reference's draw, dg_ae_model_aig.py:115-119):
+        both ends uniform over the nodes of the batch; scope='graph': the destination uniform over the source's own circuit, the
+        candidates predict_links, reconstruct_edges and link_ranking rank a link against (recon_loss / link_metrics then need
+        graph_ptr).  reverse: the share in [0, 1] of the negatives that are reversals (v, u) of true links (u, v), the hard negatives
+        of a directed decoder.  Added functionality; a setting of the model object, not part of its state_dict."""
+        if scope not in ('batch', 'graph'):
+            raise ValueError("scope must be 'batch' or 'graph', got %r" % (scope,))
+        reverse = float(reverse)
+        if not 0.0 <= reverse <= 1.0:
+            raise ValueError('reverse must lie in [0, 1], got %r' % reverse)
+        self._neg_scope, self._neg_reverse = scope, reverse
+        return self
 
-    def link_metrics(self, hs, pos_edge_index, neg_edge_index=None, plan=None):
+    def _draw_negatives(self, hs, pos_edge_index, plan, edge_keys=None, graph_ptr=None):
+        """Negative pairs as recon_loss draws them: with the batch's plan the fused device sampler (pairs bucketed for an atomic-free
+        backward), else the torch rejection sampler; under set_negative_sampling the local draw of either."""
+        scope, reverse = getattr(self, '_neg_scope', 'batch'), getattr(self, '_neg_reverse', 0.0)
+        if scope == 'graph' and graph_ptr is None:
+            raise ValueError("set_negative_sampling(scope='graph') needs the batch's graph_ptr: pass graph_ptr= to recon_loss / link_metrics")
+        local = {} if scope == 'batch' and reverse == 0.0 else dict(graph_ptr=graph_ptr if scope == 'graph' else None, reverse=reverse)
+        if plan is not None and hs.is_cuda and hs.shape[0] >= 2 and DEVICE_SAMPLER:
+            return negative_sampling_device(plan, **local)
+        return negative_sampling(pos_edge_index, hs.shape[0], keys=edge_keys, **local)
+
+    def link_metrics(self, hs, pos_edge_index, neg_edge_index=None, plan=None, graph_ptr=None):
         """ROC-AUC and average precision of the decoder on st = hs_decompose(hs): `pos_edge_index` ranked against `neg_edge_index`
         (drawn as recon_loss draws them when None).  Added functionality: the reference's DG_AE Models have no such method, only
         DirectedGAE / DirectedGVAE.test (digvae_model.py:177-189), whose definition of the two numbers this follows.  Returns the
@@ -120,7 +139,7 @@ class FunctionalModel(nn.Module):
             if plan is not None and (plan.E != pos_edge_index.shape[1] or plan.N != hs.shape[0]):
                 plan = None
             if neg_edge_index is None:
-                neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan)
+                neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan, graph_ptr=graph_ptr)
             return ops.link_record(st, None, pos_edge_index, neg_edge_index)
 
     def _decoder_halves(self, hs):
@@ -245,12 +264,13 @@ class FunctionalModel(nn.Module):
         return ops.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
 
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False,
-                   expect_scale=1.0):
+                   expect_scale=1.0, graph_ptr=None):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the
         hs_decompose node, in `self._hs_pass` for the level sweep (see forward).  `want_rank`: also rank the very pairs the loss
         uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`.  `expect_scale`: the
-        upstream gradient this loss will meet in backward (its weight in the step's total), see ops.ReconLossFn."""
+        upstream gradient this loss will meet in backward (its weight in the step's total), see ops.ReconLossFn.  `graph_ptr`: the
+        batch's host graph table, read when negatives are drawn under set_negative_sampling(scope='graph')."""
         if pass_hs and hs.requires_grad:
             st, self._hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         else:
@@ -260,7 +280,7 @@ class FunctionalModel(nn.Module):
         neg_csr = None
         if neg_edge_index is None:
             # with the batch's plan: fused device sampler, pairs bucketed for an atomic-free backward
-            neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan, edge_keys)
+            neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan, edge_keys, graph_ptr)
         if plan is not None and hs.is_cuda and torch.is_tensor(neg_edge_index) and neg_edge_index.shape[1] > 0:
             # given negatives: bucket them once (cached on the tensor's identity) so that their gradient needs no atomics either
             # kept on the batch's plan (like its pair lists), not on the model: several batches with fixed negatives each keep theirs

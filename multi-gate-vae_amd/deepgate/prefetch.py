@@ -98,9 +98,10 @@ class BatchPrefetcher:
     depth    : batches in flight (>= workers)
     skip     : fields left out (e.g. 'neg_edge_index' when negatives are drawn on the device)
     quotient_stages : half rounds of the structural encoder (2 x rounds) whose colour classes are prepared with the plan (GraphPlan.quotient)
+    graph_table : also upload the batch's graph table as int32 on the worker's stream (the negative sampler's local draw reads it)
     """
 
-    def __init__(self, chunks, device, gate_ids=None, workers=2, depth=None, skip=(), quotient_stages=8):
+    def __init__(self, chunks, device, gate_ids=None, workers=2, depth=None, skip=(), quotient_stages=8, graph_table=False):
         self.chunks = iter(chunks)
         self.device = torch.device(device)
         self.cuda = self.device.type == 'cuda'
@@ -111,6 +112,7 @@ class BatchPrefetcher:
         self.depth = max(int(depth) if depth is not None else self.workers + 1, self.workers)
         self.keys = [k for k in _KEYS if k not in skip]
         self.quotient_stages = quotient_stages if isinstance(quotient_stages, (tuple, list, set)) else int(quotient_stages)
+        self.graph_table = bool(graph_table)
         self._free = queue.Queue()
         for _ in range(self.depth + 1):
             self._free.put(_Staging(self.cuda))
@@ -160,6 +162,9 @@ class BatchPrefetcher:
             if self.gate_ids is not None:
                 plan = plan_of(b, self.gate_ids)        # its few host read-backs wait on THIS stream only
                 plan.warm(plan.xcls, self.quotient_stages)     # ... and those of the caches the step would build lazily
+                if self.graph_table:             # the int32 graph table of the local negative draw (sampling.device_graph_ptr)
+                    from .sampling import device_graph_ptr
+                    device_graph_ptr(plan, b.graph_ptr)
                 if getattr(b, 'tt_pair_index', None) is not None and b.tt_pair_index.shape[1] >= 2:
                     from . import ops
                     b._mgv_pair_lists = ops.pair_lists(b.tt_pair_index, b.x.shape[0])

@@ -6,7 +6,11 @@ pairs that are neither an existing edge nor a self loop (pairs may cross graphs 
 distribution here, from rejection sampling on the device with torch index ops (the pairs feed the
 HIP recon-loss kernel), or — when the batch's GraphPlan is at hand — from the fused device sampler
 (`negative_sampling_device`, csrc/neg_sample.hip), which also buckets the pairs by source and by destination so
-that the loss gradient needs no atomics."""
+that the loss gradient needs no atomics.
+
+Opt-in, beside the reference's draw: `graph_ptr=` draws the destination inside the source's own graph (the candidates the evaluation
+entries rank a link against), `reverse=` makes a share of the pairs reversals (v, u) of true links (u, v), the hard negatives of a
+directed decoder (csrc/mgv_neg_draw.h: neg_draw_slot_local; csrc/neg_partition.hip: mgv_neg_partition_local, mgv_neg_draw_local)."""
 import itertools
 import os
 
@@ -77,17 +81,90 @@ def bucket_negatives(neg, N):
     return NegativeEdges(srt, out_ptr, out_dst, in_ptr, in_src)
 
 
-def negative_sampling_device(plan, num_neg_samples=None, generator=None):
+def check_graph_ptr(graph_ptr, num_nodes):
+    """The batch's graph table as a host int64 tensor [G + 1], validated on the host: at least one graph, non-decreasing (empty graphs
+    allowed), first entry 0, last entry num_nodes.  ValueError otherwise."""
+    gp = torch.as_tensor(graph_ptr).detach().to('cpu', torch.int64).reshape(-1)
+    if gp.numel() < 2:
+        raise ValueError('graph_ptr needs at least one graph (two entries), got %d entries' % gp.numel())
+    if int(gp[0]) != 0 or int(gp[-1]) != int(num_nodes):
+        raise ValueError('graph_ptr must start at 0 and end at num_nodes = %d, got %d .. %d' % (int(num_nodes), int(gp[0]), int(gp[-1])))
+    if bool((gp[1:] < gp[:-1]).any()):
+        raise ValueError('graph_ptr must be non-decreasing')
+    return gp
+
+
+def reverse_count(reverse, E):
+    """R = floor(reverse * E + 0.5) of E slots: the slots that are reversals of a true edge.  reverse lies in [0, 1]."""
+    reverse = float(reverse)
+    if not 0.0 <= reverse <= 1.0:                # (also refuses a NaN)
+        raise ValueError('reverse must lie in [0, 1], got %r' % reverse)
+    return int(reverse * int(E) + 0.5)
+
+
+def device_graph_ptr(plan, graph_ptr):
+    """(int32 device tensor [G + 1], G) of a batch's graph table for the local draw: validated (check_graph_ptr) and uploaded once, on the
+    current stream, and kept on the batch's plan for as long as the same table object comes back (BatchPrefetcher makes this call on
+    its worker's stream, with the rest of the batch).  None: the whole batch is one graph."""
+    if graph_ptr is None:
+        graph_ptr = getattr(plan, '_one_graph_ptr', None)
+        if graph_ptr is None:
+            graph_ptr = plan._one_graph_ptr = torch.tensor([0, plan.N], dtype=torch.int64)
+    hit = getattr(plan, '_graph_ptr_i32', None)
+    if hit is None or hit[0] is not graph_ptr:
+        gp = check_graph_ptr(graph_ptr, plan.N)
+        hit = plan._graph_ptr_i32 = (graph_ptr, gp.to(torch.int32).to(plan.device, non_blocking=True), int(gp.numel()) - 1)
+    return hit[1], hit[2]
+
+
+def _local_negatives(plan, E, seed, graph_ptr, R):
+    """NegativeEdges of the local draw (csrc/mgv_neg_draw.h, neg_draw_slot_local): in one entry (mgv_neg_partition_local) where
+    partition_shift allows, else the draw alone (mgv_neg_draw_local) bucketed by the plan builder's CSR kernels (bucket_negatives: one
+    host read of its status) and the two list sorts.  The same arrays either way."""
+    N, dev = plan.N, plan.device
+    gp, G = device_graph_ptr(plan, graph_ptr)
+    local = (R, G, ptr(gp), plan.E, ptr(plan.in_src), ptr(plan.in_dst))
+    i32 = dict(dtype=torch.int32, device=dev)
+    shift = partition_shift(N, E) if PARTITION else None
+    if shift is not None:
+        srt = torch.empty(2, E, dtype=torch.int64, device=dev)
+        ptrs, out_dst, in_src = torch.empty(2, N + 1, **i32), torch.empty(E, **i32), torch.empty(E, **i32)
+        ws = torch.empty(_hip.call_value('mgv_neg_partition_ws_ints', N, E), **i32)
+        _hip.call('mgv_neg_partition_local', N, E, seed, shift, ptr(plan.out_ptr), ptr(plan.out_dst), *local, ptr(srt), ptr(ptrs[0]),
+                  ptr(out_dst), ptr(ptrs[1]), ptr(in_src), ptr(ws), ws.numel())
+        return NegativeEdges(srt, ptrs[0], out_dst, ptrs[1], in_src)
+    neg = torch.empty(2, E, dtype=torch.int64, device=dev)
+    _hip.call('mgv_neg_draw_local', N, E, seed, R, G, ptr(gp), ptr(plan.out_ptr), ptr(plan.out_dst), plan.E, ptr(plan.in_src), ptr(plan.in_dst),
+              ptr(neg[0]), ptr(neg[1]))
+    if E == 0:                                   # no slots: empty buckets
+        return NegativeEdges(neg, torch.zeros(N + 1, **i32), torch.empty(1, **i32), torch.zeros(N + 1, **i32), torch.empty(1, **i32))
+    ne = bucket_negatives(neg, N)
+    ss = torch.empty(N + 1 + E, **i32)           # lists in pair order -> ascending, as the partition route leaves them
+    _hip.call('mgv_sort_lists_i32', N, E, ptr(ne.out_ptr), ptr(ne.out_dst), ptr(ss), ss.numel())
+    _hip.call('mgv_sort_lists_i32', N, E, ptr(ne.in_ptr), ptr(ne.in_src), ptr(ss), ss.numel())
+    ne.edge_index[1].copy_(ne.out_dst[:E])
+    return ne
+
+
+def negative_sampling_device(plan, num_neg_samples=None, generator=None, graph_ptr=None, reverse=0.0):
     """Same distribution as `negative_sampling` (uniform over non-edges that are not self loops, with replacement),
     drawn by one kernel from a counter-based generator seeded from torch's seed and a call counter (no host sync).
     Bucketed by block partition in the same entry (mgv_neg_partition) where partition_shift allows, else by the two-entry route:
-    NegativeEdges is the same function of (seed, call number, plan) on both."""
+    NegativeEdges is the same function of (seed, call number, plan) on both.
+
+    `graph_ptr` (the batch's host int64 table [G + 1]) and `reverse` (a share in [0, 1]) opt into the local draw: the source uniform
+    over the batch, the destination uniform over the source's own graph, and the first R = floor(reverse * E + 0.5) slots reversals
+    (v, u) of listed edges (u, v) — the candidates link_ranking and predict_links rank a link against, where the reference's draw
+    (dg_ae_model_aig.py:115-119) crosses graphs.  Same seed, same count; with neither given, today's calls and today's bits."""
     N, dev = plan.N, plan.device
     if getattr(plan, 'num_self_loops', None) is None:
         plan.count_self_loops()              # (one host read-back per plan; GraphPlan.warm does it on the prefetcher's stream for fresh batches)
     E = (plan.E - plan.num_self_loops) + N if num_neg_samples is None else int(num_neg_samples)
+    R = reverse_count(reverse, E if plan.E > 0 else 0)          # (no edge to reverse: no reversed slot)
     base = generator.initial_seed() if generator is not None else torch.initial_seed()
     seed = (base * 0x9E3779B97F4A7C15 + next(_CALLS) * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF
+    if graph_ptr is not None or reverse != 0.0:
+        return _local_negatives(plan, E, seed, graph_ptr, R)
     shift = partition_shift(N, E) if PARTITION else None
     if shift is not None:
         i32 = dict(dtype=torch.int32, device=dev)
@@ -126,19 +203,43 @@ def sorted_edge_keys(pos_edge_index, num_nodes):
     return torch.sort(src[keep] * int(num_nodes) + dst[keep]).values
 
 
-def negative_sampling(pos_edge_index, num_nodes, num_neg_samples=None, generator=None, keys=None):
+def negative_sampling(pos_edge_index, num_nodes, num_neg_samples=None, generator=None, keys=None, graph_ptr=None, reverse=0.0):
+    """The torch route (no plan, or CPU tensors).  `graph_ptr` / `reverse`: the local draw of negative_sampling_device — the same
+    distribution (source uniform over the batch, destination uniform over its graph; the first R pairs reversals of listed edges),
+    not the same bits."""
     dev = pos_edge_index.device
     N = int(num_nodes)
     if keys is None:
         keys = sorted_edge_keys(pos_edge_index, N)
     want = int(keys.numel()) + N if num_neg_samples is None else int(num_neg_samples)
+    R = reverse_count(reverse, want if pos_edge_index.shape[1] > 0 else 0)
+    gp = None
+    if graph_ptr is not None:
+        gp = check_graph_ptr(graph_ptr, N).to(dev)
+    if R > 0:
+        rev = _rejection(R, N, keys, dev, generator, edges=pos_edge_index)
+        return torch.cat([rev, _rejection(want - R, N, keys, dev, generator, gp=gp)], dim=1).contiguous()
+    return _rejection(want, N, keys, dev, generator, gp=gp)
+
+
+def _rejection(want, N, keys, dev, generator, gp=None, edges=None):
+    """`want` pairs that are neither a self pair nor an edge of `keys`, by rejection: both ends uniform over [0, N); with `gp` the
+    destination uniform over the source's graph; with `edges` the reversal of a uniformly chosen listed edge."""
     out = torch.empty((2, 0), dtype=torch.long, device=dev)
     guard = 0
     while out.shape[1] < want:
         m = want - out.shape[1]
         m = m + m // 8 + 16
-        s = torch.randint(0, N, (m,), device=dev, generator=generator)
-        d = torch.randint(0, N, (m,), device=dev, generator=generator)
+        if edges is not None:
+            e = torch.randint(0, edges.shape[1], (m,), device=dev, generator=generator)
+            s, d = edges[1].long()[e], edges[0].long()[e]
+        else:
+            s = torch.randint(0, N, (m,), device=dev, generator=generator)
+            if gp is None:
+                d = torch.randint(0, N, (m,), device=dev, generator=generator)
+            else:                            # 31 uniform bits scaled into [gp[g], gp[g + 1]) of s's graph, as the device scales 32
+                g = (torch.searchsorted(gp, s, right=True) - 1).clamp_(max=gp.numel() - 2)
+                d = gp[g] + ((torch.randint(0, 1 << 31, (m,), device=dev, generator=generator) * (gp[g + 1] - gp[g])) >> 31)
         k = s * N + d
         ok = s != d
         if keys.numel() > 0:

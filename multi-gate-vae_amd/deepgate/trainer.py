@@ -109,6 +109,12 @@ class Trainer():
             print('Training in single device: ', self.device, file=sys.stderr)
         self.reg_loss = ops.l1_loss                     # nn.L1Loss() of the reference, on the HIP kernel
         self.model = model.to(self.device)
+        # --neg_scope / --neg_reverse: which negatives the reconstruction loss draws (FunctionalModel.set_negative_sampling)
+        self.neg_scope, self.neg_reverse = getattr(args, 'neg_scope', 'batch'), float(getattr(args, 'neg_reverse', 0.0))
+        if (self.neg_scope, self.neg_reverse) != ('batch', 0.0):
+            if not hasattr(self.model, 'set_negative_sampling'):
+                raise ValueError('--neg_scope / --neg_reverse: %s draws its negatives over the whole batch only' % type(self.model).__name__)
+            self.model.set_negative_sampling(self.neg_scope, self.neg_reverse)
         self.optimizer = FlatAdam(self.model.parameters(), lr=self.lr)
         if self.world_size > 1:
             for p in self.model.parameters():           # every rank starts from rank 0's weights
@@ -174,6 +180,8 @@ class Trainer():
             self._has_after_hs = 'after_hs' in inspect.signature(self.model.forward).parameters
             # weighted_loss(...).backward() brings the reconstruction loss exactly its weight as upstream gradient
             self._has_expect_scale = 'expect_scale' in inspect.signature(self.model.recon_loss).parameters
+            # the batch's graph table, for a model that draws its negatives inside each circuit (set_negative_sampling)
+            self._has_graph_ptr = 'graph_ptr' in inspect.signature(self.model.recon_loss).parameters
         side = self._side_stream() if (self.overlap and dev_is_cuda and self._has_after_hs) else None
 
         def recon(hs, pass_hs=False):
@@ -186,7 +194,8 @@ class Trainer():
             return self.model.recon_loss(hs, batch.train_pos_edge_index, neg, want_pred=want_pred, edge_keys=k,
                                          plan=getattr(batch, '_mgv_plan', None), **({'pass_hs': True} if pass_hs else {}),
                                          **({'want_rank': True} if want_rank else {}),
-                                         **({'expect_scale': self.rc_prob_func_weight[0]} if self._has_expect_scale else {}))
+                                         **({'expect_scale': self.rc_prob_func_weight[0]} if self._has_expect_scale else {}),
+                                         **({'graph_ptr': getattr(batch, 'graph_ptr', None)} if self._has_graph_ptr else {}))
 
         def recon_on_side(hs):
             # reconstruction branch (hs_decompose -> decoder loss) on a second HIP stream, recorded BEFORE the level sweep: it
@@ -327,7 +336,8 @@ class Trainer():
                 # collate, host-to-device copy and plan build of the next batches run on worker threads / their own HIP streams
                 # beside the current step (deepgate/prefetch.py); the reference does `batch.to(device)` inside the loop (trainer.py:223)
                 batches = BatchPrefetcher(loader.chunks(), self.device, gate_ids=[g for _, g in getattr(self.model, 'GATES', [])] or None,
-                                          workers=max(self.num_workers, 2), quotient_stages=self._encoder_half_rounds())
+                                          workers=max(self.num_workers, 2), quotient_stages=self._encoder_half_rounds(),
+                                          graph_table=self.neg_scope == 'graph')
                 try:
                     for iter_id, batch in enumerate(batches):
                         time_stamp = time.time()
