@@ -50,11 +50,9 @@ class FunctionalModel(nn.Module):
         parts = [getattr(self, 'aggr_%s_func' % n).composed(getattr(self, 'update_%s_func' % n)) for n, _ in self.GATES]
         return [torch.stack([p[i] for p in parts]) for i in range(5)]
 
-    def forward(self, G, after_hs=None):
-        """`after_hs(hs)` (optional): called once hs exists and BEFORE the level sweep is recorded; its result is left in
-        `self.after_hs_out`.  Trainer.run_batch starts the reconstruction branch there: its autograd nodes are then older than
-        the sweep's, so the backward engine enqueues the sweep backward first and the branch's backward (on its own stream)
-        runs beside it instead of beside the bandwidth-bound readout backward."""
+    def forward(self, G, branch=None):
+        """`branch` (step_branch.StepBranch, optional): recon_loss runs on the branch's stream once hs exists and BEFORE the level
+        sweep's nodes are created; the sweep consumes hs as it comes back through the hs_decompose node."""
         if self.num_rounds < 1:
             raise ValueError('num_rounds must be >= 1')
         plan = plan_of(G, [gid for _, gid in self.GATES])
@@ -63,17 +61,13 @@ class FunctionalModel(nn.Module):
         enc = getattr(self, self.ENCODER_ATTR)
         s, t = enc(None, None, G.edge_index, plan=plan, classes=(rows, plan.xcls))
         hs = ops.linear(s, self.hs_linear.weight, self.hs_linear.bias, x2=t)
-        # the reconstruction branch only needs hs: Trainer.run_batch may start it on a second stream as soon
-        # as this event has fired, next to the (latency-bound, GPU-underfilling) level sweep
-        self._hs_ready = torch.cuda.Event()
-        self._hs_ready.record()
-        self._hs_pass = None
-        self.after_hs_out = after_hs(hs) if after_hs is not None else None
-        # if the reconstruction branch ran in after_hs, hs came back through its hs_decompose node (same tensor): the sweep's
-        # gradient then reaches hs inside that Linear's input-gradient kernel instead of through a separate N x H add
-        hs_in = self._hs_pass if self._hs_pass is not None else hs
-        self._hs_pass = None
+        hs_in = hs
+        if branch is not None:
+            with branch.fork(hs):
+                hs_in = branch.took(*self.recon_loss(hs, plan=plan, return_hs=True, **branch.recon_args))
         hf = ops.FuncSweepFn.apply(plan, hs_in, *self._sweep_params())
+        if branch is not None:
+            hf = branch.sweep_out(hf)
         # further rounds (dg_ae_model_aig.py:70; the reference default and train.py use 1): every gate is updated again, its GRU
         # starting from the gate's previous state, on the same level kernels (b_hh is inside gh)
         for _ in range(self.num_rounds - 1):
@@ -263,16 +257,18 @@ class FunctionalModel(nn.Module):
         gaps = [min_gap] if isinstance(min_gap, (int, float)) else list(min_gap)
         return ops.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
 
-    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, pass_hs=False, want_rank=False,
-                   expect_scale=1.0, graph_ptr=None):
+    def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, want_rank=False,
+                   expect_scale=1.0, graph_ptr=None, return_hs=False):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
-        order) — the positive half of the backward then needs no atomics.  `pass_hs`: leave hs, passed through the
-        hs_decompose node, in `self._hs_pass` for the level sweep (see forward).  `want_rank`: also rank the very pairs the loss
+        order) — the positive half of the backward then needs no atomics.  `return_hs`: a fourth result, hs passed through the
+        hs_decompose node (ops.linear_passthrough; hs itself when it needs no gradient): a second consumer of hs that reads THAT
+        tensor has its gradient added inside the Linear's input-gradient kernel.  `want_rank`: also rank the very pairs the loss
         uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`.  `expect_scale`: the
         upstream gradient this loss will meet in backward (its weight in the step's total), see ops.ReconLossFn.  `graph_ptr`: the
         batch's host graph table, read when negatives are drawn under set_negative_sampling(scope='graph')."""
-        if pass_hs and hs.requires_grad:
-            st, self._hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
+        hs_pass = hs
+        if return_hs and hs.requires_grad:
+            st, hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         else:
             st = ops.linear(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         if plan is not None and (plan.E != pos_edge_index.shape[1] or plan.N != hs.shape[0]):
@@ -300,7 +296,7 @@ class FunctionalModel(nn.Module):
         if want_pred:
             gt_bin = torch.zeros(Ep + En, dtype=torch.int32, device=hs.device)
             gt_bin[:Ep] = 1
-        return loss, pred_bin if want_pred else None, gt_bin
+        return (loss, pred_bin if want_pred else None, gt_bin) + ((hs_pass,) if return_hs else ())
 
     # ---- checkpoints (dg_ae_model_aig.py:132-160) --------------------------------------------------
     def load(self, model_path):

@@ -745,9 +745,6 @@ class AttnPoolFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 # levelised functional sweep
 # ------------------------------------------------------------------------------------------------
-_SWEEP_BWD_EVENT = None
-
-
 def _sweep_bwd_prep(plan, T, H, dev):
     """Scratch and heavy-list arguments of mgv_func_sweep_bwd_x3."""
     ltp = plan.level_tile_ptr
@@ -845,14 +842,8 @@ class FuncSweepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ghf):
-        # start signal for work that should run BESIDE the (latency-bound) sweep backward of round 1 on another stream: the
-        # reconstruction branch's backward waits for it (ReconLossFn.backward), instead of starting beside the bandwidth-bound readout backward
-        global _SWEEP_BWD_EVENT
         plan, par = ctx.plan, ctx.par
         hs, hf, hp, ghd = ctx.saved_tensors
-        if hp is None and ghf.is_cuda:
-            _SWEEP_BWD_EVENT = torch.cuda.Event()
-            _SWEEP_BWD_EVENT.record()
         N, H = hs.shape
         T = par[0].shape[0]
         dev = hs.device
@@ -1792,10 +1783,6 @@ class ReconLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gloss, _gc, _gp):
-        global _SWEEP_BWD_EVENT
-        if _SWEEP_BWD_EVENT is not None and gloss.is_cuda:
-            torch.cuda.current_stream().wait_event(_SWEEP_BWD_EVENT)
-            _SWEEP_BWD_EVENT = None
         std, ps, pd, ns, nd = ctx.saved_tensors
         H2 = std.shape[1]
         H = H2 // 2

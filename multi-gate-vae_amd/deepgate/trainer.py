@@ -5,7 +5,6 @@ Appendix B): gradients ARE averaged across ranks (one RCCL all-reduce of the fla
 step), only rank 0 writes checkpoints, step metrics come from four device-side counters instead of a
 host copy of every edge prediction, and the dead N x N negative mask of the edge split is never built.
 """
-import inspect
 import os
 import sys
 import time
@@ -18,7 +17,7 @@ from . import ops
 from .data import CircuitBatch
 from .optim import FlatAdam
 from .prefetch import BatchPrefetcher
-from .sampling import sorted_edge_keys
+from .step_branch import StepBranch
 from .synthetic import collate as collate_arrays
 from .utils.logger import Logger
 from .utils.model_utils import load_model
@@ -122,8 +121,9 @@ class Trainer():
             for b in self.model.buffers():
                 torch.distributed.broadcast(b.data, 0)
         self.model_epoch = 0
-        self.overlap = True          # second stream for the reconstruction branch
-        self._side = None
+        self.overlap = True          # run the reconstruction branch on a second stream (step_branch.StepBranch)
+        self.side_stream = None      # that stream: created at the first overlapped step; set one before it to choose it (a priority stream)
+        self._branch = None          # the current step's StepBranch, from run_batch until train_step has joined its backward
         if self.local_rank == 0:
             self.logger = Logger(self.log_path)
 
@@ -175,51 +175,21 @@ class Trainer():
         {eligible, concordant, tied} are returned under 'func_counts', on the device."""
         batch.train_pos_edge_index = batch.edge_index
         neg = getattr(batch, 'neg_edge_index', None)
-        dev_is_cuda = next(self.model.parameters()).is_cuda
-        if getattr(self, '_has_after_hs', None) is None:
-            self._has_after_hs = 'after_hs' in inspect.signature(self.model.forward).parameters
-            # weighted_loss(...).backward() brings the reconstruction loss exactly its weight as upstream gradient
-            self._has_expect_scale = 'expect_scale' in inspect.signature(self.model.recon_loss).parameters
-            # the batch's graph table, for a model that draws its negatives inside each circuit (set_negative_sampling)
-            self._has_graph_ptr = 'graph_ptr' in inspect.signature(self.model.recon_loss).parameters
-        side = self._side_stream() if (self.overlap and dev_is_cuda and self._has_after_hs) else None
-
-        def recon(hs, pass_hs=False):
-            k = None
-            if neg is None and getattr(batch, '_mgv_plan', None) is None:
-                # no plan (hence no device sampler): sorted edge keys for the torch rejection sampler, static per batch
-                k = getattr(batch, '_mgv_edge_keys', None)
-                if k is None:
-                    k = batch._mgv_edge_keys = sorted_edge_keys(batch.edge_index, batch.num_nodes)
-            return self.model.recon_loss(hs, batch.train_pos_edge_index, neg, want_pred=want_pred, edge_keys=k,
-                                         plan=getattr(batch, '_mgv_plan', None), **({'pass_hs': True} if pass_hs else {}),
-                                         **({'want_rank': True} if want_rank else {}),
-                                         **({'expect_scale': self.rc_prob_func_weight[0]} if self._has_expect_scale else {}),
-                                         **({'graph_ptr': getattr(batch, 'graph_ptr', None)} if self._has_graph_ptr else {}))
-
-        def recon_on_side(hs):
-            # reconstruction branch (hs_decompose -> decoder loss) on a second HIP stream, recorded BEFORE the level sweep: it
-            # runs beside the sweep forward — on a training step including the walk that forms the loss AND its gradient rows
-            # (ops.ReconLossFn's one-walk route) — and its backward (replayed on this stream, enqueued after the sweep backward
-            # because its nodes are older) beside the latency-bound sweep backward: there the loss's part is one early-return
-            # launch and what is left is hs_decompose's backward (on the two-kernel route the gradient walk runs there as well)
-            side.wait_event(self.model._hs_ready)
-            hs.record_stream(side)
-            with torch.cuda.stream(side):
-                return recon(hs, pass_hs=True)
-
-        if side is not None:
-            hs, hf = self.model(batch, after_hs=recon_on_side)
-            loss, pred_bin, gt_bin = self.model.after_hs_out
-            self.model.after_hs_out = None          # the model must not keep this step's loss graph alive
-            main = torch.cuda.current_stream()
-            main.wait_stream(side)
-            for t in (loss, pred_bin, gt_bin, self.model.last_confusion, self.model.last_link_metrics if want_rank else None):
-                if t is not None:
-                    t.record_stream(main)
+        # the batch's plan is Model.forward's to build and to pass (every batch has one from there on: the device sampler draws).
+        # expect_scale: weighted_loss(...).backward() brings the reconstruction loss exactly its weight as upstream gradient;
+        # graph_ptr: the batch's graph table, for a model that draws its negatives inside each circuit (set_negative_sampling)
+        recon = dict(pos_edge_index=batch.train_pos_edge_index, neg_edge_index=neg, want_pred=want_pred, want_rank=want_rank,
+                     expect_scale=self.rc_prob_func_weight[0], graph_ptr=getattr(batch, 'graph_ptr', None))
+        self._branch = None
+        if self.overlap and next(self.model.parameters()).is_cuda:
+            if self.side_stream is None:
+                self.side_stream = torch.cuda.Stream()
+            self._branch = StepBranch(self.side_stream, **recon)
+            hs, hf = self.model(batch, branch=self._branch)
+            loss, pred_bin, gt_bin = self._branch.take(self.model)
         else:
             hs, hf = self.model(batch)
-            loss, pred_bin, gt_bin = recon(hs)
+            loss, pred_bin, gt_bin = self.model.recon_loss(hs, plan=batch._mgv_plan, **recon)
         loss_status = {'recon_loss': loss, 'pred_bin': pred_bin, 'gt_bin': gt_bin}
         if 'VAE' in getattr(self.args, 'model', '') and hasattr(self.model, 'kl_loss'):
             s_kl, t_kl = self.model.kl_loss()
@@ -246,11 +216,6 @@ class Trainer():
         counts = {2 * int(getattr(h, 'num_rounds', 4)) for h in halves if h is None or hasattr(h, 'num_rounds')}
         return sorted(counts)                # --s_rounds and --t_rounds may differ: both encoders' stage counts are warmed
 
-    def _side_stream(self):
-        if getattr(self, '_side', None) is None:
-            self._side = torch.cuda.Stream()
-        return self._side
-
     def weighted_loss(self, loss_status):
         w = self.rc_prob_func_weight
         return w[0] * loss_status['recon_loss'] + w[1] * loss_status['prob_loss'] + w[2] * loss_status['func_loss']
@@ -261,8 +226,9 @@ class Trainer():
         loss_status = self.run_batch(batch, want_pred=want_pred)
         loss = self.weighted_loss(loss_status)
         loss.backward()
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)      # backward work queued on the second stream
+        branch, self._branch = self._branch, None
+        if branch is not None:
+            branch.join()            # backward work queued on the second stream
         self.optimizer.step()
         return loss_status
 
