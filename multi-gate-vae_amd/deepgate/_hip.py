@@ -20,6 +20,11 @@ _CTYPE = (('int64_t', ctypes.c_int64), ('uint64_t', ctypes.c_uint64), ('int32_t'
           ('float', ctypes.c_float), ('double', ctypes.c_double), ('int', ctypes.c_int))
 
 
+F32 = torch.float32
+I32 = torch.int32
+U8 = torch.uint8
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -160,3 +165,11 @@ def check(t, dtype=torch.float32, name='tensor'):
     if not t.is_contiguous():
         raise HipLibraryError('%s must be contiguous' % name)
     return t
+
+
+def edge_rows(edge_index):
+    """The two rows of a [2, E] index as the launchers take them: int64, each contiguous."""
+    ei = edge_index
+    if ei.dtype != torch.int64:
+        ei = ei.long()
+    return ei[0].contiguous(), ei[1].contiguous()

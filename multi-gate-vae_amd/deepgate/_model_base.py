@@ -8,7 +8,7 @@ import os
 import torch
 from torch import nn
 
-from . import ops
+from . import metrics, ops, pairs, similarity
 from .arch.mlp import MLP
 from .arch.tfmlp import TFMlpAggr
 from .data import plan_of
@@ -134,7 +134,7 @@ class FunctionalModel(nn.Module):
                 plan = None
             if neg_edge_index is None:
                 neg_edge_index = self._draw_negatives(hs, pos_edge_index, plan, graph_ptr=graph_ptr)
-            return ops.link_record(st, None, pos_edge_index, neg_edge_index)
+            return metrics.link_record(st, None, pos_edge_index, neg_edge_index)
 
     def _decoder_halves(self, hs):
         """(s, t): the two column halves of st = hs_decompose(hs), as views (the pair kernels take a row stride)."""
@@ -149,7 +149,7 @@ class FunctionalModel(nn.Module):
         matrix (digae_layer.py:31-33)."""
         with torch.no_grad():
             s, t = self._decoder_halves(hs)
-            return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
+            return pairs.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
 
     def reconstruction_counts(self, hs, edge_index, graph_ptr, threshold=0.5):
         """int64 [G, 4] per graph on the device: true positives, predicted positives over all n_g^2 ordered pairs, edges, ordered pairs
@@ -157,7 +157,7 @@ class FunctionalModel(nn.Module):
         sampled non-edges.  Precision and recall are the caller's two divisions."""
         with torch.no_grad():
             s, t = self._decoder_halves(hs)
-            return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
+            return pairs.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
     def reconstruction_curve(self, hs, edge_index, graph_ptr, thresholds):
         """int64 [G, B, 4] on the device: reconstruction_counts at every one of `thresholds` (strictly ascending, at most 256) — the
@@ -166,7 +166,7 @@ class FunctionalModel(nn.Module):
         each threshold.  Added functionality: the reference can only form the dense matrix (digae_layer.py:31-33)."""
         with torch.no_grad():
             s, t = self._decoder_halves(hs)
-            return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+            return pairs.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
     def link_ranking(self, hs, edge_index, graph_ptr, ks=(1, 3, 10, 50), by='dst', filtered=True, plan=None):
         """(RankMetrics, LinkRanks) on st = hs_decompose(hs): where every true link stands among ALL candidates of its node — by='dst',
@@ -177,8 +177,8 @@ class FunctionalModel(nn.Module):
         saturates; reconstruction_counts sees the full adjacency only in aggregate at a threshold."""
         with torch.no_grad():
             s, t = self._decoder_halves(hs)
-            ranks = ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
-            return ops.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
+            ranks = metrics.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
+            return metrics.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
 
     def reconstruct_edges(self, hs, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None) on st = hs_decompose(hs): the graph the decoder
@@ -187,8 +187,8 @@ class FunctionalModel(nn.Module):
         (ops.reconstruct_edges, streamed by ops.pair_select).  E' = reconstruction_counts(...)[:, 1].sum().  Added functionality."""
         with torch.no_grad():
             s, t = self._decoder_halves(hs)
-            return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
-                                         with_scores=with_scores, max_edges=max_edges)
+            return pairs.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
+                                           with_scores=with_scores, max_edges=max_edges)
 
     def similar_gates(self, hf, k, graph_ptr=None, threshold=0.999):
         """(idx [N, k] int32, cos [N, k], n_above [N] int32) on the functional embeddings hf: every gate's k functionally closest gates
@@ -198,7 +198,7 @@ class FunctionalModel(nn.Module):
         evaluates on the listed training pairs.  Primary inputs and other never-updated nodes have hf = 0: their cosine is 0 with
         everything, so no positive threshold ever reports them.  Bit-identical or power-of-two-scaled rows score within
         (2H + 6) 2^-24 of 1 and are not clamped to it: threshold = 1.0 selects nothing reliably, hence the default 0.999."""
-        return ops.sim_topk(hf, k, graph_ptr=graph_ptr, threshold=threshold)
+        return similarity.sim_topk(hf, k, graph_ptr=graph_ptr, threshold=threshold)
 
     def equivalence_candidates(self, hf, graph_ptr=None, threshold=0.999, with_scores=False, max_pairs=None):
         """(pair_index int64 [2, P] with pair_index[0] < pair_index[1], row_ptr int64 [N + 1], cos [P] or None): every unordered pair
@@ -208,7 +208,7 @@ class FunctionalModel(nn.Module):
         than `max_pairs` pairs raise HipLibraryError before anything is filled.  Primary inputs and other never-updated nodes have
         hf = 0 (cosine 0 with everything) and are never reported at a positive threshold; equal rows score within (2H + 6) 2^-24 of
         1, not exactly 1, so threshold = 1.0 selects nothing reliably and the default is 0.999."""
-        return ops.sim_pairs(hf, graph_ptr=graph_ptr, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
+        return similarity.sim_pairs(hf, graph_ptr=graph_ptr, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
 
     def equivalence_classes(self, hf, graph_ptr=None, threshold=0.999, min_size=2):
         """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]): the equivalence candidate CLASSES of a batch, what a SAT sweeper
@@ -221,7 +221,7 @@ class FunctionalModel(nn.Module):
         never-updated nodes have hf = 0 (cosine 0 with everything) and are always singletons at a positive threshold, as are rows with
         a NaN; classes never cross graphs; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1, so threshold = 1.0 is unreliable
         and the default is 0.999.  Exact and the same bits from run to run: equal to ops.components of equivalence_candidates."""
-        return ops.sim_classes(hf, graph_ptr=graph_ptr, threshold=threshold, min_size=min_size)
+        return similarity.sim_classes(hf, graph_ptr=graph_ptr, threshold=threshold, min_size=min_size)
 
     def similarity_profile(self, hf, thresholds, graph_ptr=None):
         """int64 [G, B] on the device: per graph, the number of unordered gate pairs whose cosine of hf is > each of `thresholds`
@@ -230,7 +230,7 @@ class FunctionalModel(nn.Module):
         1 - cosine_similarity(hf[a], hf[b], eps=1e-8) (trainer.py:158-160), by which a threshold is chosen instead of guessed.  Primary
         inputs and other never-updated nodes have hf = 0: they score 0 with everything.  Equal rows score within (2H + 6) 2^-24 of
         1, not exactly 1."""
-        return ops.counts_above(ops.sim_profile(hf, thresholds, graph_ptr=graph_ptr))
+        return pairs.counts_above(similarity.sim_profile(hf, thresholds, graph_ptr=graph_ptr))
 
     def equivalence_threshold(self, hf, max_pairs, graph_ptr=None, lo=0.0):
         """{'threshold', 'pairs', 'lower', 'pairs_lower', 'tight'}: the lowest cosine threshold above `lo` at which
@@ -240,13 +240,13 @@ class FunctionalModel(nn.Module):
         functionality (trainer.py:158-160).  Ties are the caller's to understand: equal gates share ONE cosine value, which a threshold
         takes or leaves as a whole (5,000 equal gates are 12.5 M pairs), so `pairs` can lie far below max_pairs.  Rows with hf = 0
         score 0 with everything; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1."""
-        return ops.sim_threshold_for(hf, max_pairs, graph_ptr=graph_ptr, lo=lo)
+        return similarity.sim_threshold_for(hf, max_pairs, graph_ptr=graph_ptr, lo=lo)
 
     def functional_similarity(self, hf, pair_index):
         """cos(hf[a], hf[b]) of the listed pairs [2, P]: 1 - this is the `dis` of the functional loss (trainer.py:158-160, eps = 1e-8 per
         row), in the arithmetic of similar_gates and equivalence_candidates — the same bits for the same pair.  Added functionality.
         A never-updated node (hf = 0) has cosine 0 with everything."""
-        return ops.sim_at(hf, pair_index)
+        return similarity.sim_at(hf, pair_index)
 
     def function_accuracy(self, hf, tt_pair_index, tt_sim, graph_ptr=None, min_gap=0.05):
         """(acc float64 [G, B], counts int64 [G, B, 3] = eligible, concordant, tied) on the device: per circuit, the share of ALL
@@ -255,7 +255,7 @@ class FunctionalModel(nn.Module):
         counts; G = 1 without graph_ptr).  It is what get_function_acc (utils/utils.py:111-147) estimates from 100 random draws per
         circuit; -1 where no comparison is eligible, as there.  A tie in the prediction is not correct, as there."""
         gaps = [min_gap] if isinstance(min_gap, (int, float)) else list(min_gap)
-        return ops.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
+        return metrics.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
 
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, want_rank=False,
                    expect_scale=1.0, graph_ptr=None, return_hs=False):
@@ -290,7 +290,7 @@ class FunctionalModel(nn.Module):
             neg_csr, neg_edge_index = neg_edge_index.csr, neg_edge_index.edge_index
         loss, counts, pred_bin = ops.ReconLossFn.apply(st, pos_edge_index, neg_edge_index, want_pred, plan, neg_csr, expect_scale)
         self.last_confusion = counts        # {TP, FP, TN, FN} on device, no host copy needed for metrics
-        self.last_link_metrics = ops.link_record(st, None, pos_edge_index, neg_edge_index) if want_rank else None
+        self.last_link_metrics = metrics.link_record(st, None, pos_edge_index, neg_edge_index) if want_rank else None
         Ep, En = pos_edge_index.shape[1], neg_edge_index.shape[1]
         gt_bin = None
         if want_pred:

@@ -7,7 +7,7 @@ encoder and `ops.DiGCNGatherFn` / `ops.DiGCNClassFn` around the linear kernels f
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import metrics, ops, pairs
 from .arch.gcn_conv import AggConv
 from .graph_plan import GraphPlan
 
@@ -32,28 +32,28 @@ class DirectedInnerProductDecoder(nn.Module):
 
     def forward_all(self, s, t, sigmoid=True):
         # dense M x N scores at any size that fits the device (ops.PairScoresFn, under autograd); beyond that: topk
-        return ops.pair_scores(s, t, sigmoid)
+        return pairs.pair_scores(s, t, sigmoid)
 
     def topk(self, s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False):
         """The streaming form of forward_all (added functionality: the reference has only the dense matrix): per node its k best
         links inside its own graph and the number of candidates scored above `threshold`, (idx, score, n_above) of ops.pair_topk."""
-        return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self)
+        return pairs.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self)
 
     def select(self, s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """The decoded graph itself (added functionality): per node the list of ALL links inside its own graph scored above `threshold`,
         by source or (by='dst') by target, (row_ptr, col, score or None) of ops.pair_select; no N x N array and no cap per node."""
-        return ops.pair_select(s, t, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self, by=by,
-                               with_scores=with_scores, max_edges=max_edges)
+        return pairs.pair_select(s, t, graph_ptr=graph_ptr, sigmoid=sigmoid, threshold=threshold, skip_self=skip_self, by=by,
+                                 with_scores=with_scores, max_edges=max_edges)
 
     def reconstruction_curve(self, s, t, edge_index, graph_ptr, thresholds):
         """The confusion of `select` against the full adjacency at every one of `thresholds` from one walk (added functionality):
         int64 [G, B, 4] of ops.reconstruction_curve — true positives, predicted positives, edges, ordered pairs per graph."""
-        return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+        return pairs.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
     def rank(self, s, t, edge_index, graph_ptr=None, by='src', skip_self=False, filtered=True, plan=None):
         """Where every listed link stands among ALL candidates of its node by raw score (added functionality: the reference's `test`
         ranks against sampled non-edges): LinkRanks(rank_lo, rank_hi, valid) of ops.link_ranks, in the caller's edge order."""
-        return ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, skip_self=skip_self, filtered=filtered, plan=plan)
+        return metrics.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, skip_self=skip_self, filtered=filtered, plan=plan)
 
 
 def _classes_once(x, classes, width):

@@ -3,7 +3,7 @@ decoder, the reconstruction loss and the link-prediction test on the HIP kernels
 part of the DG_AE / AE training paths and is left out."""
 import torch
 
-from . import ops
+from . import metrics, ops, pairs, similarity
 from .digae_layer import DirectedInnerProductDecoder
 from .sampling import negative_sampling
 
@@ -23,40 +23,40 @@ class DirectedGAE(torch.nn.Module):
         """(idx [N, k] int32, score [N, k], n_above [N] int32): every node's k most probable successors inside its own graph and the
         number of candidates the decoder calls an edge (score > 0.5), streamed (ops.pair_topk).  Added functionality."""
         with torch.no_grad():
-            return ops.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
+            return pairs.pair_topk(s, t, k, graph_ptr=graph_ptr, sigmoid=True, threshold=0.5, skip_self=skip_self)
 
     def reconstruction_counts(self, s, t, edge_index, graph_ptr, threshold=0.5):
         """int64 [G, 4] per graph: true positives, predicted positives over all n_g^2 ordered pairs, edges, ordered pairs
         (ops.reconstruction_counts); precision and recall against the full adjacency are the caller's two divisions."""
         with torch.no_grad():
-            return ops.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
+            return pairs.reconstruction_counts(s, t, edge_index, graph_ptr, threshold)
 
     def reconstruction_curve(self, s, t, edge_index, graph_ptr, thresholds):
         """int64 [G, B, 4]: reconstruction_counts at every one of `thresholds` (strictly ascending, at most 256) from one all-pairs
         walk (ops.reconstruction_curve).  Added functionality."""
         with torch.no_grad():
-            return ops.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
+            return pairs.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
     def link_ranking(self, s, t, edge_index, graph_ptr, ks=(1, 3, 10, 50), by='dst', filtered=True, plan=None):
         """(RankMetrics, LinkRanks): exact MRR, Hits@K and rank sums per graph over the FULL candidate set, and the per-link ranks
         behind them (ops.rank_metrics of ops.link_ranks) — by='dst': every true link among all nodes of its graph that could feed its
         target; `test` ranks against sampled non-edges only.  Added functionality."""
         with torch.no_grad():
-            ranks = ops.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
-            return ops.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
+            ranks = metrics.link_ranks(s, t, edge_index, graph_ptr=graph_ptr, by=by, filtered=filtered, plan=plan)
+            return metrics.rank_metrics(ranks, edge_index, graph_ptr, ks=ks, by=by), ranks
 
     def reconstruct_edges(self, s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
         """(edge_index int64 [2, E'], row_ptr int64 [N + 1], score [E'] or None): every pair inside a graph that the decoder calls an
         edge (score > threshold) as (source, target) rows, listed per source or (by='dst') per target (ops.reconstruct_edges).  Added
         functionality."""
         with torch.no_grad():
-            return ops.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
-                                         with_scores=with_scores, max_edges=max_edges)
+            return pairs.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
+                                           with_scores=with_scores, max_edges=max_edges)
 
     def reconstructed_components(self, edge_index, N):
         """label int32 [N]: the weakly connected components of a decoded link list (reconstruct_edges' edge_index, direction ignored) —
         label[i] is the smallest id of i's component (ops.components, a union-find on the device).  Added functionality."""
-        return ops.components(edge_index, N)
+        return similarity.components(edge_index, N)
 
     def encode(self, *args, **kwargs):
         return self.encoder(*args, **kwargs)
@@ -77,4 +77,4 @@ class DirectedGAE(torch.nn.Module):
 
     def test(self, s, t, pos_edge_index, neg_edge_index):
         """(ROC-AUC, average precision) of the decoder's scores (digae_model.py:156-168), ranked on the device (ops.link_record)."""
-        return ops.read_link_records([ops.link_record(s, t, pos_edge_index, neg_edge_index)])[0]
+        return metrics.read_link_records([metrics.link_record(s, t, pos_edge_index, neg_edge_index)])[0]

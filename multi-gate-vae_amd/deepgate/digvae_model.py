@@ -7,7 +7,7 @@ HIP kernels, with `forward` completed in the obvious way (decode the sampled emb
 graph's own edges)."""
 import torch
 
-from . import ops
+from . import metrics, ops
 from .digae_layer import DirectedInnerProductDecoder
 from .sampling import negative_sampling
 
@@ -72,4 +72,4 @@ class DirectedGVAE(torch.nn.Module):
         (digvae_model.py:177-189; nothing is sampled).  The reference copies every score to the host for sklearn; here the scores are
         ranked on the device (ops.link_record) and one 64-byte record is read.  ValueError like sklearn's when one of the two sets is
         empty or a score is NaN."""
-        return ops.read_link_records([ops.link_record(s, t, pos_edge_index, neg_edge_index)])[0]
+        return metrics.read_link_records([metrics.link_record(s, t, pos_edge_index, neg_edge_index)])[0]

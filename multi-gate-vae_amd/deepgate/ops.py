@@ -10,11 +10,8 @@ import os
 import torch
 
 from . import _hip
-from ._hip import HipLibraryError, check, ptr
+from ._hip import F32, I32, U8, HipLibraryError, check, edge_rows, ptr
 
-F32 = torch.float32
-I32 = torch.int32
-U8 = torch.uint8
 LN_EPS = 1e-5
 
 # Arithmetic of the dense products: 'x3' = bf16x3 split-precision MFMA (hi/lo bf16 planes, three
@@ -884,18 +881,11 @@ class FuncSweepFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 # decoder, reconstruction loss, confusion counters
 # ------------------------------------------------------------------------------------------------
-def _edge_rows(edge_index):
-    ei = edge_index
-    if ei.dtype != torch.int64:
-        ei = ei.long()
-    return ei[0].contiguous(), ei[1].contiguous()
-
-
 class EdgeDotFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, t, edge_index, sigmoid):
         sd, td = check(s.detach().contiguous(), F32, 's'), check(t.detach().contiguous(), F32, 't')
-        src, dst = _edge_rows(edge_index)
+        src, dst = edge_rows(edge_index)
         E, H = src.numel(), sd.shape[1]
         out = torch.empty(E, dtype=F32, device=sd.device)
         _hip.call('mgv_edge_dot_fwd', H, E, ptr(sd), ptr(td), H, ptr(src), ptr(dst), int(bool(sigmoid)), ptr(out))
@@ -916,799 +906,6 @@ class EdgeDotFn(torch.autograd.Function):
 
 def edge_dot(s, t, edge_index, sigmoid=True):
     return EdgeDotFn.apply(s, t, edge_index, sigmoid)
-
-
-def _pair_rows(x, name):
-    """(tensor, row stride) as the pair-score launchers take an operand: fp32 rows with unit column stride, a row stride that is a
-    multiple of 4 and a 16-byte aligned base — a column half of st = hs_decompose(hs) goes in as it is, anything else is copied."""
-    x = x.detach()
-    if x.dim() != 2:
-        raise HipLibraryError('%s must be a matrix [rows, H] (got shape %s)' % (name, tuple(x.shape)))
-    if not x.is_cuda:
-        raise HipLibraryError('%s must live on the GPU (got %s); the hot path has no CPU implementation' % (name, x.device))
-    if x.dtype != F32:
-        raise HipLibraryError('%s must be %s (got %s)' % (name, F32, x.dtype))
-    rows_ok = x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0
-    if x.shape[0] <= 1 or not rows_ok:
-        x = x.contiguous()
-    return x, _pair_ld(x)
-
-
-def _pair_ld(x):
-    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
-
-
-def _pair_operands(s, t):
-    sd, lds = _pair_rows(s, 's')
-    td, ldt = _pair_rows(t, 't')
-    if sd.shape[1] != td.shape[1]:
-        raise HipLibraryError('s and t must have the same width (got %d and %d)' % (sd.shape[1], td.shape[1]))
-    return sd, lds, td, ldt, sd.shape[1]
-
-
-_PAIR_WIDTHS = (16, 32, 64, 128)          # csrc/mgv_launch.h AllWidths
-
-
-def _pair_width(x, name):
-    if x.dim() == 2 and x.shape[1] not in _PAIR_WIDTHS:
-        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): the pair kernels serve H in %s, got %d'
-                              % (name, list(_PAIR_WIDTHS), x.shape[1]))
-
-
-def _pair_graphs(graph_ptr, dev):
-    """(gp int32 [G + 1] on the device, G) as the walk entries take a batch's graphs; None: (None, 0), one graph."""
-    if graph_ptr is None:
-        return None, 0
-    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=I32).contiguous()
-    if gp.numel() < 1:
-        raise HipLibraryError('graph_ptr needs at least one entry')
-    return gp, gp.numel() - 1
-
-
-def _free_bytes(dev):
-    free, _ = torch.cuda.mem_get_info(dev)
-    return free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)  # blocks the caching allocator can hand out again
-
-
-def _dense_fits(M, N, dev):
-    """A dense M x N result the device cannot hold is refused here, by name, instead of by the allocator."""
-    need = 4 * M * N
-    free = _free_bytes(dev)
-    if need > free:
-        raise HipLibraryError('dense scores of %d x %d pairs need %.1f GiB, the device has %.1f GiB free: use the streaming form, '
-                              'ops.pair_topk / DirectedInnerProductDecoder.topk (top-k links and counts per row, no N x N array)'
-                              % (M, N, need / 2.0 ** 30, free / 2.0 ** 30))
-
-
-class PairScoresFn(torch.autograd.Function):
-    """out[i, j] = sigma(<s_i, t_j>) over all pairs (digae_layer.py:31-33), exact fp32 in ascending k; the backward writes ds = G t and
-    dt = G^T s without atomics (mgv_pair_scores_bwd)."""
-
-    @staticmethod
-    def forward(ctx, s, t, sigmoid):
-        sd, lds, td, ldt, H = _pair_operands(s, t)
-        M, N = sd.shape[0], td.shape[0]
-        _dense_fits(M, N, sd.device)
-        out = torch.empty((M, N), dtype=F32, device=sd.device)
-        _hip.call('mgv_pair_scores_fwd', H, M, N, ptr(sd), lds, ptr(td), ldt, int(bool(sigmoid)), ptr(out), max(N, 1))
-        ctx.save_for_backward(sd, td, out)
-        ctx.sigmoid = bool(sigmoid)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        sd, td, out = ctx.saved_tensors
-        lds, ldt = _pair_ld(sd), _pair_ld(td)
-        M, N, H = sd.shape[0], td.shape[0], sd.shape[1]
-        gout = check(gout.contiguous(), F32, 'gout')
-        ds = torch.empty((M, H), dtype=F32, device=sd.device) if ctx.needs_input_grad[0] else None
-        dt = torch.empty((N, H), dtype=F32, device=sd.device) if ctx.needs_input_grad[1] else None
-        _hip.call('mgv_pair_scores_bwd', H, M, N, ptr(sd), lds, ptr(td), ldt, int(ctx.sigmoid), ptr(out), max(N, 1), ptr(gout), max(N, 1),
-                  ptr(ds), H, ptr(dt), H)
-        return ds, dt, None
-
-
-def pair_scores(s, t, sigmoid=True):
-    """Decoder scores of all M x N pairs at any size, under autograd."""
-    return PairScoresFn.apply(s, t, sigmoid)
-
-
-def pair_scores_at(s, t, edge_index, sigmoid=True):
-    """Scores of the listed pairs in the arithmetic of pair_scores: equal to pair_scores(s, t)[src, dst] bit for bit (no grad; the
-    training path's per-edge decoder is edge_dot)."""
-    sd, lds, td, ldt, H = _pair_operands(s, t)
-    src, dst = _edge_rows(edge_index)
-    E = src.numel()
-    out = torch.empty(E, dtype=F32, device=sd.device)
-    _hip.call('mgv_pair_scores_at', H, E, ptr(sd), lds, ptr(td), ldt, ptr(src), ptr(dst), int(bool(sigmoid)), ptr(out))
-    return out
-
-
-def pair_topk(s, t, k, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False):
-    """(idx [N, k] int32, score [N, k], n_above [N] int32) per row u over the nodes of u's own graph (graph_ptr [G + 1], None: one graph):
-    the k best links by raw dot product (ties: lower id first; -1 / -inf past the end) and the number of candidates whose score is
-    > threshold.  Streaming: no N x N array.  No grad; nothing is read back except the two ends of a graph_ptr, which the launcher
-    checks (None: no host synchronisation at all)."""
-    sd, lds, td, ldt, H = _pair_operands(s, t)
-    N = sd.shape[0]
-    if td.shape[0] != N:
-        raise HipLibraryError('pair_topk ranks the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
-    k = int(k)
-    dev = sd.device
-    gp, G = _pair_graphs(graph_ptr, dev)
-    kk = min(max(k, 1), 32)
-    idx = torch.empty((N, kk), dtype=I32, device=dev)
-    score = torch.empty((N, kk), dtype=F32, device=dev)
-    n_above = torch.empty(N, dtype=I32, device=dev)
-    _hip.call('mgv_pair_topk', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, k, int(bool(sigmoid)), float(threshold), int(bool(skip_self)),
-              ptr(idx), ptr(score), ptr(n_above))
-    return idx, score, n_above
-
-
-def _list_room(name, total, free, *, noun, listed, limit_name, limit, item_bytes, hint):
-    """The two refusals between a selection's count and its fill (nothing is allocated before them): more than the caller's
-    `limit_name` allows, or a result — `listed` in words — of item_bytes per `noun` the device cannot hold; by name, like _dense_fits."""
-    if limit is not None and total > int(limit):
-        raise HipLibraryError('%s: %d %s are above the threshold, %s allows %d: %s' % (name, total, noun, limit_name, int(limit), hint))
-    need = item_bytes * total
-    if free is not None and need > free:
-        raise HipLibraryError('%s: %s above the threshold need %.1f GiB, the device has %.1f GiB free: %s'
-                              % (name, listed % total, need / 2.0 ** 30, free / 2.0 ** 30, hint))
-
-
-def _select_room(total, with_scores, max_edges, free):
-    """pair_select's refusals: lists of int32 ids, float32 scores beside them when asked for."""
-    _list_room('pair_select', total, free, noun='links', listed='the lists of %d links', limit_name='max_edges', limit=max_edges,
-               item_bytes=8 if with_scores else 4,
-               hint='raise the threshold, or take the k best links per node with ops.pair_topk / DirectedInnerProductDecoder.topk')
-
-
-def _count_scan_fill(count_entry, fill_entry, N, common, dev, with_scores, room):
-    """(row_ptr int64 [N + 1], col int32 [total], score float32 [total] or None) of a selection walk over N rows with the arguments
-    `common` of both entries: count, exclusive scan on the device, ONE read-back of the total (the result must be allocated), room(total, free
-    bytes) — which refuses by raising —, allocate, fill."""
-    n_sel = torch.empty(N, dtype=I32, device=dev)
-    _hip.call(count_entry, *common, ptr(n_sel))
-    row_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(n_sel, 0, dtype=torch.int64, out=row_ptr[1:])
-    total = int(row_ptr[-1])                                      # the read-back
-    room(total, _free_bytes(dev))
-    col = torch.empty(total, dtype=I32, device=dev)
-    score = torch.empty(total, dtype=F32, device=dev) if with_scores else None
-    _hip.call(fill_entry, *common, ptr(row_ptr), total, ptr(col), ptr(score))
-    return row_ptr, col, score
-
-
-def pair_select(s, t, graph_ptr=None, sigmoid=True, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
-    """(row_ptr int64 [N + 1], col int32 [E'], score float32 [E'] or None): the reconstructed graph as per-node lists — for every row u
-    the nodes v of u's own graph (graph_ptr [G + 1], None: one graph; without v = u when skip_self) whose score is > threshold, as
-    batch-wide ids in ascending order at col[row_ptr[u] : row_ptr[u + 1]].  The decision is the one behind pair_topk's n_above, on the
-    dense entry's bits.  by='src': row u lists its targets v (<s_u, t_v>); by='dst': the operands change places and row v lists its
-    sources u, the in-neighbour lists — every product commutes and k keeps its order, so the scores are the dense entries, transposed.
-    Count, exclusive scan on the device, ONE read-back of the total (the result must be allocated; the only synchronisation besides the
-    two ends of a graph_ptr), fill; no atomics, the same bytes from call to call, nothing of size N^2.  A total above `max_edges` or
-    beyond the free memory raises HipLibraryError before the fill.  No grad."""
-    if by not in ('src', 'dst'):
-        raise HipLibraryError("pair_select: by must be 'src' (row u lists its targets) or 'dst' (row v lists its sources), got %r" % (by,))
-    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
-        _pair_width(s, 'pair_select')
-    if by == 'dst':
-        s, t = t, s
-    sd, lds, td, ldt, H = _pair_operands(s, t)
-    N = sd.shape[0]
-    if td.shape[0] != N:
-        raise HipLibraryError('pair_select lists the nodes of one batch: s and t need the same number of rows (got %d and %d)' % (N, td.shape[0]))
-    gp, G = _pair_graphs(graph_ptr, sd.device)
-    common = (H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), float(threshold), int(bool(skip_self)))
-    return _count_scan_fill('mgv_pair_select_count', 'mgv_pair_select_fill', N, common, sd.device, with_scores,
-                            lambda total, free: _select_room(total, with_scores, max_edges, free))
-
-
-def reconstruct_edges(s, t, graph_ptr=None, threshold=0.5, skip_self=False, by='src', with_scores=False, max_edges=None):
-    """(edge_index int64 [2, E'], row_ptr, score or None): pair_select's lists (sigmoid scores) as (source, target) rows in list order,
-    whichever side they are listed by.  E' is reconstruction_counts(...)[:, 1].sum() by construction (skip_self off)."""
-    row_ptr, col, score = pair_select(s, t, graph_ptr=graph_ptr, sigmoid=True, threshold=threshold, skip_self=skip_self, by=by,
-                                      with_scores=with_scores, max_edges=max_edges)
-    N = row_ptr.numel() - 1
-    rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=col.device), row_ptr[1:] - row_ptr[:-1],
-                                   output_size=col.numel())
-    col = col.to(torch.int64)
-    return torch.stack([rows, col] if by == 'src' else [col, rows]), row_ptr, score
-
-
-def reconstruction_counts(s, t, edge_index, graph_ptr, threshold=0.5):
-    """int64 [G, 4] on the device, per graph of the batch: {true positives, predicted positives over all n_g^2 ordered pairs, edges,
-    ordered pairs} of the decoder at `threshold` against the FULL adjacency (the sampled counters of ReconLossFn see E + N non-edges
-    of N^2 - E).  The true positives are pair_scores_at over the edges and the predicted positives the n_above of pair_topk: the same
-    bits on both sides of the same `>`.  Integer sums throughout; precision = [:, 0] / [:, 1] and recall = [:, 0] / [:, 2] are the
-    caller's divisions.  An edge counts for the graph of its source."""
-    dev = s.device
-    gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64)
-    G = gp.numel() - 1
-    src, dst = _edge_rows(edge_index)
-    _, _, n_above = pair_topk(s, t, 1, graph_ptr=gp, sigmoid=True, threshold=threshold, skip_self=False)
-    if G <= 0:
-        return torch.zeros((0, 4), dtype=torch.int64, device=dev)
-    hit = (pair_scores_at(s, t, edge_index, sigmoid=True) > threshold).to(torch.int64)
-    gid = torch.bucketize(src, gp[1:].contiguous(), right=True).clamp_(max=G - 1)
-    tp = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, hit)                     # integer adds: exact in any order
-    edges = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, torch.ones_like(hit))
-    cs = torch.zeros(s.shape[0] + 1, dtype=torch.int64, device=dev)
-    cs[1:] = torch.cumsum(n_above.to(torch.int64), 0)
-    n = gp[1:] - gp[:-1]
-    return torch.stack([tp, cs[gp[1:]] - cs[gp[:-1]], edges, n * n], dim=1)
-
-
-def dense_scores(s, t):
-    """s t^T for `forward_all` at any size (raw dot products)."""
-    return pair_scores(s, t, sigmoid=False)
-
-
-# ------------------------------------------------------------------------------------------------
-# functional-similarity search on hf (added functionality: the inference side of the functional loss, trainer.py:158-160)
-# ------------------------------------------------------------------------------------------------
-# Two facts for every function below.  Primary inputs and other never-updated nodes have hf = 0: their cosine is 0 with everything, so no
-# positive threshold ever reports them.  Bit-identical or exactly power-of-two-scaled rows score within (2H + 6) 2^-24 of 1 and are not
-# clamped to it: threshold = 1.0 selects nothing reliably, hence the default 0.999.
-SIM_THRESHOLD = 0.999
-
-
-def row_unit(x, eps=1e-8, want_norm=False):
-    """y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity and of the functional loss (trainer.py:158-160,
-    mgv_func_loss_fwd); with want_norm also |x[i]| unclamped: (y, norm).  A zero row stays a zero row, a row with a NaN becomes NaN.
-    The sum of squares is float32 without rescaling (hf is a GRU output in (-1, 1)).  No grad."""
-    _pair_width(x, 'row_unit')
-    with torch.no_grad():
-        xd, ldx = _pair_rows(x, 'x')
-        N, H = xd.shape
-        y = torch.empty((N, H), dtype=F32, device=xd.device)
-        norm = torch.empty(N, dtype=F32, device=xd.device) if want_norm else None
-        _hip.call('mgv_row_unit', H, N, ptr(xd), ldx, float(eps), ptr(y), H, ptr(norm))
-    return (y, norm) if want_norm else y
-
-
-def sim_topk(x, k, graph_ptr=None, threshold=SIM_THRESHOLD, eps=1e-8):
-    """(idx [N, k] int32, cos [N, k], n_above [N] int32): per row u the k nodes v != u of u's own graph with the largest cosine
-    (ties: lower id first; -1 / -inf past the end), and the number of ALL candidates v != u whose cosine is > threshold (so n_above
-    is symmetric).  A row needs all its candidates, so this is pair_topk on the unit rows; a cosine is the same bits as in sim_pairs
-    and sim_at.  Zero rows (primary inputs) score 0 with everything; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1."""
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        return pair_topk(y, y, k, graph_ptr=graph_ptr, sigmoid=False, threshold=threshold, skip_self=True)
-
-
-def _sim_room(total, with_scores, max_pairs, free):
-    """sim_pairs' refusals: int64 pair_index, the int32 list it is made from, float32 scores when asked for."""
-    _list_room('sim_pairs', total, free, noun='pairs', listed='%d pairs', limit_name='max_pairs', limit=max_pairs,
-               item_bytes=24 if with_scores else 20,
-               hint='raise the threshold, or take the k most similar gates per node with ops.sim_topk / similar_gates')
-
-
-def sim_pairs(x, graph_ptr=None, threshold=SIM_THRESHOLD, with_scores=False, max_pairs=None, eps=1e-8):
-    """(pair_index int64 [2, P] with pair_index[0] < pair_index[1], row_ptr int64 [N + 1], score [P] or None): every unordered pair of
-    nodes of one graph whose cosine is > threshold, once, ordered by the smaller id and then the larger — the candidates for SAT
-    sweeping and equivalence checking.  Unit rows, then the symmetric selection (mgv_sim_select_*: half the tiles of pair_select on
-    the same rows): count, exclusive int64 scan, ONE read-back of the total, fill; nothing of size N^2, no atomics.  A total above
-    `max_pairs` or beyond the free memory raises HipLibraryError before anything is allocated or filled.  Zero rows (primary inputs)
-    pair with nothing at a positive threshold; threshold = 1.0 selects nothing reliably (equal rows score within (2H + 6) 2^-24 of 1)."""
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        N, H = y.shape
-        dev = y.device
-        gp, G = _pair_graphs(graph_ptr, dev)
-        common = (H, N, ptr(y), H, ptr(gp), G, float(threshold))
-        row_ptr, col, score = _count_scan_fill('mgv_sim_select_count', 'mgv_sim_select_fill', N, common, dev, with_scores,
-                                               lambda total, free: _sim_room(total, with_scores, max_pairs, free))
-        rows = torch.repeat_interleave(torch.arange(N, dtype=torch.int64, device=dev), row_ptr[1:] - row_ptr[:-1],
-                                       output_size=col.numel())
-        return torch.stack([rows, col.to(torch.int64)]), row_ptr, score
-
-
-def sim_at(x, pair_index, eps=1e-8):
-    """cos(x[a], x[b]) of the listed pairs [2, P], the cosine of the functional loss (1 - sim_at is its `dis`, trainer.py:158-160) in
-    the arithmetic of sim_topk and sim_pairs: the same bits for the same pair."""
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        return pair_scores_at(y, y, pair_index, sigmoid=False)
-
-
-# ------------------------------------------------------------------------------------------------
-# the distribution of all-pair scores (added functionality: thresholds chosen by count; mgv_pair_hist / mgv_sim_hist)
-# ------------------------------------------------------------------------------------------------
-# The two facts above hold here too: zero rows score 0 with everything, equal rows score within (2H + 6) 2^-24 of 1.
-PROFILE_MAX_EDGES = 256
-
-
-def _profile_edges(edges, dev):
-    """The table as the launchers take it: float32 [B] on the device, converted ONCE — every count refers to these float32 values."""
-    e = torch.as_tensor(edges).detach().to(device=dev, dtype=F32).contiguous().flatten()
-    if not 1 <= e.numel() <= PROFILE_MAX_EDGES:
-        raise HipLibraryError('a profile takes 1 to %d edges (got %d)' % (PROFILE_MAX_EDGES, e.numel()))
-    return e
-
-
-def pair_profile(s, t, edges, graph_ptr=None, sigmoid=True, skip_self=False):
-    """int64 [G, B + 1] on the device (G = 1 without graph_ptr): per graph, the candidates of pair_select — v in u's graph, without v = u
-    when skip_self, sigmoid or raw score — binned by the number of `edges` (float32, strictly ascending, 1 <= B <= 256) their score is
-    > than: bin 0 holds score <= edges[0], bin B score > edges[-1]; a NaN score is in no bin.  ONE all-pairs walk for the whole table
-    (mgv_pair_hist), the decisions the bits of pair_select's: counts_above(profile)[g, j] is the number of links pair_select would
-    list for graph g at threshold edges[j].  Integer atomics: exact and the same from call to call.  No grad."""
-    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
-        _pair_width(s, 'pair_profile')
-    with torch.no_grad():
-        sd, lds, td, ldt, H = _pair_operands(s, t)
-        N = sd.shape[0]
-        if td.shape[0] != N:
-            raise HipLibraryError('pair_profile bins the pairs of one batch: s and t need the same number of rows (got %d and %d)'
-                                  % (N, td.shape[0]))
-        dev = sd.device
-        e = _profile_edges(edges, dev)
-        gp, G = _pair_graphs(graph_ptr, dev)
-        hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=dev)
-        _hip.call('mgv_pair_hist', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(sigmoid)), int(bool(skip_self)), ptr(e), e.numel(),
-                  ptr(hist))
-        return hist if gp is None else hist[:G]
-
-
-def _unit_profile(y, e, graph_ptr):
-    """mgv_sim_hist on unit rows y and a device table e -> int64 [G, B + 1]."""
-    N, H = y.shape
-    gp, G = _pair_graphs(graph_ptr, y.device)
-    hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=y.device)
-    _hip.call('mgv_sim_hist', H, N, ptr(y), H, ptr(gp), G, ptr(e), e.numel(), ptr(hist))
-    return hist if gp is None else hist[:G]
-
-
-def sim_profile(x, edges, graph_ptr=None, eps=1e-8):
-    """int64 [G, B + 1]: pair_profile's bins for the cosine of sim_pairs — unit rows (row_unit), every unordered pair of one graph once
-    (v > u), half the tiles (mgv_sim_hist).  counts_above(profile)[g, j] is the number of pairs sim_pairs lists for graph g at
-    threshold edges[j], as integers.  Zero rows (primary inputs) score 0 with everything; equal rows score within (2H + 6) 2^-24 of
-    1, not exactly 1."""
-    _pair_width(x, 'sim_profile')
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        return _unit_profile(y, _profile_edges(edges, y.device), graph_ptr)
-
-
-def counts_above(profile):
-    """int64 [G, B]: pairs above each edge — the reverse cumulative sum of a profile without its bin 0."""
-    with torch.no_grad():
-        return profile[:, 1:].flip(1).cumsum(1).flip(1)
-
-
-def reconstruction_curve(s, t, edge_index, graph_ptr, thresholds):
-    """int64 [G, B, 4] on the device: reconstruction_counts at every threshold of `thresholds` (strictly ascending), entry for entry
-    equal to torch.stack([reconstruction_counts(s, t, edge_index, graph_ptr, thr) for thr in thresholds], 1), from ONE all-pairs walk:
-    the predicted positives are counts_above of pair_profile, the true positives pair_scores_at over the edges, binned by the same
-    float32 table (bucketize: the number of thresholds the score is > than) and added per source graph.  Integer sums throughout."""
-    with torch.no_grad():
-        dev = s.device
-        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64)
-        G = gp.numel() - 1
-        e = _profile_edges(thresholds, dev)
-        B = e.numel()
-        src, dst = _edge_rows(edge_index)
-        pp = counts_above(pair_profile(s, t, e, graph_ptr=gp, sigmoid=True, skip_self=False))
-        if G <= 0:
-            return torch.zeros((0, B, 4), dtype=torch.int64, device=dev)
-        rep = pair_scores_at(s, t, edge_index, sigmoid=True)
-        k = torch.bucketize(rep, e, right=False)                       # #{j : rep > e[j]}
-        ok = ~torch.isnan(rep)                                         # a NaN passes no threshold (bucketize would put it behind all)
-        gid = torch.bucketize(src, gp[1:].contiguous(), right=True).clamp_(max=G - 1)
-        tbin = torch.zeros(G * (B + 1), dtype=torch.int64, device=dev).index_add_(0, gid * (B + 1) + k, ok.to(torch.int64))
-        tp = counts_above(tbin.view(G, B + 1))
-        edges = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, torch.ones_like(gid))
-        n = gp[1:] - gp[:-1]
-        return torch.stack([tp, pp, edges[:, None].expand(G, B), (n * n)[:, None].expand(G, B)], dim=2)
-
-
-# ------------------------------------------------------------------------------------------------
-# the rank of every true link among all candidates of its node (added functionality: exact MRR / Hits@K; mgv_pair_rank_counts)
-# ------------------------------------------------------------------------------------------------
-LinkRanks = namedtuple('LinkRanks', 'rank_lo rank_hi valid')
-RankLists = namedtuple('RankLists', 'thr_ptr thr perm valid row')
-RankMetrics = namedtuple('RankMetrics', 'ranked hits_lo hits_hi sum_lo sum_hi mrr')
-
-
-def pair_rank_counts(s, t, thr_ptr, thr, graph_ptr=None, skip_self=False):
-    """(n_gt, n_eq) int32 [T], the entry mgv_pair_rank_counts as it is: for row u and every j in [thr_ptr[u], thr_ptr[u + 1]) the
-    candidates v of u — pair_select's: v in u's graph, without v = u when skip_self, a NaN score never — whose RAW score <s_u, t_v> is
-    > thr[j] and == thr[j].  thr_ptr [N + 1] (int32 on the device, starting at 0), thr [T] float32; EACH ROW'S LIST MUST ASCEND, NaNs
-    last (what torch.sort gives; link_ranks sorts).  One all-pairs walk per 32 entries of a tile's longest list; integer counters,
-    plain stores, no global atomics: the same bytes from call to call.  A NaN threshold gets (0, 0).  No grad."""
-    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
-        _pair_width(s, 'pair_rank_counts')
-    with torch.no_grad():
-        sd, lds, td, ldt, H = _pair_operands(s, t)
-        N = sd.shape[0]
-        if td.shape[0] != N:
-            raise HipLibraryError('pair_rank_counts ranks inside one batch: s and t need the same number of rows (got %d and %d)'
-                                  % (N, td.shape[0]))
-        dev = sd.device
-        gp, G = _pair_graphs(graph_ptr, dev)
-        tp = torch.as_tensor(thr_ptr).to(device=dev, dtype=I32).contiguous()
-        if tp.numel() != N + 1:
-            raise HipLibraryError('thr_ptr needs N + 1 = %d entries (got %d)' % (N + 1, tp.numel()))
-        th = torch.as_tensor(thr).detach().to(device=dev, dtype=F32).contiguous().flatten()
-        n_gt = torch.empty(th.numel(), dtype=I32, device=dev)
-        n_eq = torch.empty(th.numel(), dtype=I32, device=dev)
-        _hip.call('mgv_pair_rank_counts', H, N, ptr(sd), lds, ptr(td), ldt, ptr(gp), G, int(bool(skip_self)), ptr(tp), ptr(th), ptr(n_gt),
-                  ptr(n_eq))
-        return n_gt, n_eq
-
-
-def _rank_by(by, name):
-    if by not in ('src', 'dst'):
-        raise ValueError("%s: by must be 'src' (a link among its source's targets) or 'dst' (among its target's sources), got %r" % (name, by))
-
-
-def _rank_rows(edge_index, N, by):
-    """(row, col) int64 [E] of a link under `by`; an id outside [0, N) raises ValueError (one read-back)."""
-    ei = edge_index.long()
-    if ei.dim() != 2 or ei.shape[0] != 2:
-        raise ValueError('edge_index must be [2, E] (got shape %s)' % (tuple(edge_index.shape),))
-    if ei.shape[1] > 0 and (int(ei.min()) < 0 or int(ei.max()) >= N):
-        raise ValueError('edge_index holds node ids outside [0, %d)' % N)
-    return (ei[0].contiguous(), ei[1].contiguous()) if by == 'src' else (ei[1].contiguous(), ei[0].contiguous())
-
-
-def _f32_order_key(x):
-    """int64 in [0, 2^32): ascending with the float32 value, every NaN (made one NaN first) behind +inf."""
-    x = torch.where(torch.isnan(x), torch.full_like(x, float('nan')), x)
-    b = x.contiguous().view(I32).to(torch.int64) & 0xffffffff
-    return torch.where(b >= 0x80000000, 0xffffffff - b, b + 0x80000000)
-
-
-def _run_ends(start):
-    """(first, last) index of the run each position belongs to; start[i]: a run begins at i (start[0] is True)."""
-    E = start.numel()
-    idx = torch.arange(E, device=start.device)
-    first = torch.cummax(torch.where(start, idx, torch.zeros_like(idx)), 0).values
-    end = torch.ones_like(start)
-    end[:-1] = start[1:]
-    last = torch.cummin(torch.where(end, idx, torch.full_like(idx, E - 1)).flip(0), 0).values.flip(0)
-    return first, last
-
-
-def link_rank_lists(edge_index, score, N, graph_ptr=None, by='src', skip_self=False, row_ptr=None):
-    """The per-row threshold lists mgv_pair_rank_counts takes, from the links' own raw scores (float32 [E], pair_scores_at): plain torch,
-    on whatever device the arguments live.  RankLists(thr_ptr int32 [N + 1], thr float32 [E], perm int64 [E], valid bool [E], row int64
-    [E]), the last four in LIST order: rows ascending, inside a row the scores ascending; perm[i] is the caller's index of entry i.
-    A link is invalid — NaN in thr, behind the row's valid ones, and in no rank, filter or metric — when its other end lies outside
-    its row's graph, when its score is NaN, and under skip_self when it is a self loop.  ONE sort, by the key (row, score); row_ptr
-    (int [N + 1], a GraphPlan's out_ptr for by='src' / in_ptr for by='dst' when edge_index is the plan's) saves counting the rows.
-    The same sort finds a duplicated pair (ValueError): its two copies share row and score bits, so only entries with an equal
-    neighbour are looked at by column.  An id outside [0, N): ValueError."""
-    _rank_by(by, 'link_rank_lists')
-    row, col = _rank_rows(edge_index, N, by)
-    dev = row.device
-    E = row.numel()
-    score = score.detach().to(F32)
-    if graph_ptr is None:
-        ok = torch.ones(E, dtype=torch.bool, device=dev)
-    else:
-        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64).contiguous()
-        if gp.numel() < 2:
-            ok = torch.zeros(E, dtype=torch.bool, device=dev)
-        else:
-            ok = torch.bucketize(row, gp[1:].contiguous(), right=True) == torch.bucketize(col, gp[1:].contiguous(), right=True)
-    ok = ok & ~torch.isnan(score)
-    if skip_self:
-        ok = ok & (row != col)
-    thr = torch.where(ok, score, torch.full_like(score, float('nan')))
-    key, perm = torch.sort(row * (1 << 32) + _f32_order_key(thr), stable=True)
-    row_s, col_s, thr_s, ok_s = row[perm], col[perm], thr[perm], ok[perm]
-    if E > 1:
-        same = key[1:] == key[:-1]
-        near = torch.zeros(E, dtype=torch.bool, device=dev)
-        near[1:] |= same
-        near[:-1] |= same
-        pair = torch.sort(row_s[near] * N + col_s[near]).values
-        if pair.numel() > 1 and bool((pair[1:] == pair[:-1]).any()):
-            raise ValueError('edge_index lists a pair twice: a rank among all candidates is defined for distinct links')
-    if row_ptr is None:
-        thr_ptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-        thr_ptr[1:] = torch.cumsum(torch.bincount(row, minlength=N), 0)
-        thr_ptr = thr_ptr.to(I32)
-    else:
-        thr_ptr = torch.as_tensor(row_ptr).to(device=dev, dtype=I32).contiguous()
-        if thr_ptr.numel() != N + 1:
-            raise ValueError('row_ptr needs N + 1 = %d entries (got %d)' % (N + 1, thr_ptr.numel()))
-    return RankLists(thr_ptr, thr_s, perm, ok_s, row_s)
-
-
-def link_rank_filter(lists, n_gt, n_eq, filtered=True):
-    """LinkRanks(rank_lo, rank_hi int64 [E], valid bool [E]) in the CALLER's edge order from the counts of mgv_pair_rank_counts over
-    link_rank_lists: rank_lo = 1 + n_gt', rank_hi = n_gt' + n_eq'.  filtered: the other true links of the row do not count against a
-    link — n_gt' = n_gt - #{other valid listed links of the row with a higher score}, n_eq' = n_eq - #{others with an equal score},
-    read off the row's own ascending list (positions and runs of equal values: integers, no second walk).  An invalid link has
-    (0, 0, False).  Plain torch on any device."""
-    thr_ptr, thr, perm, ok, row = lists
-    E = thr.numel()
-    gt, eq = n_gt.to(torch.int64), n_eq.to(torch.int64)
-    if filtered and E > 0:
-        start = torch.ones(E, dtype=torch.bool, device=thr.device)
-        start[1:] = (row[1:] != row[:-1]) | (thr[1:] != thr[:-1])          # float equality, the kernel's `==` (-0 == 0); NaN: never
-        first, last = _run_ends(start)
-        nvalid = torch.zeros(thr_ptr.numel() - 1, dtype=torch.int64, device=thr.device).index_add_(0, row, ok.to(torch.int64))
-        vend = thr_ptr[:-1].to(torch.int64) + nvalid                       # the valid links of a row stand first in its list
-        gt = gt - (vend[row] - (last + 1))
-        eq = eq - (last - first)
-    lo = torch.where(ok, 1 + gt, torch.zeros_like(gt))
-    hi = torch.where(ok, gt + eq, torch.zeros_like(gt))
-    rank_lo, rank_hi = torch.empty_like(lo), torch.empty_like(hi)
-    valid = torch.empty_like(ok)
-    rank_lo[perm], rank_hi[perm], valid[perm] = lo, hi, ok
-    return LinkRanks(rank_lo, rank_hi, valid)
-
-
-def link_ranks(s, t, edge_index, graph_ptr=None, by='src', skip_self=False, filtered=True, plan=None):
-    """LinkRanks(rank_lo, rank_hi int64 [E], valid bool [E]) in the caller's edge order: where every listed link (u, v) stands among ALL
-    candidates of its node by raw score <s_u, t_v> — by='src' among the nodes u could point to (its own graph, without u itself when
-    skip_self), by='dst' among the nodes that could feed v (the operands change places as in pair_select).  rank_lo = 1 + #{candidates
-    scored higher}, rank_hi = #{higher} + #{equal}: the best and the worst place its ties allow (a link counts among its own equals,
-    so rank_lo <= rank_hi).  filtered (the default): the row's other true links do not count against a link.
-    The thresholds are pair_scores_at(sigmoid=False), the bits the walk computes: a valid link always finds itself.  Lists by
-    link_rank_lists (one sort; with `plan` — the batch's GraphPlan, when edge_index is the plan's own edge list — its CSR pointers are
-    the rows' ranges), counts by mgv_pair_rank_counts, the filter by link_rank_filter.  Invalid links (other end outside the row's
-    graph, NaN score, a self loop under skip_self): valid False, ranks 0.  An id outside [0, N) or a duplicated pair: ValueError.
-    E = 0 launches nothing.  No grad."""
-    _rank_by(by, 'link_ranks')
-    with torch.no_grad():
-        N = s.shape[0]
-        dev = s.device
-        edge_index = edge_index.to(dev)
-        _rank_rows(edge_index, N, by)                                      # ids before anything dereferences them
-        if edge_index.shape[1] == 0:
-            z = torch.zeros(0, dtype=torch.int64, device=dev)
-            return LinkRanks(z, z.clone(), torch.zeros(0, dtype=torch.bool, device=dev))
-        score = pair_scores_at(s, t, edge_index, sigmoid=False)
-        row_ptr = None
-        if plan is not None and plan.N == N and plan.E == edge_index.shape[1]:
-            row_ptr = plan.out_ptr if by == 'src' else plan.in_ptr
-        lists = link_rank_lists(edge_index, score, N, graph_ptr=graph_ptr, by=by, skip_self=skip_self, row_ptr=row_ptr)
-        if by == 'dst':
-            s, t = t, s
-        n_gt, n_eq = pair_rank_counts(s, t, lists.thr_ptr, lists.thr, graph_ptr=graph_ptr, skip_self=skip_self)
-        return link_rank_filter(lists, n_gt, n_eq, filtered)
-
-
-def rank_metrics(ranks, edge_index, graph_ptr, ks=(1, 3, 10, 50), by='src'):
-    """RankMetrics per graph of the batch, on the ranks' device: ranked int64 [G] (valid links), hits_lo / hits_hi int64 [G, len(ks)]
-    (links with rank_lo <= K / rank_hi <= K), sum_lo / sum_hi int64 [G] (mean rank = sum / ranked) and mrr float64 [G], the mean of
-    (1 / rank_lo + 1 / rank_hi) / 2.  A link counts for the graph of its row (its source; its target for by='dst').  Integer sums
-    are exact in any order; mrr is summed in ONE fixed order — the links grouped by graph (stable sort), a float64 cumulative sum,
-    differences at the graphs' ends — so it is the same bits from run to run.  A graph without a ranked link: mrr NaN, zeros
-    elsewhere."""
-    _rank_by(by, 'rank_metrics')
-    with torch.no_grad():
-        lo, hi, valid = ranks
-        dev = lo.device
-        gp = torch.as_tensor(graph_ptr).to(device=dev, dtype=torch.int64)
-        G = max(gp.numel() - 1, 0)
-        K = len(ks)
-        i64 = dict(dtype=torch.int64, device=dev)
-        if G == 0:
-            return RankMetrics(torch.zeros(0, **i64), torch.zeros((0, K), **i64), torch.zeros((0, K), **i64), torch.zeros(0, **i64),
-                               torch.zeros(0, **i64), torch.zeros(0, dtype=torch.float64, device=dev))
-        row = edge_index.long().to(dev)[0 if by == 'src' else 1]
-        gid = torch.bucketize(row, gp[1:].contiguous(), right=True).clamp_(max=G - 1)
-        v = valid.to(torch.int64)
-        kk = torch.tensor([int(k) for k in ks], **i64)
-        ranked = torch.zeros(G, **i64).index_add_(0, gid, v)
-        hits_lo = torch.zeros((G, K), **i64).index_add_(0, gid, ((lo[:, None] <= kk[None, :]) & valid[:, None]).to(torch.int64))
-        hits_hi = torch.zeros((G, K), **i64).index_add_(0, gid, ((hi[:, None] <= kk[None, :]) & valid[:, None]).to(torch.int64))
-        sum_lo = torch.zeros(G, **i64).index_add_(0, gid, lo * v)
-        sum_hi = torch.zeros(G, **i64).index_add_(0, gid, hi * v)
-        one = torch.ones_like(lo)
-        term = torch.where(valid, (1.0 / torch.where(valid, lo, one).double() + 1.0 / torch.where(valid, hi, one).double()) / 2,
-                           torch.zeros(lo.shape, dtype=torch.float64, device=dev))
-        order = torch.sort(gid, stable=True).indices
-        cs = torch.zeros(lo.numel() + 1, dtype=torch.float64, device=dev)
-        cs[1:] = torch.cumsum(term[order], 0)
-        ends = torch.zeros(G + 1, **i64)
-        ends[1:] = torch.cumsum(torch.bincount(gid, minlength=G), 0)
-        mrr = (cs[ends[1:]] - cs[ends[:-1]]) / ranked.double()             # 0 / 0: NaN for a graph without a ranked link
-        return RankMetrics(ranked, hits_lo, hits_hi, sum_lo, sum_hi, mrr)
-
-
-def _f32(v):
-    return float(torch.tensor(float(v), dtype=F32))
-
-
-def _f32_key(v):
-    """The place of float32(v) in the order of all float32 values, as an integer: adjacent floats differ by 1, -0.0 and 0.0 are both 0."""
-    bits = int(torch.tensor(float(v), dtype=F32).view(I32))
-    return bits if bits >= 0 else -(bits & 0x7fffffff)
-
-
-def _edges_between(lo, hi, bins):
-    """min(bins, all) distinct float32 values across [lo, hi], both ends included, ascending, evenly spaced in the ORDER of the float32
-    values (linear inside a binade, geometric across binades): a bracket of at most 2^32 floats shrinks by bins - 1 per round, so six
-    rounds of 64 edges reach adjacent floats from any start."""
-    a, b = _f32_key(lo), _f32_key(hi)
-    n = max(min(int(bins), b - a + 1), 1)
-    ks = a + (torch.arange(n, dtype=torch.int64) * (b - a)) // max(n - 1, 1)
-    return torch.where(ks >= 0, ks, -ks - (1 << 31)).to(I32).view(F32)
-
-
-def threshold_search(profile_fn, max_pairs, lo=0.0, hi=2.0, bins=64, max_rounds=6):
-    """The bracket logic of sim_threshold_for on any walk: profile_fn(edges float32 [B], ascending) -> int64 [G, B + 1].  The bracket
-    (lower, threshold] always has count(lower) > max_pairs >= count(threshold) with both counts taken from a walk; count(hi) must
-    be 0 <= max_pairs for the caller's `hi`.  -> the dict of sim_threshold_for."""
-    max_pairs = int(max_pairs)
-    if max_pairs < 0:
-        raise HipLibraryError('max_pairs must be >= 0 (got %d)' % max_pairs)
-    bins = min(max(int(bins), 3), PROFILE_MAX_EDGES)
-    lower, upper, pairs_lower, pairs, tight = _f32(lo), _f32(hi), None, None, False
-    if not lower < upper:
-        raise HipLibraryError('the search needs lo < %g (got %g)' % (upper, lower))
-    for rnd in range(max(int(max_rounds), 1)):
-        e = _edges_between(lower, upper, bins)
-        above = counts_above(profile_fn(e)).sum(0).tolist()           # the round's ONE read-back: batch-wide pairs above each edge
-        ev = e.tolist()
-        j = next((i for i, n in enumerate(above) if n <= max_pairs), None)      # the count falls along the table
-        if j is None:
-            raise HipLibraryError('%d pairs are above %g, the upper end of the search: more than max_pairs = %d' % (above[-1], ev[-1], max_pairs))
-        if j == 0:                                                     # only in the first round: the count at lo already fits
-            return {'threshold': ev[0], 'pairs': above[0], 'lower': None, 'pairs_lower': None, 'tight': True}
-        lower, pairs_lower, upper, pairs = ev[j - 1], above[j - 1], ev[j], above[j]
-        tight = _f32_key(upper) - _f32_key(lower) <= 1                 # no float32 strictly between the two ends
-        if tight:
-            break
-    return {'threshold': upper, 'pairs': pairs, 'lower': lower, 'pairs_lower': pairs_lower, 'tight': tight}
-
-
-def sim_threshold_for(x, max_pairs, graph_ptr=None, lo=0.0, bins=64, max_rounds=6, eps=1e-8):
-    """The lowest cosine threshold whose batch-wide pair count fits `max_pairs`, from the distribution instead of trial walks:
-    {'threshold' (a Python float holding a float32 value), 'pairs', 'lower', 'pairs_lower', 'tight'}.  pairs <= max_pairs and pairs is
-    the total sim_pairs lists at `threshold`; when `lower` is not None it is the bracket's other end, lower < threshold with
-    pairs_lower > max_pairs.  The bracket starts as (lo, 2.0] — no cosine exceeds 1 + (2H + 6) 2^-24, so nothing is above 2.0 — and
-    each round puts `bins` distinct float32 edges across it, both ends included, takes ONE sim_profile walk and ONE read-back, and
-    keeps the adjacent pair of edges between which the count crosses max_pairs; it stops when no float32 lies strictly between the
-    two ends (tight) or after max_rounds.  If the count at `lo` already fits, the result is lo with lower = None.
-    Ties are the caller's to understand: 5,000 equal gates are 12.5 M pairs at ONE cosine value, which a threshold takes or leaves
-    as a whole, so the tight answer can lie far below max_pairs.  Zero rows score 0 with everything and never pass a threshold
-    >= 0; equal rows score within (2H + 6) 2^-24 of 1."""
-    _pair_width(x, 'sim_threshold_for')
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        return threshold_search(lambda e: _unit_profile(y, _profile_edges(e, y.device), graph_ptr), max_pairs, lo=lo, hi=2.0, bins=bins,
-                                max_rounds=max_rounds)
-
-
-# ------------------------------------------------------------------------------------------------
-# connected components and candidate classes (added functionality: csrc/components.hip, csrc/mgv_unionfind.h)
-# ------------------------------------------------------------------------------------------------
-_CC_ERR = {1: 'an entry of the forest outside [0, x] (parent was not initialised)', 2: 'a union-find loop reached its cap of 2^20 rounds',
-           3: 'a listed node id outside [0, N)'}
-
-
-def _cc_status(name, st):
-    """st = the four ints of the union-find's status record, already on the host."""
-    if st[0] != 0:
-        raise HipLibraryError('%s: the union-find reported an error: %s (code %d, a = %d, b = %d, rounds = %d)'
-                              % (name, _CC_ERR.get(st[0], 'unknown'), st[0], st[1], st[2], st[3]))
-
-
-def _cc_forest(N, dev):
-    if N >= 2 ** 31:
-        raise HipLibraryError('components: node ids are int32, N = %d is beyond them' % N)
-    parent = torch.empty(N, dtype=I32, device=dev)
-    status = torch.empty(4, dtype=I32, device=dev)
-    _hip.call('mgv_cc_init', N, ptr(parent), ptr(status))
-    return parent, status
-
-
-def _cc_labels(N, parent):
-    label = torch.empty(N, dtype=I32, device=parent.device)
-    _hip.call('mgv_cc_labels', N, ptr(parent), ptr(label), None)      # sizes come with the class table
-    return label
-
-
-def _cc_from_pairs(pair_index, N):
-    """(label, status) of the pair list's components; status is still on the device."""
-    a, b = _edge_rows(pair_index)
-    parent, status = _cc_forest(N, pair_index.device)
-    _hip.call('mgv_cc_union_pairs', N, a.numel(), ptr(a), ptr(b), ptr(parent), ptr(status))
-    return _cc_labels(N, parent), status
-
-
-def _min_size(min_size):
-    if int(min_size) != min_size or int(min_size) < 1:
-        raise HipLibraryError('min_size must be an integer >= 1 (1 lists every node, singletons included), got %r' % (min_size,))
-    return int(min_size)
-
-
-def components(pair_index, N):
-    """label int32 [N]: the connected components of the undirected graph on nodes 0 .. N - 1 whose edges are the columns of pair_index
-    (int64 [2, P], P = 0 included; any order and orientation, duplicates and a == a allowed) — label[i] is the smallest id of i's
-    component, so label[i] == i marks a component's representative and an untouched node is its own.  A concurrent union-find on the
-    device in which a root is only ever hooked under a smaller root: exact, and the same bits from run to run.  For lists from
-    sim_pairs / equivalence_candidates (candidate classes) and from reconstruct_edges (components of the decoded graph,
-    digae_layer.py:31-33) alike.  One synchronisation: the union-find's status record is read back, and anything in it (an id outside
-    [0, N)) raises HipLibraryError.  No grad."""
-    N = int(N)
-    if N < 0:
-        raise HipLibraryError('components: N must be >= 0, got %d' % N)
-    if not (torch.is_tensor(pair_index) and pair_index.dim() == 2 and pair_index.shape[0] == 2):
-        raise HipLibraryError('components: pair_index must be an int64 tensor [2, P]')
-    if not pair_index.is_cuda:
-        raise HipLibraryError('pair_index must live on the GPU (got %s); the hot path has no CPU implementation' % pair_index.device)
-    if pair_index.dtype != torch.int64:
-        raise HipLibraryError('pair_index must be torch.int64 (got %s)' % pair_index.dtype)
-    with torch.no_grad():
-        label, status = _cc_from_pairs(pair_index, N)
-        _cc_status('components', status.tolist())             # the read-back
-    return label
-
-
-def _class_table(label, min_size, status, name):
-    N, dev = label.numel(), label.device
-    ws_ints = _hip.call_value('mgv_cc_class_ws_ints', N)
-    if ws_ints < 0:
-        raise HipLibraryError('%s: MGV_EUNSUPPORTED (unsupported size): N = %d' % (name, N))
-    ws = torch.empty(ws_ints, dtype=I32, device=dev)
-    counts = torch.empty(6, dtype=I32, device=dev)
-    _hip.call('mgv_cc_class_count', N, ptr(label), min_size, ptr(status), ptr(ws), ws_ints, ptr(counts))
-    got = counts.tolist()                                     # the read-back: C, M and the status record
-    _cc_status(name, got[2:])
-    C, M = got[0], got[1]
-    class_ptr = torch.empty(C + 1, dtype=torch.int64, device=dev)
-    members = torch.empty(M, dtype=I32, device=dev)
-    temp_ints = _hip.call_value('mgv_sort_pairs_temp_ints', 4, max(M, 1))
-    temp = torch.empty(max(temp_ints, 1), dtype=I32, device=dev)
-    _hip.call('mgv_cc_class_fill', N, ptr(label), C, M, ptr(ws), ws_ints, ptr(temp), temp_ints, ptr(class_ptr), ptr(members))
-    return class_ptr, members
-
-
-def class_table(label, min_size=2):
-    """(class_ptr int64 [C + 1], members int32 [M]): the classes of `label` (int32 [N] as components / sim_classes return it) with at
-    least min_size members, as one compact table.  Classes come in the order of their labels and members ascend inside a class, so
-    members[class_ptr[c]] is class c's label (its smallest id, the natural representative) and members[class_ptr[c] : class_ptr[c + 1]]
-    the whole class.  min_size = 2 leaves the singletons out; 1 lists every node.  Sizes, two scans and a stable sort by label on the
-    device with ONE read-back (C and M: the result must be allocated).  No grad."""
-    min_size = _min_size(min_size)
-    check(label, I32, 'label')
-    if label.dim() != 1:
-        raise HipLibraryError('class_table: label must be int32 [N]')
-    with torch.no_grad():
-        return _class_table(label, min_size, None, 'class_table')
-
-
-def sim_classes(x, graph_ptr=None, threshold=SIM_THRESHOLD, min_size=2, route='walk', eps=1e-8, max_pairs=None):
-    """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]): the candidate classes a SAT sweeper consumes — the connected
-    components of the relation "same graph and cosine > threshold" on the rows of x (hf), as components' labels (label[i] = the
-    smallest id of i's class) and class_table's table of the classes with at least min_size members.
-    The classes are SINGLE-LINKAGE components of the thresholded relation: two members of one class can have a cosine below the
-    threshold (a chain of close neighbours links them); every member has at least one other member above it.  Primary inputs
-    (hf = 0: cosine 0 with everything) and rows that hold a NaN are always singletons at a positive threshold.  Classes never cross
-    graphs (graph_ptr [G + 1]; None: one graph).  threshold = 1.0 is unreliable: equal rows score within (2H + 6) 2^-24 of 1, not
-    exactly 1, hence the default 0.999.
-    route='walk': the symmetric tile walk of sim_pairs unites each pair where it finds it (mgv_sim_union).  No pair list ever exists:
-    memory is O(N) and nothing is refused for size — 5,000 equal gates are 12.5 M pairs but one class of 5,000.
-    route='pairs': sim_pairs followed by components; it keeps sim_pairs' refusals (max_pairs, free memory).
-    Both routes give the same labels, exactly, and the same bits from run to run.  Unit rows come from row_unit.  One read-back (the
-    table's two sizes and the union-find's status record) besides the two ends of a graph_ptr.  No grad."""
-    if route not in ('walk', 'pairs'):
-        raise HipLibraryError("sim_classes: route must be 'walk' (classes straight from the tile walk) or 'pairs' (sim_pairs, then "
-                              "components), got %r" % (route,))
-    min_size = _min_size(min_size)
-    if route == 'walk' and max_pairs is not None:
-        raise HipLibraryError("sim_classes: max_pairs belongs to route='pairs'; the walk holds no pair list")
-    if route == 'pairs':
-        pi, _, _ = sim_pairs(x, graph_ptr=graph_ptr, threshold=threshold, max_pairs=max_pairs, eps=eps)
-        with torch.no_grad():
-            label, status = _cc_from_pairs(pi, x.shape[0])
-            return (label,) + _class_table(label, min_size, status, 'sim_classes')
-    y = row_unit(x, eps)
-    with torch.no_grad():
-        N, H = y.shape
-        gp, G = _pair_graphs(graph_ptr, y.device)
-        parent, status = _cc_forest(N, y.device)
-        _hip.call('mgv_sim_union', H, N, ptr(y), H, ptr(gp), G, float(threshold), ptr(parent), ptr(status))
-        label = _cc_labels(N, parent)
-        return (label,) + _class_table(label, min_size, status, 'sim_classes')
 
 
 def _recon_heavy(plan):
@@ -1747,8 +944,8 @@ class ReconLossFn(torch.autograd.Function):
         std = check(st.detach().contiguous(), F32, 'st')
         N, H2 = std.shape
         H = H2 // 2
-        ps, pd = _edge_rows(pos_edge_index)
-        ns, nd = _edge_rows(neg_edge_index)
+        ps, pd = edge_rows(pos_edge_index)
+        ns, nd = edge_rows(neg_edge_index)
         Ep, En = ps.numel(), ns.numel()
         dev = std.device
         sums = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -1824,84 +1021,6 @@ def confusion_counts(pred_bin, gt_bin):
 
 
 # ------------------------------------------------------------------------------------------------
-# link-prediction ranking metrics (digvae_model.py:177-189: decode, copy to the host, sklearn)
-# ------------------------------------------------------------------------------------------------
-LINK_RECORD_WORDS = 8       # AUC, AP (float64) | U2, P, Q, tie groups, NaN scores (int64) | spare
-
-
-def link_record(st_or_s, t=None, pos_edge_index=None, neg_edge_index=None, return_scores=False):
-    """One ranking of P positive against Q negative pairs, entirely on the device and without a host synchronisation
-    (csrc/link_metrics.hip: score keys -> radix sort -> two streaming passes).  Returns the 64-byte record the kernels wrote, a
-    float64[8] tensor: words 0-1 AUC and AP, words 2-6 (read through `.view(torch.int64)`) U2, P, Q, the number of tie groups and
-    the number of NaN scores (non-zero: the metrics mean nothing), word 7 unused; with `return_scores` also the fp32 scores that
-    were ranked, positives first.  `st_or_s`: the [N, 2H] `st` layout of recon_loss (t=None) or s [N, H] with t [N, H].
-    `neg_edge_index`: a [2, Q] tensor or a sampling.NegativeEdges.  No autograd: the metrics are piecewise constant."""
-    neg = getattr(neg_edge_index, 'edge_index', neg_edge_index)
-    P, Q = int(pos_edge_index.shape[1]), int(neg.shape[1])
-    if P == 0 or Q == 0:
-        # sklearn's behaviour for y_true with one class; both sizes are host values: nothing is launched
-        raise ValueError('Only one class present (%d positive, %d negative pairs): ROC-AUC and average precision are not defined' % (P, Q))
-    sd = check(st_or_s.detach().contiguous(), F32, 'st' if t is None else 's')
-    if t is None:
-        ld = sd.shape[1]
-        H = ld // 2
-        td = sd[:, H:]
-    else:
-        td = check(t.detach().contiguous(), F32, 't')
-        ld = H = sd.shape[1]
-        if td.shape != sd.shape:
-            raise HipLibraryError('s and t must have the same shape (got %s and %s)' % (tuple(sd.shape), tuple(td.shape)))
-    n = P + Q
-    if n >= 1 << 31:
-        raise HipLibraryError('mgv_link_keys failed: %s (%d pairs; the ranking holds fewer than 2^31)' % (_hip._ERR[-2], n))
-    ps, pd = _edge_rows(pos_edge_index)
-    ns, nd = _edge_rows(neg)
-    for name, e in (('pos_edge_index', ps), ('neg_edge_index', ns)):
-        if not e.is_cuda:
-            raise HipLibraryError('%s must live on the GPU (got %s)' % (name, e.device))
-    dev = sd.device
-    rec = torch.zeros(LINK_RECORD_WORDS, dtype=torch.float64, device=dev)
-    status = rec.view(I32)[12:13]                      # low half of int64 word 6
-    buf = torch.empty(3, n + (-n) % 4, dtype=I32, device=dev)      # keys, sorted keys, permutation: each on a 16-byte boundary
-    keys, skey, order = buf[0, :n], buf[1, :n], buf[2, :n]
-    scores = torch.empty(n, dtype=F32, device=dev) if return_scores else None
-    _hip.call('mgv_link_keys', H, ptr(sd), ptr(td), ld, ptr(ps), ptr(pd), P, ptr(ns), ptr(nd), Q, ptr(keys), ptr(scores), ptr(status))
-    t_i = _hip.call_value('mgv_sort_pairs_temp_ints', 4, n)
-    w_i = _hip.call_value('mgv_link_rank_work_ints', n)
-    if t_i < 0 or w_i < 0:
-        raise HipLibraryError('link metrics: no workspace size for %d pairs' % n)
-    temp = torch.empty(t_i + w_i + 2, dtype=I32, device=dev)
-    _hip.call('mgv_sort_pairs', 4, n, ptr(keys), ptr(skey), ptr(order), 32, ptr(temp), t_i)
-    work = temp[t_i + (t_i & 1):]                      # 8-byte aligned
-    _hip.call('mgv_link_rank', n, P, ptr(skey), ptr(order), ptr(rec), ptr(work), work.numel())
-    return (rec, scores) if return_scores else rec
-
-
-def link_auc_ap(st_or_s, t=None, pos_edge_index=None, neg_edge_index=None, return_scores=False):
-    """(metrics, status[, scores, counts]): `metrics` float64[2] = (AUC, AP) and `status` int64[1] = the number of NaN scores, both
-    on the device and both views of one link_record (no host synchronisation; a non-zero status means a NaN was ranked and the
-    metrics are void).  `return_scores`: also the ranked fp32 scores (positives first) and counts int64[4] = U2, P, Q, tie groups."""
-    out = link_record(st_or_s, t, pos_edge_index, neg_edge_index, return_scores)
-    rec = out[0] if return_scores else out
-    words = rec.view(torch.int64)
-    if return_scores:
-        return rec[:2], words[6:7], out[1], words[2:6]
-    return rec[:2], words[6:7]
-
-
-def read_link_records(records):
-    """[(auc, ap), ...] of link_record tensors as Python floats: ONE host read for all of them; ValueError if any ranked a NaN
-    (sklearn: "Input contains NaN")."""
-    if not records:
-        return []
-    host = torch.stack(list(records)).cpu()
-    bad = host.view(torch.int64)[:, 6]
-    if bool((bad != 0).any()):
-        raise ValueError('Input contains NaN: %d of the ranked scores are NaN' % int(bad.sum()))
-    return [(float(r[0]), float(r[1])) for r in host]
-
-
-# ------------------------------------------------------------------------------------------------
 # losses on node rows
 # ------------------------------------------------------------------------------------------------
 class L1LossFn(torch.autograd.Function):
@@ -1933,7 +1052,7 @@ def l1_loss(x, target):
 def pair_lists(tt_pair_index, num_nodes):
     """The truth-table pairs grouped by first and by second member: (a_ptr[N+1], a_pair[P], b_ptr[N+1], b_pair[P]), pair ids in
     their original order inside a group (csrc/plan_build.hip).  Static per batch: the trainer caches it on the batch."""
-    pa, pb = _edge_rows(tt_pair_index)
+    pa, pb = edge_rows(tt_pair_index)
     P, N, dev = pa.numel(), int(num_nodes), pa.device
     i32 = dict(dtype=I32, device=dev)
     a_ptr, b_ptr = torch.empty(N + 1, **i32), torch.empty(N + 1, **i32)
@@ -1958,7 +1077,7 @@ class FuncLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hf, tt_pair_index, tt_sim, lists=None, passthrough=False):
         hfd = check(hf.detach().contiguous(), F32, 'hf')
-        pa, pb = _edge_rows(tt_pair_index)
+        pa, pb = edge_rows(tt_pair_index)
         tt = check(tt_sim.detach().to(F32).contiguous(), F32, 'tt_sim')
         P, H = pa.numel(), hfd.shape[1]
         dis = torch.empty(P, dtype=F32, device=hfd.device)
@@ -2009,103 +1128,6 @@ def func_loss_passthrough(hf, tt_pair_index, tt_sim, cache=None):
     """(loss, hf'): hf' is hf; feed hf' to the other consumer of hf (the readout) and the two gradients meet inside the
     function-loss backward kernel instead of in an N x H add."""
     return FuncLossFn.apply(hf, tt_pair_index, tt_sim, _pair_lists_for(hf, tt_pair_index, cache), True)
-
-
-# ------------------------------------------------------------------------------------------------
-# exact functional ordering accuracy (added functionality: every comparison of get_function_acc, utils/utils.py:111-147, counted;
-# mgv_concord_counts)
-# ------------------------------------------------------------------------------------------------
-CONCORD_TILE = 256              # csrc/concordance.hip kConcordTile: rows of a workgroup and columns of an LDS tile
-CONCORD_MAX_GAPS = 8
-MIN_GAP = 0.05                  # utils/utils.py:112
-
-
-def segment_table(first, graph_ptr, second=None):
-    """(seg_ptr int64 [G + 1], ok bool scalar) in plain torch, on the device of `first`: segment g of the listed pairs are those whose
-    first node lies in graph g, found by searchsorted — which is the pairs of graph g exactly when they come grouped by circuit in
-    circuit order and neither node leaves the circuit; `ok` says so."""
-    gp = torch.as_tensor(graph_ptr).to(device=first.device, dtype=torch.int64).contiguous()
-    G = gp.numel() - 1
-    if G < 1:
-        return torch.zeros(1, dtype=torch.int64, device=first.device), torch.as_tensor(first.numel() == 0, device=first.device)
-    gid = torch.searchsorted(gp[1:].contiguous(), first, right=True)           # the graph of each pair's first node
-    ok = ((first >= gp[0]) & (first < gp[-1])).all()
-    if first.numel() > 1:
-        ok = ok & (gid[1:] >= gid[:-1]).all()
-    if second is not None:
-        ok = ok & (torch.searchsorted(gp[1:].contiguous(), second, right=True) == gid).all() & (second >= gp[0]).all()
-    seg = torch.searchsorted(gid, torch.arange(G + 1, dtype=torch.int64, device=first.device), right=False)
-    return seg, ok
-
-
-def pair_segments(tt_pair_index, graph_ptr, cache=None):
-    """int32 seg_ptr [G + 1] on the device: the listed pairs of circuit g are [seg_ptr[g], seg_ptr[g + 1]).  The pairs must come grouped
-    by circuit in circuit order (synthetic.collate and the parser deliver them so) with both nodes of a pair in one circuit, else
-    ValueError: one small host read when the table is built, which is kept on `cache` (the batch) like pair_lists."""
-    pa, pb = _edge_rows(tt_pair_index)
-    gp = torch.as_tensor(graph_ptr)
-    key = (pa.numel(), gp.numel(), pa.device)
-    if cache is not None:
-        kept = getattr(cache, '_mgv_pair_segments', None)
-        if kept is not None and kept[0] == key:
-            return kept[1]
-    with torch.no_grad():
-        seg, ok = segment_table(pa, gp, pb)
-        if not bool(ok):
-            raise ValueError('tt_pair_index must list its pairs grouped by circuit, in circuit order, both nodes of a pair in one circuit')
-        seg = seg.to(I32)
-    if cache is not None:
-        cache._mgv_pair_segments = (key, seg)
-    return seg
-
-
-def _concord_gaps(gaps):
-    """The gaps as the entry takes them: a ctypes float array on the host, converted to float32 ONCE; NaN or negative: ValueError."""
-    g = torch.as_tensor(gaps, dtype=torch.float64).flatten().to(F32)
-    if not 1 <= g.numel() <= CONCORD_MAX_GAPS:
-        raise ValueError('1 to %d gaps (got %d)' % (CONCORD_MAX_GAPS, g.numel()))
-    vals = g.tolist()
-    if any(not v >= 0.0 for v in vals):
-        raise ValueError('a gap must be >= 0 and not NaN (got %r)' % (vals,))
-    return (_hip.ctypes.c_float * len(vals))(*vals)
-
-
-def concord_counts(gt, pred, seg_ptr=None, gaps=(MIN_GAP,)):
-    """int64 [G, B, 3] on the device (G = 1 without seg_ptr): {eligible, concordant, tied} over EVERY unordered comparison {p, q} of one
-    segment of the listed pairs (mgv_concord_counts).  dd = gt[q] - gt[p], de = pred[q] - pred[p] in float32; eligible at gap j:
-    dd != 0 and |dd| >= gaps[j]; concordant: dd and de both > 0 or both < 0; tied: de == 0.  A NaN in gt: not eligible; a NaN in pred:
-    eligible, neither concordant nor tied.  Integer atomics: exact, the same bytes from call to call; no host read.  No grad."""
-    with torch.no_grad():
-        g = check(torch.as_tensor(gt).detach().to(F32).contiguous().flatten(), F32, 'gt')
-        p = check(torch.as_tensor(pred).detach().to(device=g.device, dtype=F32).contiguous().flatten(), F32, 'pred')
-        if p.numel() != g.numel():
-            raise HipLibraryError('gt and pred list the same pairs (got %d and %d)' % (g.numel(), p.numel()))
-        hg = _concord_gaps(gaps)
-        B = len(hg)
-        sp, G = None, 0
-        if seg_ptr is not None:
-            sp = torch.as_tensor(seg_ptr).to(device=g.device, dtype=I32).contiguous()
-            G = sp.numel() - 1
-            if G < 0:
-                raise HipLibraryError('seg_ptr needs at least one entry')
-        out = torch.empty((max(G, 1), B, 3), dtype=torch.int64, device=g.device)
-        _hip.call('mgv_concord_counts', g.numel(), ptr(g), ptr(p), ptr(sp), G, hg, B, ptr(out))
-        return out if sp is None else out[:G]
-
-
-def function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=None, gaps=(MIN_GAP,), cache=None):
-    """(acc float64 [G, B], counts int64 [G, B, 3]) on the device: per circuit and gap, concordant / eligible over ALL comparisons of two
-    listed truth-table pairs whose distances differ by at least the gap — the quantity get_function_acc (utils/utils.py:111-147)
-    estimates from 100 draws — with pred = 1 - sim_at(hf, tt_pair_index) in float32, the bits Model.functional_similarity reports and
-    the reference's expression.  acc is -1 where nothing is eligible, the reference's return value for that case.  Without graph_ptr:
-    one circuit.  No grad, no host read once the batch's segment table exists (pair_segments, kept on `cache`)."""
-    with torch.no_grad():
-        pred = 1.0 - sim_at(hf.detach(), tt_pair_index)
-        seg = None if graph_ptr is None else pair_segments(tt_pair_index, graph_ptr, cache)
-        counts = concord_counts(tt_sim.detach().to(device=pred.device), pred, seg, gaps)
-        el, co = counts[..., 0], counts[..., 1]
-        acc = torch.where(el > 0, co.double() / el.clamp(min=1).double(), torch.full_like(el, -1, dtype=torch.float64))
-        return acc, counts
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2272,3 +1294,16 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, gr
         check(t, F32, n)
     _hip.call('mgv_adam_step', param.numel(), ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), float(lr),
               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), int(step))
+
+
+# ------------------------------------------------------------------------------------------------
+# the analysis surface lives in pairs / similarity / metrics (none of them imports this module); the documented public names are
+# re-bound here.  Their underscored helpers are not: patch those in their home module.
+# ------------------------------------------------------------------------------------------------
+from .pairs import (PROFILE_MAX_EDGES, PairScoresFn, counts_above, dense_scores, pair_profile, pair_scores,  # noqa: E402,F401
+                    pair_scores_at, pair_select, pair_topk, reconstruct_edges, reconstruction_counts, reconstruction_curve)
+from .similarity import (SIM_THRESHOLD, class_table, components, row_unit, sim_at, sim_classes, sim_pairs,  # noqa: E402,F401
+                         sim_profile, sim_threshold_for, sim_topk, threshold_search)
+from .metrics import (CONCORD_MAX_GAPS, CONCORD_TILE, LINK_RECORD_WORDS, MIN_GAP, LinkRanks, RankLists, RankMetrics,  # noqa: E402,F401
+                      concord_counts, function_accuracy, link_auc_ap, link_rank_filter, link_rank_lists, link_ranks, link_record,
+                      pair_rank_counts, pair_segments, rank_metrics, read_link_records, segment_table)

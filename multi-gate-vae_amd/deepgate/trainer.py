@@ -13,7 +13,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import metrics, ops
 from .data import CircuitBatch
 from .optim import FlatAdam
 from .prefetch import BatchPrefetcher
@@ -203,8 +203,8 @@ class Trainer():
         if want_rank:
             loss_status['link_metrics'] = self.model.last_link_metrics
         if want_func_acc:
-            loss_status['func_counts'] = ops.function_accuracy(hf, batch['tt_pair_index'], batch['tt_sim'],
-                                                               graph_ptr=getattr(batch, 'graph_ptr', None), cache=batch)[1][:, 0]
+            loss_status['func_counts'] = metrics.function_accuracy(hf, batch['tt_pair_index'], batch['tt_sim'],
+                                                                   graph_ptr=getattr(batch, 'graph_ptr', None), cache=batch)[1][:, 0]
         return loss_status
 
     def _encoder_half_rounds(self):
@@ -330,7 +330,7 @@ class Trainer():
                 rank_cols = ''
                 if rank:
                     # one host read for the whole phase; raises if a batch ranked a NaN score
-                    pairs = ops.read_link_records(records)
+                    pairs = metrics.read_link_records(records)
                     if pairs:
                         rank_cols = ' |AUC: {:.4f} |AP: {:.4f}'.format(sum(a for a, _ in pairs) / len(pairs), sum(b for _, b in pairs) / len(pairs))
                 if facc and func_counts:

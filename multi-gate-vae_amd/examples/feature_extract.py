@@ -191,7 +191,7 @@ def main(argv=None):
     np.savez(a.out, **out)
     print('[INFO] %d graphs embedded in %.2f s -> %s' % (len(graphs), time.time() - t0, a.out))
     if a.link_metrics:
-        pairs = deepgate.ops.read_link_records(records)          # one host read for all batches
+        pairs = deepgate.metrics.read_link_records(records)      # one host read for all batches
         print('[INFO] link prediction over %d batches: AUC %.4f, AP %.4f' % (len(pairs), sum(x for x, _ in pairs) / len(pairs),
                                                                              sum(y for _, y in pairs) / len(pairs)))
     if a.predict_links:

@@ -125,7 +125,7 @@ def test_planted_defects_are_caught_by_the_checker_of_the_device_tests():
 
 
 def test_host_refusals_of_the_functions_need_no_gpu():
-    from deepgate import _hip, ops
+    from deepgate import _hip, ops, similarity
     from deepgate._model_base import FunctionalModel as M
     x, x48 = torch.zeros(4, 16), torch.zeros(4, 48)
     pairs = torch.zeros((2, 3), dtype=I64)
@@ -153,8 +153,8 @@ def test_host_refusals_of_the_functions_need_no_gpu():
     with pytest.raises(E):
         ops.components(torch.zeros(3, dtype=I64), 4)
     with pytest.raises(E, match='union-find'):
-        ops._cc_status('components', [3, 7, 99, 0])
-    ops._cc_status('components', [0, 0, 0, 0])
+        similarity._cc_status('components', [3, 7, 99, 0])
+    similarity._cc_status('components', [0, 0, 0, 0])
     # the surface says what a user will meet
     for f in (ops.sim_classes, M.equivalence_classes):
         doc = ' '.join(f.__doc__.split()).lower()

@@ -285,7 +285,7 @@ def test_the_entries_refuse_on_the_host_before_anything_is_launched():
 
 
 def test_host_refusals_of_the_functions_need_no_gpu():
-    from deepgate import _hip, ops
+    from deepgate import _hip, ops, similarity
     x, x48 = torch.zeros(4, 16), torch.zeros(4, 48)
     pairs = torch.zeros((2, 3), dtype=I64)
     for call in (lambda v: ops.row_unit(v), lambda v: ops.sim_topk(v, 2), lambda v: ops.sim_pairs(v), lambda v: ops.sim_at(v, pairs)):
@@ -294,14 +294,14 @@ def test_host_refusals_of_the_functions_need_no_gpu():
         with pytest.raises(_hip.HipLibraryError, match='GPU'):
             call(x)                                          # no CPU implementation behind it
     with pytest.raises(_hip.HipLibraryError) as e:
-        ops._sim_room(98113, False, 50000, None)
+        similarity._sim_room(98113, False, 50000, None)
     assert '98113' in str(e.value) and '50000' in str(e.value) and 'threshold' in str(e.value) and 'sim_topk' in str(e.value)
     with pytest.raises(_hip.HipLibraryError) as e:
-        ops._sim_room(2 ** 30, True, None, 2 ** 30)
+        similarity._sim_room(2 ** 30, True, None, 2 ** 30)
     assert str(2 ** 30) in str(e.value) and '24.0 GiB' in str(e.value)
-    ops._sim_room(10, True, 10, 240)                         # exactly at both limits: accepted
-    ops._sim_room(10, False, None, 200)
-    ops._sim_room(0, False, 0, 0)
+    similarity._sim_room(10, True, 10, 240)                  # exactly at both limits: accepted
+    similarity._sim_room(10, False, None, 200)
+    similarity._sim_room(0, False, 0, 0)
 
 
 def test_the_header_declares_the_entries_with_their_reference_lines():

@@ -142,7 +142,7 @@ def test_counts_past_32_bits_match_the_closed_form():
 
 def test_out_is_overwritten_guards_stay_and_a_table_beyond_p_is_clamped():
     dev, T = _dev(), _T()
-    from deepgate import _hip, ops
+    from deepgate import _hip, metrics
     from deepgate._hip import ptr
     P = 2 * T + 11
     gt, pred = CR.random_case(P, 5)
@@ -152,7 +152,7 @@ def test_out_is_overwritten_guards_stay_and_a_table_beyond_p_is_clamped():
     g, p = torch.as_tensor(gt, device=dev), torch.as_tensor(pred, device=dev)
     sp = torch.as_tensor(seg, dtype=torch.int32, device=dev)
     n = 3 * 3 * 3
-    hg = ops._concord_gaps(GAPS[3])
+    hg = metrics._concord_gaps(GAPS[3])
     bufs = []
     for sentinel in (-7, 123456789012345):
         buf = torch.full((n + 64,), sentinel, dtype=torch.int64, device=dev)

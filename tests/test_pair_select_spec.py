@@ -182,7 +182,7 @@ def test_a_wrong_score_or_a_transposed_list_is_caught():
 
 # ------------------------------------------------------------------------------------------------ host-only paths
 def test_host_refusals_need_no_gpu():
-    from deepgate import _hip, ops
+    from deepgate import _hip, ops, pairs
     s = torch.zeros(4, 16)
     with pytest.raises(_hip.HipLibraryError, match="by must be 'src'"):
         ops.pair_select(s, s, by='both')
@@ -191,15 +191,15 @@ def test_host_refusals_need_no_gpu():
     with pytest.raises(_hip.HipLibraryError, match='GPU'):
         ops.pair_select(s, s)                               # no CPU implementation behind it
     with pytest.raises(_hip.HipLibraryError) as e:
-        ops._select_room(98113, False, 50000, None)
+        pairs._select_room(98113, False, 50000, None)
     msg = str(e.value)
     assert '98113' in msg and '50000' in msg and 'threshold' in msg and 'pair_topk' in msg
     with pytest.raises(_hip.HipLibraryError) as e:
-        ops._select_room(3 * 2 ** 30, True, None, 2 ** 30)
+        pairs._select_room(3 * 2 ** 30, True, None, 2 ** 30)
     msg = str(e.value)
     assert str(3 * 2 ** 30) in msg and '24.0 GiB' in msg and 'pair_topk' in msg
-    ops._select_room(10, True, 10, 80)                      # exactly at both limits: accepted
-    ops._select_room(0, False, 0, 0)
+    pairs._select_room(10, True, 10, 80)                    # exactly at both limits: accepted
+    pairs._select_room(0, False, 0, 0)
 
 
 def test_the_header_declares_both_entries_with_their_reference_lines():

@@ -44,7 +44,7 @@ def main(argv=None):
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--skip-batch', action='store_true')
     a = ap.parse_args(argv)
-    from deepgate import _hip, ops
+    from deepgate import _hip, ops, similarity
     ptr = _hip.ptr
     dev = torch.device('cuda:0')
     H = 64
@@ -104,7 +104,7 @@ def main(argv=None):
         out['torch_over_hist64'] = out['torch_64_ms'] / out['hist_64_ms']
         # threshold by count: the profile search against a bisection of count walks
         res, steps, walks = [None], [0], [0]
-        real_profile = ops._unit_profile
+        real_profile = similarity._unit_profile
 
         def counted_profile(*args):
             walks[0] += 1
@@ -112,15 +112,15 @@ def main(argv=None):
 
         def search():
             walks[0] = 0
-            ops._unit_profile = counted_profile
+            similarity._unit_profile = counted_profile
             try:
                 res[0] = ops.sim_threshold_for(x, max_pairs, graph_ptr=gp)
             finally:
-                ops._unit_profile = real_profile
+                similarity._unit_profile = real_profile
 
         def bisect():
             yy = ops.row_unit(x)
-            lo, hi, steps[0] = ops._f32_key(0.0), ops._f32_key(2.0), 0
+            lo, hi, steps[0] = similarity._f32_key(0.0), similarity._f32_key(2.0), 0
             val = lambda k: float(torch.tensor(k, dtype=torch.int32).view(torch.float32))
 
             def total(thr):

@@ -35,8 +35,7 @@ def main():
     attn_u = torch.randn(T, 2 * H, device=dev) * 0.1
     Wvc = torch.randn(T, 3 * H, 2 * H, device=dev) * 0.1
     bvc, bih, bhh = (torch.randn(T, 3 * H, device=dev) * 0.1 for _ in range(3))
-    hf = ops.func_sweep(plan, hs, attn_u, Wvc, bvc, bih, bhh) if hasattr(ops, 'func_sweep') else \
-        ops.FuncSweepFn.apply(plan, hs, attn_u, Wvc, bvc, bih, bhh)
+    hf = ops.FuncSweepFn.apply(plan, hs, attn_u, Wvc, bvc, bih, bhh)
     wpack = ops.sweep_wpack(Wvc)
     ghf = torch.randn(N, H, device=dev)
     ghs = torch.empty(N, H, device=dev)
