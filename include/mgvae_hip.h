@@ -408,6 +408,29 @@ int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_
  * bytes; refusals as for mgv_pair_select_fill (cap < 0: MGV_EINVAL). */
 int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                         const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
+/* ---- matching across circuits (added functionality; trainer.py:158-160 in the arithmetic of digae_layer.py:31-33; csrc/pair_scores.hip).
+ * The walk of mgv_pair_topk / mgv_pair_select_* on unit rows y (mgv_row_unit), raw scores, where the candidates of a row of graph g are
+ * ALL rows of graph peer[g]: a golden design against its revision, a library block against an instance.  graph_ptr [G+1] int32 as
+ * above, required; peer [G] int32 on the device: -1 = the rows of g have no candidates; peer[g] = g is allowed and a row is then a
+ * candidate of itself (there is no skip_self); peer need not be an involution and several graphs may name one peer.  Range ends read
+ * through peer are clamped into [0, N].  A cosine is ONE k-ascending fmaf chain, the bits mgv_pair_scores_at(y, y, sigmoid = 0) reports
+ * for the pair.  A row tile walks only the column tiles that hold a candidate of one of its 64 rows, in ascending order.
+ * top-k: idx[N][k] int32 batch-wide ids by cosine descending, ties by ascending id, -1 past the end; score[N][k] the cosine, -inf where
+ * idx is -1; n_above[N] int32 the number of ALL candidates whose cosine is > threshold; a NaN is nobody's candidate.  1 <= k <= 32.
+ * Refused before anything is launched: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); k out of range, NULL graph_ptr or peer, a bad
+ * row stride or alignment, N out of range, a graph_ptr that does not start at 0 and end at N, an entry of peer outside [-1, G) (peer
+ * is read back whole for this, one small blocking copy beside graph_ptr's two ends): MGV_EINVAL.  N = 0 launches nothing. */
+int mgv_cross_topk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, int k, float threshold,
+                   int32_t* idx, float* score, int32_t* n_above, void* stream);
+/* count (trainer.py:158-160, digae_layer.py:31-33): n_sel[N] int32, written for every row = n_above of mgv_cross_topk for the same
+ * arguments.  Refusals as there. */
+int mgv_cross_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, float threshold,
+                           int32_t* n_sel, void* stream);
+/* fill (trainer.py:158-160, digae_layer.py:31-33): row u's candidates with cosine > threshold as ascending batch-wide int32 ids at
+ * col[row_ptr[u] ..], score[cap] (or NULL) the cosine beside each.  The contract of mgv_pair_select_fill: a row writes only inside
+ * [row_ptr[u], min(row_ptr[u+1], cap)), no atomics, a second call gives the same bytes; cap < 0: MGV_EINVAL. */
+int mgv_cross_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, float threshold,
+                          const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream);
 /* ---- the distribution of all-pair scores (added functionality; the thresholds of the entries above chosen by count: digae_layer.py:31-33,
  * digae_model.py:118-122 for the decoder, trainer.py:158-160 for the cosine; csrc/pair_scores.hip).  One walk of mgv_pair_select_count —
  * the same candidates (u's own graph, without v = u when skip_self), the same reported score (the sigmoid when `sigmoid`), a NaN counted

@@ -16,6 +16,8 @@
 
 #include <limits.h>
 
+#include <vector>
+
 namespace mgv {
 
 constexpr int kPairTile = 64;          // output tile: 64 x 64, wave w owns rows 16 w .. 16 w + 15 and all 64 columns
@@ -723,6 +725,225 @@ __global__ __launch_bounds__(kThreads) void k_pair_rank(int64_t N, const float* 
     }
 }
 
+// ---------------------------------------------------------------------------------- candidates in ANOTHER graph: matching across circuits
+// The walk of k_pair_topk / k_pair_select on unit rows (s = t = y, the raw score) where the candidates of a row of graph g are ALL rows
+// of graph peer[g] (peer[g] = -1: none; peer[g] = g: the row's own graph, itself included).  hf depends only on a circuit's own
+// structure, so rows of two graphs of one batch are comparable as they stand: a golden design against its revision.
+// What differs from the walk above is only WHERE the candidates lie: a row tile's rows may belong to several graphs whose peers lie
+// far apart, so the column tiles are not one range but a few.  cross_spans leaves them in LDS as ascending disjoint spans of column
+// tiles, and the tile loop — the same five lines — stands once inside a loop over the spans; a column tile that holds no candidate of
+// any of the 64 rows is never loaded or scored.  With one span (two large graphs) the loop is the one k_pair_topk runs.
+// The existing kernels are left as they are on purpose: their register allocation moves with the range logic (NOTEBOOK 2026-10-19).
+
+// The candidate columns [rlo[i], rhi[i]) of row u0 + i: the rows of the peer of the row's graph, clamped into [0, N] as row_ranges
+// clamps; nothing for a row past N, a row behind the last graph, peer = -1 or a peer outside the table.
+__device__ __forceinline__ void cross_ranges(int64_t N, int64_t u0, const int32_t* gp, int G, const int32_t* peer, int* rlo, int* rhi) {
+    if (threadIdx.x >= kPairTile) return;
+    const int64_t u = u0 + threadIdx.x;
+    int64_t lo = 0, hi = 0;
+    if (u < N) {
+        int a = 0, b = G;                                  // first graph whose end lies behind u
+        while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+        const int p = a < G ? peer[a] : -1;
+        if (p >= 0 && p < G) { lo = gp[p]; hi = gp[p + 1]; }
+        lo = lo < 0 ? 0 : (lo > N ? N : lo);               // whatever the tables hold, no column outside [0, N) is touched
+        hi = hi < lo ? lo : (hi > N ? N : hi);
+    }
+    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+}
+
+// The column tiles that hold a candidate of any of the 64 rows: *ns ascending, disjoint, non-adjacent spans [ta[j], tb[j]).  Wave 0
+// does it behind the barrier that publishes the ranges; the caller's next barrier publishes the spans.  Rows of one graph follow each
+// other, so a range counts once, at its first row (at most 64 ranges): each lane ranks its range among them by first tile (a rank sort
+// over a ballot of the first rows), then lane 0 merges the sorted ranges that overlap or touch.
+__device__ __forceinline__ void cross_spans(const int* rlo, const int* rhi, int* ta, int* tb, int* ns) {
+    if (threadIdx.x >= kPairTile) return;
+    const int i = threadIdx.x, lo = rlo[i], hi = rhi[i];
+    const bool first = lo < hi && (i == 0 || lo != rlo[i - 1] || hi != rhi[i - 1]);
+    const int t0 = lo / kPairTile, t1 = (hi + kPairTile - 1) / kPairTile;
+    const uint64_t firsts = __ballot(first);
+    int rank = 0;
+    for (uint64_t m = firsts; m != 0ull; m &= m - 1) {
+        const int j = __ffsll((unsigned long long)m) - 1, tj = rlo[j] / kPairTile;
+        rank += (tj < t0 || (tj == t0 && j < i)) ? 1 : 0;
+    }
+    if (first) { ta[rank] = t0; tb[rank] = t1; }
+    wave_lds_fence();
+    if (i == 0) {
+        const int n = __popcll(firsts);
+        int out = 0, end = 0;
+        for (int j = 0; j < n; ++j) {
+            const int a = ta[j], b = tb[j];                // read before slot out <= j is written
+            if (out > 0 && a <= end) { end = b > end ? b : end; }
+            else { ta[out] = a; end = b; ++out; }
+            tb[out - 1] = end;
+        }
+        *ns = out;
+    }
+}
+
+// k_pair_topk's consumer — the blocks through LDS, four lanes per row, the sorted list per row — on the spans of cross_spans.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_cross_topk(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
+                                                         int k, float threshold, int32_t* idx, float* score, int32_t* n_above) {
+    constexpr int LDS_SC = 17;
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ float sc[kPairTile * LDS_SC];
+    __shared__ float lv[kPairTile * kTopkMax];
+    __shared__ int li[kPairTile * kTopkMax];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], ta[kPairTile], tb[kPairTile], ns;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    cross_ranges(N, u0, gp, G, peer, rlo, rhi);
+    const int srow = 16 * w + (lane >> 2), sub = lane & 3;
+    for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
+    __syncthreads();
+    cross_spans(rlo, rhi, ta, tb, &ns);
+    __syncthreads();
+    const int64_t su = u0 + srow;                          // the row this lane scans for
+    const int mylo = rlo[srow], myhi = rhi[srow], spans = ns;
+    const int no = 0;                                      // no skip_self, no sigmoid: a row of a self-peer is its own candidate
+    const int64_t row0 = u0 + 16 * w;
+    float a[H / 4];
+    load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
+    int cnt = 0;
+    for (int sp = 0; sp < spans; ++sp) {
+        const int64_t ct0 = ta[sp], ct1 = tb[sp];
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                wave_lds_fence();                              // the previous block's reads are done
+#pragma unroll
+                for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * LDS_SC + r] = acc[c][g];
+                wave_lds_fence();
+                const int64_t cb = ct * kPairTile + 16 * c;
+                for (int st = 0; st < 4; ++st) {
+                    const int64_t col = cb + 4 * st + sub;
+                    const float v = sc[srow * LDS_SC + 4 * st + sub];
+                    float rep;
+                    const bool valid = candidate<false>(v, col, su, mylo, myhi, no, no, rep);
+                    cnt += (valid && rep > threshold) ? 1 : 0;
+                    const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
+                    if (__ballot(pass) == 0ull) continue;
+                    for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
+                        if (pass && sub == turn) {
+                            float* L = lv + srow * kTopkMax;
+                            int* I = li + srow * kTopkMax;
+                            if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
+                                int pos = k - 1;
+                                while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
+                                    L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
+                                }
+                                L[pos] = v; I[pos] = (int)col;
+                            }
+                        }
+                        wave_lds_fence();
+                    }
+                }
+            }
+        }
+    }
+    wave_lds_fence();
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    if (su < N) {
+        if (sub == 0) n_above[su] = cnt;
+        for (int j = sub; j < k; j += 4) {
+            const int id = li[srow * kTopkMax + j];
+            idx[su * k + j] = id == INT_MAX ? -1 : id;
+            score[su * k + j] = id == INT_MAX ? -INFINITY : lv[srow * kTopkMax + j];
+        }
+    }
+}
+
+// k_pair_select's consumer — the decision where the score lies, FILL = false: counts, FILL = true: ballot, prefix popcount and the row's
+// cursor — on the spans of cross_spans.  The spans ascend and a row's candidates lie in one of them: ascending ids, no atomics.
+template <int H, bool FILL>
+__global__ __launch_bounds__(kThreads) void k_cross_select(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
+                                                           float threshold, int32_t* n_sel, const int64_t* row_ptr, int64_t cap,
+                                                           int32_t* col_out, float* score_out) {
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], ta[kPairTile], tb[kPairTile], ns;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    cross_ranges(N, u0, gp, G, peer, rlo, rhi);
+    __syncthreads();
+    cross_spans(rlo, rhi, ta, tb, &ns);
+    __syncthreads();
+    const int64_t row0 = u0 + 16 * w;
+    const int spans = ns, no = 0;
+    // the lane's four rows 4 q + g: candidate range, slots, cursor
+    int mylo[4], myhi[4], cnt[4];
+    int64_t base[4];
+    uint64_t room[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int lr = 16 * w + 4 * q + g;
+        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; cnt[g] = 0;
+        base[g] = 0; room[g] = 0;
+        if (FILL && u0 + lr < N) {
+            const int64_t b = row_ptr[u0 + lr], e0 = row_ptr[u0 + lr + 1], e = e0 < cap ? e0 : cap;
+            base[g] = b;
+            room[g] = e > b ? (uint64_t)e - (uint64_t)b : 0ull;     // exact for any b < e
+        }
+    }
+    float a[H / 4];
+    load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
+    for (int sp = 0; sp < spans; ++sp) {
+        const int64_t ct0 = ta[sp], ct1 = tb[sp];
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t col = ct * kPairTile + 16 * c + r;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float rep;
+                    const bool pass = candidate<false>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], no, no, rep) && rep > threshold;
+                    if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
+                    const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
+                    const uint64_t i = (uint64_t)(unsigned)cnt[g] + (uint64_t)__popc(bits & ((1u << r) - 1u));
+                    cnt[g] += __popc(bits);
+                    if (pass && i < room[g]) {                  // i < room: base + i < min(row_ptr[u+1], cap), no overflow
+                        const int64_t pos = base[g] + (int64_t)i;
+                        if (pos >= 0) {
+                            col_out[pos] = (int32_t)col;
+                            if (score_out != nullptr) score_out[pos] = rep;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!FILL) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            int n = cnt[g];
+            n += __shfl_xor(n, 1, 64);
+            n += __shfl_xor(n, 2, 64);
+            n += __shfl_xor(n, 4, 64);
+            n += __shfl_xor(n, 8, 64);
+            const int64_t u = row0 + 4 * q + g;
+            if (r == 0 && u < N) n_sel[u] = n;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- unit rows
 // y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
 // row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
@@ -909,6 +1130,67 @@ extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, c
 extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
                                    const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
     return select_fill_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, threshold, 0, true, row_ptr, cap, col, score, (hipStream_t)stream);
+}
+
+// the arguments the cross entries share, in the order of the walk entries: the width, both tables present, pair_walk_args on (y, y),
+// then every entry of peer in [-1, G) — the table is read back whole (G int32s, one more small blocking copy beside graph_ptr's ends)
+static int cross_walk_args(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, hipStream_t st,
+                           bool* launch) {
+    *launch = false;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(graph_ptr != nullptr && peer != nullptr && G >= 0);
+    const int rc = pair_walk_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, launch);
+    if (rc != MGV_OK) return rc;
+    if (G > 0) {
+        std::vector<int32_t> p((size_t)G);
+        hipError_t e = hipMemcpyAsync(p.data(), peer, sizeof(int32_t) * (size_t)G, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return (int)e;
+        for (int g = 0; g < G; ++g) MGV_CHECK_ARG(p[g] >= -1 && p[g] < G);
+    }
+    return MGV_OK;
+}
+
+extern "C" int mgv_cross_topk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, int k,
+                              float threshold, int32_t* idx, float* score, int32_t* n_above, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // as mgv_pair_topk
+    bool launch;
+    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(idx != nullptr && score != nullptr && n_above != nullptr);
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_cross_topk<w>, N, st, N, y, ldy, graph_ptr, G, peer, k, threshold, idx, score, n_above);
+    });
+}
+
+extern "C" int mgv_cross_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
+                                      float threshold, int32_t* n_sel, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(n_sel != nullptr);
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_cross_select<w, false>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, n_sel, nullptr, 0, nullptr, nullptr);
+    });
+}
+
+extern "C" int mgv_cross_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
+                                     float threshold, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(cap >= 0);
+    bool launch;
+    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
+    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_cross_select<w, true>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, nullptr, row_ptr, cap, col, score);
+    });
 }
 
 extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,

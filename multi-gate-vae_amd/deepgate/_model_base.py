@@ -223,6 +223,39 @@ class FunctionalModel(nn.Module):
         and the default is 0.999.  Exact and the same bits from run to run: equal to ops.components of equivalence_candidates."""
         return similarity.sim_classes(hf, graph_ptr=graph_ptr, threshold=threshold, min_size=min_size)
 
+    def match_gates(self, hf, k, graph_ptr, peer, threshold=0.999):
+        """(idx [N, k] int32, cos [N, k], n_above [N] int32) ACROSS circuits: every gate's k functionally closest gates in the PEER of
+        its circuit by cosine of hf — peer [G]: the candidates of a gate of graph g are all gates of graph peer[g], -1 for none, g
+        itself allowed (a gate is then its own candidate), many graphs may name one peer — as batch-wide ids, -1 / -inf past the
+        end, and the number of the peer's gates whose cosine with it is > threshold (ops.cross_topk, streamed without an N x N
+        array).  Added functionality: the candidate internal equivalence points between a golden design and its revision, where
+        similar_gates looks inside one circuit; hf depends only on a circuit's own structure, so two circuits embedded by one model
+        are comparable as they stand (trainer.py:158-160).  Primary inputs have hf = 0 (cosine 0 with everything) and are matched by
+        name in practice; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1, hence the default 0.999."""
+        return similarity.cross_topk(hf, k, graph_ptr, peer, threshold=threshold)
+
+    def cross_equivalence_candidates(self, hf, graph_ptr, peer, threshold=0.999, mutual=False, with_scores=False, max_pairs=None):
+        """(pair_index int64 [2, P], row_ptr int64 [N + 1], cos [P] or None): every pair (gate u, gate v of the peer of u's circuit)
+        whose hf have a cosine > threshold, listed per u in ascending v (ops.cross_pairs; peer as in match_gates).  With an
+        involutive peer a pair appears once from each side.  mutual=True: only the reciprocal best matches — v is u's closest gate
+        and u is v's — each once with u in the lower-indexed circuit (ops.cross_mutual), returned as (pair_index [2, M], None, cos
+        [M] or None); it is defined where peer[peer[g]] = g and has no list to refuse.  More than `max_pairs` pairs raise
+        HipLibraryError before anything is filled.  Added functionality (trainer.py:158-160): the cut points of combinational
+        equivalence checking.  Primary inputs (hf = 0) are never reported at a positive threshold; use 0.999 rather than 1.0."""
+        if mutual:
+            pi, cos = similarity.cross_mutual(hf, graph_ptr, peer, threshold=threshold)
+            return pi, None, (cos if with_scores else None)
+        return similarity.cross_pairs(hf, graph_ptr, peer, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
+
+    def cross_equivalence_classes(self, hf, graph_ptr, peer, threshold=0.999, min_size=2):
+        """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]) as equivalence_classes returns them, but the classes may span
+        a circuit and its peer: the connected components of "cosine of hf > threshold" over the pairs of
+        cross_equivalence_candidates together with those of equivalence_candidates (ops.cross_classes; peer as in match_gates).  A
+        class that holds gates of both circuits is a set of candidate equivalence points a checker can merge.  Added functionality
+        (trainer.py:158-160).  Single linkage; primary inputs (hf = 0) and rows with a NaN are always singletons; circuits share a
+        class only through peer links; use 0.999 rather than 1.0."""
+        return similarity.cross_classes(hf, graph_ptr, peer, threshold=threshold, min_size=min_size)
+
     def similarity_profile(self, hf, thresholds, graph_ptr=None):
         """int64 [G, B] on the device: per graph, the number of unordered gate pairs whose cosine of hf is > each of `thresholds`
         (strictly ascending, at most 256) — what equivalence_candidates would list at each of them, as integers, from ONE walk

@@ -6,8 +6,8 @@ import torch
 
 from . import _hip
 from ._hip import F32, I32, HipLibraryError, check, edge_rows, ptr
-from .pairs import (PROFILE_MAX_EDGES, _count_scan_fill, _list_room, _list_rows, _pair_graphs, _pair_rows, _pair_width, _profile_edges,
-                    counts_above, pair_scores_at, pair_topk)
+from .pairs import (PROFILE_MAX_EDGES, _count_scan_fill, _graph_of, _list_room, _list_rows, _pair_graphs, _pair_rows, _pair_width,
+                    _profile_edges, counts_above, pair_scores_at, pair_topk)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -297,3 +297,117 @@ def sim_classes(x, graph_ptr=None, threshold=SIM_THRESHOLD, min_size=2, route='w
         _hip.call('mgv_sim_union', H, N, ptr(y), H, ptr(gp), G, float(threshold), ptr(parent), ptr(status))
         label = _cc_labels(N, parent)
         return (label,) + _class_table(label, min_size, status, 'sim_classes')
+
+
+# ------------------------------------------------------------------------------------------------
+# matching across circuits (added functionality: mgv_cross_topk / mgv_cross_select_*; a golden design against its revision)
+# ------------------------------------------------------------------------------------------------
+# hf depends only on a circuit's own structure and one model embeds every circuit of a batch, so rows of different graphs are comparable
+# as they stand.  `peer` [G] says who is a candidate: the candidates of a row of graph g are ALL rows of graph peer[g]; -1: none;
+# peer[g] = g: the row's own graph, itself included (there is no skip_self here); it need not be an involution, and several graphs may
+# name one peer (ten revisions against one golden design).  The two facts at the head of this file hold here too.
+def _peer_table(peer, graph_ptr, name):
+    """(graph_ptr int32 [G + 1], peer int32 [G]) on the HOST, checked before anything touches the device: peer needs a graph_ptr
+    (HipLibraryError), has one integer per graph and every entry in [-1, G) (ValueError).  A table that lives on the device is read
+    back for this."""
+    if graph_ptr is None:
+        raise HipLibraryError('%s: peer names graphs, so it needs graph_ptr [G + 1] (got None)' % name)
+    gp = torch.as_tensor(graph_ptr).detach().cpu().flatten()
+    if gp.numel() < 1:
+        raise HipLibraryError('graph_ptr needs at least one entry')
+    G = gp.numel() - 1
+    p = torch.as_tensor(peer).detach().cpu()
+    if p.numel() and (p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool):     # ([] is a float tensor)
+        raise ValueError('%s: peer must hold integers, one graph index per graph (got %s)' % (name, p.dtype))
+    if p.dim() != 1 or p.numel() != G:
+        raise ValueError('%s: peer must have one entry per graph, [%d] (got shape %s)' % (name, G, tuple(p.shape)))
+    if G and (int(p.min()) < -1 or int(p.max()) >= G):
+        raise ValueError('%s: every entry of peer must be -1 (no candidates) or a graph index in [0, %d) (got %d .. %d)'
+                         % (name, G, int(p.min()), int(p.max())))
+    return gp.to(I32), p.to(I32)
+
+
+def cross_topk(x, k, graph_ptr, peer, threshold=SIM_THRESHOLD, eps=1e-8):
+    """(idx [N, k] int32, cos [N, k], n_above [N] int32): per row u of graph g the k rows of graph peer[g] with the largest cosine
+    (batch-wide ids; ties: lower id first; -1 / -inf past the end, and everywhere when peer[g] = -1) and the number of ALL rows of
+    peer[g] whose cosine is > threshold.  mgv_cross_topk on the unit rows: a cosine is the same bits as in cross_pairs and sim_at; a
+    row tile walks only the column tiles that hold one of its rows' candidates.  Nothing is read back except graph_ptr's two ends and
+    peer, which the launcher checks.  No grad."""
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_topk')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        N, H = y.shape
+        dev = y.device
+        gp, pr, G = gph.to(dev), ph.to(dev), ph.numel()
+        k = int(k)
+        kk = min(max(k, 1), 32)
+        idx = torch.empty((N, kk), dtype=I32, device=dev)
+        cos = torch.empty((N, kk), dtype=F32, device=dev)
+        n_above = torch.empty(N, dtype=I32, device=dev)
+        _hip.call('mgv_cross_topk', H, N, ptr(y), H, ptr(gp), G, ptr(pr), k, float(threshold), ptr(idx), ptr(cos), ptr(n_above))
+        return idx, cos, n_above
+
+
+def _cross_room(total, with_scores, max_pairs, free):
+    """cross_pairs' refusals, as _sim_room."""
+    _list_room('cross_pairs', total, free, noun='pairs', listed='%d pairs', limit_name='max_pairs', limit=max_pairs,
+               item_bytes=24 if with_scores else 20,
+               hint='raise the threshold, or take the k best matches per gate with ops.cross_topk / match_gates')
+
+
+def cross_pairs(x, graph_ptr, peer, threshold=SIM_THRESHOLD, with_scores=False, max_pairs=None, eps=1e-8):
+    """(pair_index int64 [2, P], row_ptr int64 [N + 1], score [P] or None): pair_index[0] is a row u, pair_index[1] a row v of the peer
+    of u's graph with cosine > threshold; ordered by u and then v, row_ptr delimits the rows' lists.  With an involutive peer
+    (peer[peer[g]] = g) a pair appears ONCE FROM EACH SIDE, as (u, v) in u's list and as (v, u) in v's, with the same bits.
+    mgv_cross_select_*: count, exclusive int64 scan, ONE read-back of the total (the result must be allocated: the synchronisation
+    cross_topk does not have), fill; nothing of size N^2, no atomics, the same bytes from call to call.  A total above `max_pairs` or
+    beyond the free memory raises HipLibraryError before anything is allocated or filled.  No grad."""
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_pairs')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        N, H = y.shape
+        dev = y.device
+        gp, pr, G = gph.to(dev), ph.to(dev), ph.numel()
+        common = (H, N, ptr(y), H, ptr(gp), G, ptr(pr), float(threshold))
+        row_ptr, col, score = _count_scan_fill('mgv_cross_select_count', 'mgv_cross_select_fill', N, common, dev, with_scores,
+                                               lambda total, free: _cross_room(total, with_scores, max_pairs, free))
+        rows = _list_rows(row_ptr, col.numel())
+        return torch.stack([rows, col.to(torch.int64)]), row_ptr, score
+
+
+def cross_mutual(x, graph_ptr, peer, threshold=SIM_THRESHOLD, eps=1e-8):
+    """(pair_index int64 [2, M], cos [M]): the reciprocal best matches — the pairs (u, v) where v is u's top-1 in the peer of u's graph,
+    u is v's top-1 in the peer of v's graph and the cosine is > threshold — each once, with u in the lower-indexed graph (u <= v
+    inside a graph that is its own peer), ordered by u.  Defined only where peer[peer[g]] = g: graphs where that fails contribute
+    nothing.  From ONE cross_topk with k = 1 and device torch ops; a tie for a row's top-1 goes to the lower id, as there."""
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_mutual')
+    idx, cos, _ = cross_topk(x, 1, gph, ph, threshold=threshold, eps=eps)
+    with torch.no_grad():
+        dev = idx.device
+        N, G = idx.shape[0], ph.numel()
+        if N == 0 or G == 0:
+            return torch.zeros((2, 0), dtype=torch.int64, device=dev), torch.zeros(0, dtype=F32, device=dev)
+        pl = ph.to(torch.int64)
+        inv = (pl >= 0) & (pl[pl.clamp(min=0)] == torch.arange(G))          # peer[peer[g]] == g
+        u = torch.arange(N, dtype=torch.int64, device=dev)
+        v = idx[:, 0].to(torch.int64)
+        back = idx[v.clamp(min=0), 0].to(torch.int64)
+        gid = _graph_of(torch.cat([u, v.clamp(min=0)]), gph.to(device=dev, dtype=torch.int64), G)
+        gu, gv = gid[:N], gid[N:]
+        keep = (v >= 0) & (back == u) & (cos[:, 0] > threshold) & inv.to(dev)[gu] & ((gu < gv) | ((gu == gv) & (u <= v)))
+        return torch.stack([u[keep], v[keep]]), cos[keep, 0]
+
+
+def cross_classes(x, graph_ptr, peer, threshold=SIM_THRESHOLD, min_size=2, max_pairs=None, eps=1e-8):
+    """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]) as sim_classes returns them: the connected components of
+    "cosine > threshold" over the cross pairs (cross_pairs) TOGETHER WITH the within-circuit pairs (sim_pairs), so a class may now
+    span a graph and its peer — and nothing else: two graphs share a class only through a chain of peer links (several graphs that
+    name one peer can meet in it).  Single linkage, as sim_classes.  components and class_table on the two lists; each list keeps its
+    refusals (max_pairs applies to each, free memory).  No grad."""
+    min_size = _min_size(min_size)
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_classes')
+    cross, _, _ = cross_pairs(x, gph, ph, threshold=threshold, max_pairs=max_pairs, eps=eps)
+    own, _, _ = sim_pairs(x, graph_ptr=gph, threshold=threshold, max_pairs=max_pairs, eps=eps)
+    with torch.no_grad():
+        label, status = _cc_from_pairs(torch.cat([cross, own], dim=1), x.shape[0])
+        return (label,) + _class_table(label, min_size, status, 'cross_classes')

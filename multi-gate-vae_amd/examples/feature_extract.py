@@ -9,6 +9,8 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --reconstruct 0.5   # + the decoded edge list of every graph
     python examples/feature_extract.py --type aig --synthetic 4 --similar 8         # + every gate's 8 functionally closest gates
     python examples/feature_extract.py --type aig --synthetic 4 --equivalences 0.999   # + the gate pairs with cos(hf) above 0.999
+    python examples/feature_extract.py --type aig --synthetic 4 --match 8           # + every gate's 8 closest gates in the NEXT/PREVIOUS graph
+    python examples/feature_extract.py --type aig --synthetic 4 --cross_equivalences 0.999   # + the gate pairs ACROSS graphs 2i, 2i + 1
     python examples/feature_extract.py --type aig --synthetic 4 --equivalences_max 1000   # the same, at most 1000 pairs per batch
     python examples/feature_extract.py --type aig --synthetic 4 --similarity_profile 12   # + pairs per graph above 1 - 2^-j, j = 1..12
     python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
@@ -54,6 +56,15 @@ def main(argv=None):
                     'whose hf have a cosine above THR, the candidates for equivalence checking (name/eq_pairs [2, P], local ids, first < '
                     'second; name/eq_cos; Model.equivalence_candidates).  Equal rows score within (2H + 6) 2^-24 of 1, not exactly 1: '
                     'use 0.999 rather than 1.0; primary inputs (hf = 0) are never reported at a positive THR')
+    ap.add_argument('--match', type=int, default=0, metavar='K', help='match gates ACROSS circuits: the consecutive graphs (2i, 2i + 1) of '
+                    'every batch are each other\'s peer (a golden design and its revision; an odd last graph has none), and every gate '
+                    'gets its K closest gates of the peer graph by cosine of hf (name/match_idx, ids local to the PEER graph, -1 past '
+                    'the end; name/match_cos; Model.match_gates; 1 <= K <= 32).  Primary inputs have hf = 0 and match nothing')
+    ap.add_argument('--cross_equivalences', type=float, default=None, metavar='THR', help='with the pairing of --match, also store for '
+                    'every graph the pairs (its gate, a gate of its peer graph) whose hf have a cosine above THR, the candidate '
+                    'equivalence points between two circuits (name/xeq_pairs [2, P]: row 0 local to the graph, row 1 local to its '
+                    'peer, listed per gate in ascending order; name/xeq_cos; Model.cross_equivalence_candidates).  A pair appears in '
+                    'both graphs\' lists; use 0.999 rather than 1.0')
     ap.add_argument('--classes', type=float, default=None, metavar='THR', help='also store every graph\'s equivalence candidate classes, '
                     'what a SAT sweeper consumes: the connected components of "cos(hf) above THR" (name/eq_label [n], the smallest local '
                     'id of a gate\'s class; name/eq_class_ptr [C + 1] and name/eq_members [M], the classes with at least two gates, '
@@ -119,6 +130,18 @@ def main(argv=None):
             if a.similar:
                 sim_idx, sim_cos, _ = model.similar_gates(hf, a.similar, graph_ptr=batch.graph_ptr)
                 sim_idx, sim_cos = sim_idx.cpu().numpy(), sim_cos.cpu().numpy()
+            if a.match or a.cross_equivalences is not None:
+                G = len(chunk)
+                peer = [g ^ 1 if (g ^ 1) < G else -1 for g in range(G)]          # (2i, 2i + 1); an odd last graph has no peer
+                pbase = [ptr[q] if q >= 0 else 0 for q in peer]
+            if a.match:
+                m_idx, m_cos, _ = model.match_gates(hf, a.match, batch.graph_ptr, peer)
+                m_idx, m_cos = m_idx.cpu().numpy(), m_cos.cpu().numpy()
+            if a.cross_equivalences is not None:
+                xeq, xeq_ptr, xeq_cos = model.cross_equivalence_candidates(hf, batch.graph_ptr, peer, threshold=a.cross_equivalences,
+                                                                           with_scores=True)
+                xeq, xeq_cos = xeq.cpu().numpy(), xeq_cos.cpu().numpy()
+                xptr = xeq_ptr[batch.graph_ptr.to(xeq_ptr.device).long()].tolist()             # the graphs' places in the list
             eq_thr = a.equivalences
             if a.equivalences_max is not None:
                 eq_thr = model.equivalence_threshold(hf, a.equivalences_max, graph_ptr=batch.graph_ptr,
@@ -164,6 +187,16 @@ def main(argv=None):
                     loc = sim_idx[ptr[k]:ptr[k + 1]]
                     out[name + '/sim_idx'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
                     out[name + '/sim_cos'] = sim_cos[ptr[k]:ptr[k + 1]]
+                if a.match:
+                    loc = m_idx[ptr[k]:ptr[k + 1]]
+                    out[name + '/match_idx'] = np.where(loc >= 0, loc - pbase[k], -1).astype(np.int32)
+                    out[name + '/match_cos'] = m_cos[ptr[k]:ptr[k + 1]]
+                if a.cross_equivalences is not None:
+                    pr = xeq[:, xptr[k]:xptr[k + 1]]
+                    out[name + '/xeq_pairs'] = np.stack([pr[0] - ptr[k], pr[1] - pbase[k]]).astype(np.int32)
+                    out[name + '/xeq_cos'] = xeq_cos[xptr[k]:xptr[k + 1]]
+                    print('[INFO] %s: %d gate pairs with %s at cos(hf) > %g' % (name, xptr[k + 1] - xptr[k], 'graph %d' % (b0 + peer[k])
+                                                                              if peer[k] >= 0 else 'no peer', a.cross_equivalences))
                 if eq_thr is not None:
                     out[name + '/eq_pairs'] = (eq[:, qptr[k]:qptr[k + 1]] - ptr[k]).astype(np.int32)
                     out[name + '/eq_cos'] = eq_cos[qptr[k]:qptr[k + 1]]
