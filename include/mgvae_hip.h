@@ -515,6 +515,34 @@ int mgv_cc_class_fill(int64_t N, const int32_t* label, int64_t C, int64_t M, int
  * parent (N > 0) or status: MGV_EINVAL. */
 int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,
                   int32_t* status, void* stream);
+/* cross classes straight from the cross walk (trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): the tiles, spans,
+ * candidates and decision of mgv_cross_select_fill — v any row of the peer of u's graph, cosine not NaN and > threshold (strict) — but
+ * where the fill would store v in row u's list, u and v are united in parent (initialised by mgv_cc_init; several calls may add to
+ * one forest: mgv_sim_union followed by mgv_cross_union on one forest gives classes that span a graph and its peer).  u == v (a row of
+ * a graph that is its own peer) does nothing, as in mgv_cc_union_pairs.  No pair list ever exists: memory is O(N) whatever the
+ * threshold.  CONTRACT: mgv_cc_labels afterwards gives exactly the components of the list mgv_cross_select_fill returns for the same
+ * arguments — a cosine is the same bits whichever entry computes it, and a root is only hooked under a smaller root.  Ids reach the
+ * union-find only after the walk's clamp of the ranges into [0, N]: no id outside [0, N) is dereferenced whatever graph_ptr and peer
+ * hold.  With an involutive peer every pair is met from both sides; the second meeting is two finds and an exit (no rows are skipped).
+ * Arguments and refusals as mgv_cross_select_count; in addition a NULL parent (N > 0) or a NULL status: MGV_EINVAL.  N = 0 launches
+ * nothing. */
+int mgv_cross_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, float threshold,
+                    int32_t* parent, int32_t* status, void* stream);
+/* the distribution of cross scores (trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): the walk, candidates and score of
+ * mgv_cross_select_count — unit rows y, every row of the peer of the row's graph, raw cosine — binned as mgv_pair_hist bins:
+ * hist[g][k] = number of (row u of graph g, candidate v in graph peer[g]) with #{j : cos > edges[j]} == k.  hist int64 [G][B + 1] is
+ * OVERWRITTEN (the launcher zeroes it); the row is the ROW's graph, so with an involutive peer a pair is counted once from each side,
+ * in hist[g] and in hist[peer[g]].  A graph with peer = -1 or without rows has a zero row; a NaN is counted nowhere.  Defining
+ * property, as integers: for every g and j, sum(hist[g][j+1:]) equals the sum over g's rows of n_sel of mgv_cross_select_count at
+ * threshold = edges[j] — the same `>` on the same bits.  Integer atomics only (64-bit LDS counters for a row tile's first and last
+ * graph, direct 64-bit adds for the graphs between them, a lane's consecutive candidates of one (graph, bin) merged into one add):
+ * exact, the same bytes from call to call.
+ * Refused before anything is zeroed or launched: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); B outside [1, 256], NULL edges or
+ * hist, a table that does not ascend strictly or holds a NaN (read back, as for mgv_pair_hist), and everything mgv_cross_select_count
+ * refuses (NULL graph_ptr or peer, a peer entry outside [-1, G), a bad row stride or alignment, N out of range, a graph_ptr that does
+ * not start at 0 and end at N): MGV_EINVAL.  N = 0 zeroes hist and launches nothing. */
+int mgv_cross_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, const float* edges,
+                   int B, int64_t* hist, void* stream);
 /* sums[0] += sum_pos -log(sigma+1e-15), sums[1] += sum_neg -log(1-sigma+1e-15); counts += {TP,FP,TN,FN}
  * (trainer.py:240-244); pred_bin[Epos+Eneg] optional */
 int mgv_recon_loss_fwd(int H, const float* s, const float* t, int ld, const int64_t* pos_src, const int64_t* pos_dst,

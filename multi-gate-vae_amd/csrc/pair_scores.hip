@@ -944,6 +944,187 @@ __global__ __launch_bounds__(kThreads) void k_cross_select(int64_t N, const floa
     }
 }
 
+// cross_ranges with the row's graph index beside its range (rgi[i] < max(G, 1): a row of hist), as row_ranges<true> leaves it.  A
+// function of its own: the three kernels above keep the cross_ranges they were compiled with.
+__device__ __forceinline__ void cross_ranges_gi(int64_t N, int64_t u0, const int32_t* gp, int G, const int32_t* peer, int* rlo, int* rhi,
+                                                int* rgi) {
+    if (threadIdx.x >= kPairTile) return;
+    const int64_t u = u0 + threadIdx.x;
+    int64_t lo = 0, hi = 0;
+    int gi = 0;
+    if (u < N) {
+        int a = 0, b = G;                                  // first graph whose end lies behind u
+        while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+        const int p = a < G ? peer[a] : -1;
+        if (a < G) gi = a;
+        if (p >= 0 && p < G) { lo = gp[p]; hi = gp[p + 1]; }
+        lo = lo < 0 ? 0 : (lo > N ? N : lo);               // whatever the tables hold, no column outside [0, N) is touched
+        hi = hi < lo ? lo : (hi > N ? N : hi);
+    }
+    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi; rgi[threadIdx.x] = gi;
+}
+
+// ---------------------------------------------------------------------------------- cross classes straight from the walk
+// The walk of k_cross_select<H, true> — the same spans, tiles, candidate<false> on the raw cosine and `> threshold` — with k_sim_union's
+// consumer: where the fill would store column `col` in row `row`'s list, the pair is united in `parent` (mgv_unionfind.h).  A lane
+// decides its 16 entries of the tile into a bit mask and unites the set bits outside the MFMA section.  A cosine is the same bits
+// whichever kernel computes it and a root is only hooked under a smaller root, so the components are exactly those of the list
+// mgv_cross_select_fill writes.  row == col (a row of a self-peer) unites nothing, as in mgv_cc_union_pairs.
+// Ids: a row decides something only when its range is not empty, which cross_ranges grants only to a row below N, and a column passes
+// only inside [rlo, rhi), clamped into [0, N]: both ids lie inside parent whatever graph_ptr and peer hold.
+// With an involutive peer every pair is met from both sides; the second meeting is two finds and an exit.  The rows of the higher
+// graph of such a couple are NOT skipped: a row tile holds rows of several graphs, so the skip saves tiles only where a whole tile
+// belongs to one skipped graph, and it would make the kernel's spans differ from the fill's (NOTEBOOK 2026-10-20).
+// LDS: score tile + 1,028 B of tables = 34,820 B at H = 128, 18,436 B at H = 64, 10,244 B at H = 32, 6,148 B at H = 16.  The
+// compiler's resource report: 159 VGPRs + 16 AGPRs and 2 waves per SIMD at H = 128, 109 + 16 and 4 at H = 64, 92 + 16 and 4 at
+// H = 32, 72 + 8 and 6 at H = 16, nothing spilled: at least the waves of k_cross_select<H, false> at every width.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_cross_union(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
+                                                          float threshold, int32_t* parent, int32_t* status) {
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], ta[kPairTile], tb[kPairTile], ns;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    cross_ranges(N, u0, gp, G, peer, rlo, rhi);
+    __syncthreads();
+    cross_spans(rlo, rhi, ta, tb, &ns);
+    __syncthreads();
+    const int64_t row0 = u0 + 16 * w;
+    const int spans = ns, no = 0;
+    int mylo[4], myhi[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { mylo[g] = rlo[16 * w + 4 * q + g]; myhi[g] = rhi[16 * w + 4 * q + g]; }   // empty for a row past N
+    float a[H / 4];
+    load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
+    for (int sp = 0; sp < spans; ++sp) {
+        const int64_t ct0 = ta[sp], ct1 = tb[sp];
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+            unsigned bits = 0;                                  // bit 4 c + g: the lane's entry (row 4 q + g, column 16 c + r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t col = ct * kPairTile + 16 * c + r;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    float rep;
+                    const bool pass = candidate<false>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], no, no, rep) && rep > threshold;
+                    bits |= pass ? 1u << (4 * c + g) : 0u;
+                }
+            }
+            while (bits != 0) {                                 // row < N and mylo <= col < myhi <= N: both ids inside parent
+                const int b = __ffs(bits) - 1;
+                bits &= bits - 1;
+                const int u = (int)(row0 + 4 * q + (b & 3)), v = (int)(ct * kPairTile + 16 * (b >> 2) + r);
+                if (u != v) uf_unite(parent, u, v, status);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------- the distribution of cross scores
+// The walk of k_cross_select<H, false> — the same spans, tiles and candidate<false> on the raw cosine — with k_pair_hist's consumer:
+// a candidate of a row of graph g is binned by bin = #{j : cos > edges[j]} into hist[g] (the ROW's graph, not the peer's), with the
+// branch-free binary search over the +inf-padded table in LDS, the 64-bit LDS counters for the tile's first and last row graph, direct
+// 64-bit integer adds for the graphs between them and the per-lane run merge, all as described there.  What differs is how much a graph
+// between the first and the last can add directly: it has at most 62 rows, but each of them has all rows of the peer as candidates,
+// not 62; the run merge (a lane's consecutive candidates of one (graph, bin) are one add) is what bounds those adds.
+// Integer atomics only: exact, the same bytes from call to call.  A lane's run counts at most 16 candidates per tile: int32.
+// LDS at H = 128: score tile 33,792 B + three row tables 768 B + two span tables and their count 516 B + edges 2,048 B + counters
+// 4,112 B = 41,240 B with the counters' alignment; 24,856 B at H = 64, 16,664 B at H = 32, 12,568 B at H = 16.  Registers and waves
+// per SIMD as the compiler's resource report has them (-Rpass-analysis=kernel-resource-usage): H = 128: 153 VGPRs + 16 AGPRs, 2 waves;
+// H = 64: 111 + 16, 4 waves; H = 32: 88 + 16, 4 waves; H = 16: 77 + 16, 5 waves — against 2 / 3 / 4 / 5 of k_cross_select<H, false>
+// (174, 116, 85 and 70 VGPRs + 16): the histogram costs the count walk no occupancy at any width.  Registers bound it, not LDS: the
+// waves the registers allow are at most five workgroups per CU, 5 x 12,568 B at H = 16 and 2 x 41,240 B at H = 128 of its 160 KB.
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_cross_hist(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
+                                                         const float* edges, int B, int top, unsigned long long* hist) {
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], rgi[kPairTile], ta[kPairTile], tb[kPairTile], ns;
+    __shared__ float el[kHistTable];
+    __shared__ unsigned long long lh[kHistSlots * (kHistMaxEdges + 1)];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    const int B1 = B + 1;
+    cross_ranges_gi(N, u0, gp, G, peer, rlo, rhi, rgi);    // rgi: a row of hist
+    for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
+    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) lh[i] = 0ull;
+    __syncthreads();
+    cross_spans(rlo, rhi, ta, tb, &ns);
+    __syncthreads();
+    const int64_t row0 = u0 + 16 * w;
+    const int64_t left = N - 1 - u0;                       // u0 < N: the tile's last row inside N
+    const int gfirst = rgi[0], glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
+    const int spans = ns, no = 0;
+    int mylo[4], myhi[4], mygi[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int lr = 16 * w + 4 * q + g;
+        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; mygi[g] = rgi[lr];
+    }
+    // the lane's run: run_n candidates of bin run_bin of graph run_gi that no atomic has seen yet
+    int run_gi = 0, run_bin = 0, run_n = 0;
+    auto flush = [&]() {
+        if (run_n > 0) {
+            if (run_gi == gfirst) atomicAdd(&lh[run_bin], (unsigned long long)run_n);
+            else if (run_gi == glast) atomicAdd(&lh[B1 + run_bin], (unsigned long long)run_n);
+            else atomicAdd(&hist[(int64_t)run_gi * B1 + run_bin], (unsigned long long)run_n);
+        }
+    };
+    float a[H / 4];
+    load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
+    for (int sp = 0; sp < spans; ++sp) {
+        const int64_t ct0 = ta[sp], ct1 = tb[sp];
+        float4 nxt[H / 16];
+        tile_load<H>(nxt, y, ldy, ct0 * kPairTile, N);
+        for (int64_t ct = ct0; ct < ct1; ++ct) {
+            __syncthreads();
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+            __syncthreads();
+            if (ct + 1 < ct1) tile_load<H>(nxt, y, ldy, (ct + 1) * kPairTile, N);
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {                      // row by row: a run lasts as long as the row's scores stay in one bin
+                bool valid[4], any = false;
+                float rep[4];
+                int pos[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    valid[c] = candidate<false>(acc[c][g], ct * kPairTile + 16 * c + r, row0 + 4 * q + g, mylo[g], myhi[g], no, no, rep[c]);
+                    any = any || valid[c];
+                    pos[c] = 0;
+                }
+                if (__ballot(any) == 0ull) continue;           // the wave has no candidate in these rows of this tile
+                for (int step = top; step > 0; step >>= 1) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (!valid[c]) continue;
+                    const int bin = pos[c] < B ? pos[c] : B;   // an ascending table never gives more; nothing else is indexed
+                    if (run_n > 0 && run_gi == mygi[g] && run_bin == bin) { ++run_n; continue; }
+                    flush();
+                    run_gi = mygi[g]; run_bin = bin; run_n = 1;
+                }
+            }
+        }
+    }
+    flush();
+    __syncthreads();
+    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) {
+        const unsigned long long n = lh[i];
+        if (n != 0ull) atomicAdd(&hist[(int64_t)(i < B1 ? gfirst : glast) * B1 + (i < B1 ? i : i - B1)], n);
+    }
+}
+
 // ---------------------------------------------------------------------------------- unit rows
 // y[i] = x[i] / max(|x[i]|, eps), the per-row clamp of torch.cosine_similarity (trainer.py:158-160) and of k_func_dist.  H / 4 lanes per
 // row, one float4 each; the sum of squares meets in the row's lanes in float32.  A NaN norm is kept (NaN < eps is false): the whole
@@ -1206,6 +1387,38 @@ extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const in
     });
 }
 
+extern "C" int mgv_cross_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
+                               float threshold, int32_t* parent, int32_t* status, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    if (rc != MGV_OK) return rc;
+    MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
+    if (!launch) return MGV_OK;
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_cross_union<w>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, parent, status);
+    });
+}
+
+// the table of a profile entry (1 <= B <= kHistMaxEdges, edges not NULL) must ascend strictly and hold no NaN: it is read back, like the
+// two ends of graph_ptr (one small blocking copy)
+static int hist_edges_check(const float* edges, int B, hipStream_t st) {
+    float e[mgv::kHistMaxEdges];
+    hipError_t err = hipMemcpyAsync(e, edges, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return (int)err;
+    MGV_CHECK_ARG(e[0] == e[0]);
+    for (int j = 1; j < B; ++j) MGV_CHECK_ARG(e[j] > e[j - 1]);           // false for a NaN on either side
+    return MGV_OK;
+}
+
+// half the first power of two above B: the first step of the kernels' binary search
+static int hist_top(int B) {
+    int top = 1;
+    while (2 * top <= B) top *= 2;
+    return top;
+}
+
 // the two profile entries: checks in the order of the selection entries, then the table; *launch = false: hist is zero and nothing is left to do
 static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
                          int skip_self, bool sym, const float* edges, int B, int64_t* hist, hipStream_t st) {
@@ -1214,19 +1427,13 @@ static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float*
     bool launch;
     const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
     if (rc != MGV_OK) return rc;
-    // the table must ascend strictly and hold no NaN: it is read back, like the two ends of graph_ptr (one small blocking copy)
-    float e[mgv::kHistMaxEdges];
-    hipError_t err = hipMemcpyAsync(e, edges, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) return (int)err;
-    MGV_CHECK_ARG(e[0] == e[0]);
-    for (int j = 1; j < B; ++j) MGV_CHECK_ARG(e[j] > e[j - 1]);           // false for a NaN on either side
+    const int ok = hist_edges_check(edges, B, st);
+    if (ok != MGV_OK) return ok;
     const int64_t rows = G > 1 ? G : 1;
-    err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)rows * (size_t)(B + 1), st);
+    hipError_t err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)rows * (size_t)(B + 1), st);
     if (err != hipSuccess) return (int)err;
     if (!launch) return MGV_OK;
-    int top = 1;                                                          // half the first power of two above B
-    while (2 * top <= B) top *= 2;
+    const int top = hist_top(B);
     unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
     return launch_width(mgv::AllWidths{}, H, [&](auto w) {
         auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_hist<w, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, edges, B, top, h); };
@@ -1242,6 +1449,29 @@ extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const fl
 extern "C" int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B,
                             int64_t* hist, void* stream) {
     return pair_hist_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, 0, true, edges, B, hist, (hipStream_t)stream);
+}
+
+// the cross profile: the checks of the profile entries for edges, B and hist, those of the cross entries for the rest
+extern "C" int mgv_cross_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
+                              const float* edges, int B, int64_t* hist, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(B >= 1 && B <= mgv::kHistMaxEdges && edges != nullptr && hist != nullptr);
+    bool launch;
+    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    if (rc != MGV_OK) return rc;
+    const int ok = hist_edges_check(edges, B, st);
+    if (ok != MGV_OK) return ok;
+    if (G > 0) {
+        hipError_t err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)G * (size_t)(B + 1), st);
+        if (err != hipSuccess) return (int)err;
+    }
+    if (!launch) return MGV_OK;
+    const int top = hist_top(B);
+    unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_cross_hist<w>, N, st, N, y, ldy, graph_ptr, G, peer, edges, B, top, h);
+    });
 }
 
 extern "C" int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,

@@ -247,14 +247,34 @@ class FunctionalModel(nn.Module):
             return pi, None, (cos if with_scores else None)
         return similarity.cross_pairs(hf, graph_ptr, peer, threshold=threshold, with_scores=with_scores, max_pairs=max_pairs)
 
-    def cross_equivalence_classes(self, hf, graph_ptr, peer, threshold=0.999, min_size=2):
+    def cross_equivalence_classes(self, hf, graph_ptr, peer, threshold=0.999, min_size=2, route='pairs'):
         """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]) as equivalence_classes returns them, but the classes may span
         a circuit and its peer: the connected components of "cosine of hf > threshold" over the pairs of
         cross_equivalence_candidates together with those of equivalence_candidates (ops.cross_classes; peer as in match_gates).  A
         class that holds gates of both circuits is a set of candidate equivalence points a checker can merge.  Added functionality
         (trainer.py:158-160).  Single linkage; primary inputs (hf = 0) and rows with a NaN are always singletons; circuits share a
-        class only through peer links; use 0.999 rather than 1.0."""
-        return similarity.cross_classes(hf, graph_ptr, peer, threshold=threshold, min_size=min_size)
+        class only through peer links; use 0.999 rather than 1.0.  route='pairs' builds both pair lists first and can refuse for
+        their size; route='walk' unites the pairs where the two tile walks find them, in O(N) memory, and gives the same classes."""
+        return similarity.cross_classes(hf, graph_ptr, peer, threshold=threshold, min_size=min_size, route=route)
+
+    def cross_similarity_profile(self, hf, thresholds, graph_ptr, peer):
+        """int64 [G, B] on the device: per graph g, the number of (gate of g, gate of graph peer[g]) pairs whose cosine of hf is > each
+        of `thresholds` (strictly ascending, at most 256) — what cross_equivalence_candidates would list for g's gates at each of
+        them, as integers, from ONE walk (ops.counts_above of ops.cross_profile; peer as in match_gates).  With an involutive peer a
+        pair counts once in each of the two circuits' rows.  Added functionality (trainer.py:158-160): the distribution by which a
+        threshold for matching a golden design against its revision is chosen instead of guessed.  Rows with hf = 0 score 0 with
+        everything; equal rows score within (2H + 6) 2^-24 of 1, not exactly 1."""
+        return pairs.counts_above(similarity.cross_profile(hf, thresholds, graph_ptr, peer))
+
+    def cross_equivalence_threshold(self, hf, max_pairs, graph_ptr, peer, lo=0.0):
+        """{'threshold', 'pairs', 'lower', 'pairs_lower', 'tight'}: the lowest cosine threshold above `lo` at which
+        cross_equivalence_candidates lists at most `max_pairs` pairs for the whole batch, and exactly `pairs` of them
+        (ops.cross_threshold_for: a few profile walks in place of a bisection of count walks; peer as in match_gates).  Pairs are
+        counted as cross_equivalence_candidates lists them: with an involutive peer once from each side.  When `lower` is not None,
+        cross_equivalence_candidates(threshold=lower, max_pairs=max_pairs) is refused: pairs_lower > max_pairs.  Added functionality
+        (trainer.py:158-160).  Ties are the caller's to understand, as for equivalence_threshold: equal gates share ONE cosine value,
+        which a threshold takes or leaves as a whole, so `pairs` can lie far below max_pairs."""
+        return similarity.cross_threshold_for(hf, max_pairs, graph_ptr, peer, lo=lo)
 
     def similarity_profile(self, hf, thresholds, graph_ptr=None):
         """int64 [G, B] on the device: per graph, the number of unordered gate pairs whose cosine of hf is > each of `thresholds`

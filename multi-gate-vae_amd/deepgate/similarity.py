@@ -398,16 +398,78 @@ def cross_mutual(x, graph_ptr, peer, threshold=SIM_THRESHOLD, eps=1e-8):
         return torch.stack([u[keep], v[keep]]), cos[keep, 0]
 
 
-def cross_classes(x, graph_ptr, peer, threshold=SIM_THRESHOLD, min_size=2, max_pairs=None, eps=1e-8):
+def cross_classes(x, graph_ptr, peer, threshold=SIM_THRESHOLD, min_size=2, max_pairs=None, eps=1e-8, route='pairs'):
     """(label int32 [N], class_ptr int64 [C + 1], members int32 [M]) as sim_classes returns them: the connected components of
     "cosine > threshold" over the cross pairs (cross_pairs) TOGETHER WITH the within-circuit pairs (sim_pairs), so a class may now
     span a graph and its peer — and nothing else: two graphs share a class only through a chain of peer links (several graphs that
-    name one peer can meet in it).  Single linkage, as sim_classes.  components and class_table on the two lists; each list keeps its
-    refusals (max_pairs applies to each, free memory).  No grad."""
+    name one peer can meet in it).  Single linkage, as sim_classes.
+    route='pairs' (the default): components and class_table on the two lists; each list keeps its refusals (max_pairs applies to
+    each, free memory).
+    route='walk': one forest, on which the symmetric walk of sim_pairs (mgv_sim_union) and then the cross walk of cross_pairs
+    (mgv_cross_union) unite each pair where they find it.  No pair list ever exists: memory is O(N) and nothing is refused for size —
+    a revision that keeps 5,000 equal gates of its golden design is 25 M cross pairs (50 M with an involutive peer) but one class of
+    10,000.  max_pairs belongs to route='pairs'.  One read-back (the table's two sizes and the union-find's status record) besides
+    graph_ptr's two ends and peer, which the launchers check.
+    Both routes give the same three tensors, exactly, and the same bits from run to run.  No grad."""
+    if route not in ('walk', 'pairs'):
+        raise HipLibraryError("cross_classes: route must be 'pairs' (cross_pairs and sim_pairs, then components) or 'walk' (classes "
+                              "straight from the two tile walks), got %r" % (route,))
     min_size = _min_size(min_size)
+    if route == 'walk' and max_pairs is not None:
+        raise HipLibraryError("cross_classes: max_pairs belongs to route='pairs'; the walk holds no pair list")
     gph, ph = _peer_table(peer, graph_ptr, 'cross_classes')
+    if route == 'walk':
+        y = row_unit(x, eps)
+        with torch.no_grad():
+            N, H = y.shape
+            dev = y.device
+            gp, pr, G = gph.to(dev), ph.to(dev), ph.numel()
+            parent, status = _cc_forest(N, dev)
+            _hip.call('mgv_sim_union', H, N, ptr(y), H, ptr(gp), G, float(threshold), ptr(parent), ptr(status))
+            _hip.call('mgv_cross_union', H, N, ptr(y), H, ptr(gp), G, ptr(pr), float(threshold), ptr(parent), ptr(status))
+            label = _cc_labels(N, parent)
+            return (label,) + _class_table(label, min_size, status, 'cross_classes')
     cross, _, _ = cross_pairs(x, gph, ph, threshold=threshold, max_pairs=max_pairs, eps=eps)
     own, _, _ = sim_pairs(x, graph_ptr=gph, threshold=threshold, max_pairs=max_pairs, eps=eps)
     with torch.no_grad():
         label, status = _cc_from_pairs(torch.cat([cross, own], dim=1), x.shape[0])
         return (label,) + _class_table(label, min_size, status, 'cross_classes')
+
+
+# the distribution of cross cosines (mgv_cross_hist) and the threshold search on it
+def _cross_unit_profile(y, e, gp, pr):
+    """mgv_cross_hist on unit rows y, a device table e and the device tables gp [G + 1], pr [G] -> int64 [G, B + 1]."""
+    N, H = y.shape
+    G = pr.numel()
+    hist = torch.empty((max(G, 1), e.numel() + 1), dtype=torch.int64, device=y.device)      # never a NULL pointer
+    _hip.call('mgv_cross_hist', H, N, ptr(y), H, ptr(gp), G, ptr(pr), ptr(e), e.numel(), ptr(hist))
+    return hist[:G]
+
+
+def cross_profile(x, edges, graph_ptr, peer, eps=1e-8):
+    """int64 [G, B + 1]: sim_profile's bins for the cosines of cross_pairs — unit rows (row_unit), every (row u of graph g, row v of
+    graph peer[g]), binned by the number of `edges` (strictly ascending, at most 256) the cosine is above, in row g (mgv_cross_hist:
+    ONE walk for all edges).  counts_above(profile)[g, j] is the number of pairs cross_pairs lists for the rows of graph g at
+    threshold edges[j], as integers; with an involutive peer a pair is counted once from each side, in g's row and in its peer's.
+    A graph with peer = -1 or without rows has a zero row; a NaN is counted nowhere.  No grad."""
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_profile')
+    _pair_width(x, 'cross_profile')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        return _cross_unit_profile(y, _profile_edges(edges, y.device), gph.to(y.device), ph.to(y.device))
+
+
+def cross_threshold_for(x, max_pairs, graph_ptr, peer, lo=0.0, bins=64, max_rounds=6, eps=1e-8):
+    """sim_threshold_for across circuits: the lowest cosine threshold whose batch-wide count of cross pairs fits `max_pairs`, from the
+    distribution (cross_profile walks) instead of trial count walks -> the dict of sim_threshold_for, {'threshold', 'pairs', 'lower',
+    'pairs_lower', 'tight'}.  "Pairs" are the entries of cross_pairs' lists, summed over all rows: pairs is exactly
+    cross_pairs(threshold=result['threshold'])[0].shape[1], so with an involutive peer a pair counts ONCE FROM EACH SIDE (twice), and
+    a self-peer counts (u, v), (v, u) and (u, u).  The bracket, the rounds, `tight` and what ties do are threshold_search's and
+    sim_threshold_for's: one walk and one read-back per round.  No grad."""
+    gph, ph = _peer_table(peer, graph_ptr, 'cross_threshold_for')
+    _pair_width(x, 'cross_threshold_for')
+    y = row_unit(x, eps)
+    with torch.no_grad():
+        gp, pr = gph.to(y.device), ph.to(y.device)
+        return threshold_search(lambda e: _cross_unit_profile(y, _profile_edges(e, y.device), gp, pr), max_pairs, lo=lo, hi=2.0, bins=bins,
+                                max_rounds=max_rounds)

@@ -11,7 +11,9 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --equivalences 0.999   # + the gate pairs with cos(hf) above 0.999
     python examples/feature_extract.py --type aig --synthetic 4 --match 8           # + every gate's 8 closest gates in the NEXT/PREVIOUS graph
     python examples/feature_extract.py --type aig --synthetic 4 --cross_equivalences 0.999   # + the gate pairs ACROSS graphs 2i, 2i + 1
-    python examples/feature_extract.py --type aig --synthetic 4 --equivalences_max 1000   # the same, at most 1000 pairs per batch
+    python examples/feature_extract.py --type aig --synthetic 4 --cross_equivalences_max 1000   # the same, at most 1000 pairs per batch
+    python examples/feature_extract.py --type aig --synthetic 4 --cross_classes 0.999   # + the classes that may span graphs 2i, 2i + 1
+    python examples/feature_extract.py --type aig --synthetic 4 --equivalences_max 1000   # --equivalences, at most 1000 pairs per batch
     python examples/feature_extract.py --type aig --synthetic 4 --similarity_profile 12   # + pairs per graph above 1 - 2^-j, j = 1..12
     python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
     python examples/feature_extract.py --type aig --synthetic 4 --link_ranking 1,10    # + exact MRR / Hits@1 / Hits@10 of the true fan-ins
@@ -65,6 +67,16 @@ def main(argv=None):
                     'equivalence points between two circuits (name/xeq_pairs [2, P]: row 0 local to the graph, row 1 local to its '
                     'peer, listed per gate in ascending order; name/xeq_cos; Model.cross_equivalence_candidates).  A pair appears in '
                     'both graphs\' lists; use 0.999 rather than 1.0')
+    ap.add_argument('--cross_equivalences_max', type=int, default=None, metavar='P', help='choose the threshold of --cross_equivalences by '
+                    'count: the lowest one (not below --cross_equivalences when that is given too, else 0) at which a batch lists at most '
+                    'P cross pairs, a pair counted once from each side as the lists hold it (Model.cross_equivalence_threshold), then '
+                    'store the pairs as --cross_equivalences does and the threshold used (name/xeq_threshold)')
+    ap.add_argument('--cross_classes', type=float, default=None, metavar='THR', help='with the pairing of --match, also store the candidate '
+                    'classes that may span a graph and its peer: the connected components of "cos(hf) above THR" over the pairs inside '
+                    'each graph and across each couple, straight from the tile walks without a pair list '
+                    '(Model.cross_equivalence_classes(route=\'walk\')): name/xcl_label [n], the smallest id of a gate\'s class, local to '
+                    'the couple (2i, 2i + 1) laid end to end — a label below the size of graph 2i is a gate of graph 2i — and the '
+                    'number of classes that hold gates of both graphs is printed')
     ap.add_argument('--classes', type=float, default=None, metavar='THR', help='also store every graph\'s equivalence candidate classes, '
                     'what a SAT sweeper consumes: the connected components of "cos(hf) above THR" (name/eq_label [n], the smallest local '
                     'id of a gate\'s class; name/eq_class_ptr [C + 1] and name/eq_members [M], the classes with at least two gates, '
@@ -130,18 +142,28 @@ def main(argv=None):
             if a.similar:
                 sim_idx, sim_cos, _ = model.similar_gates(hf, a.similar, graph_ptr=batch.graph_ptr)
                 sim_idx, sim_cos = sim_idx.cpu().numpy(), sim_cos.cpu().numpy()
-            if a.match or a.cross_equivalences is not None:
+            xeq_thr = a.cross_equivalences
+            if a.match or xeq_thr is not None or a.cross_equivalences_max is not None or a.cross_classes is not None:
                 G = len(chunk)
                 peer = [g ^ 1 if (g ^ 1) < G else -1 for g in range(G)]          # (2i, 2i + 1); an odd last graph has no peer
                 pbase = [ptr[q] if q >= 0 else 0 for q in peer]
             if a.match:
                 m_idx, m_cos, _ = model.match_gates(hf, a.match, batch.graph_ptr, peer)
                 m_idx, m_cos = m_idx.cpu().numpy(), m_cos.cpu().numpy()
-            if a.cross_equivalences is not None:
-                xeq, xeq_ptr, xeq_cos = model.cross_equivalence_candidates(hf, batch.graph_ptr, peer, threshold=a.cross_equivalences,
-                                                                           with_scores=True)
+            if a.cross_equivalences_max is not None:
+                xeq_thr = model.cross_equivalence_threshold(hf, a.cross_equivalences_max, batch.graph_ptr, peer,
+                                                            lo=0.0 if xeq_thr is None else xeq_thr)['threshold']
+            if xeq_thr is not None:
+                xeq, xeq_ptr, xeq_cos = model.cross_equivalence_candidates(hf, batch.graph_ptr, peer, threshold=xeq_thr, with_scores=True)
                 xeq, xeq_cos = xeq.cpu().numpy(), xeq_cos.cpu().numpy()
                 xptr = xeq_ptr[batch.graph_ptr.to(xeq_ptr.device).long()].tolist()             # the graphs' places in the list
+            if a.cross_classes is not None:
+                xcl_label, xcl_ptr, xcl_mem = (x.cpu().numpy() for x in model.cross_equivalence_classes(
+                    hf, batch.graph_ptr, peer, threshold=a.cross_classes, route='walk'))
+                # members ascend inside a class: its first and last member lie in its lowest and highest graph
+                g_lo = np.searchsorted(ptr[1:], xcl_mem[xcl_ptr[:-1]], side='right')
+                g_hi = np.searchsorted(ptr[1:], xcl_mem[xcl_ptr[1:] - 1], side='right')
+                xcl_span = np.bincount(g_lo[g_lo != g_hi], minlength=G)                        # counted at the lower graph of a couple
             eq_thr = a.equivalences
             if a.equivalences_max is not None:
                 eq_thr = model.equivalence_threshold(hf, a.equivalences_max, graph_ptr=batch.graph_ptr,
@@ -191,12 +213,20 @@ def main(argv=None):
                     loc = m_idx[ptr[k]:ptr[k + 1]]
                     out[name + '/match_idx'] = np.where(loc >= 0, loc - pbase[k], -1).astype(np.int32)
                     out[name + '/match_cos'] = m_cos[ptr[k]:ptr[k + 1]]
-                if a.cross_equivalences is not None:
+                if xeq_thr is not None:
                     pr = xeq[:, xptr[k]:xptr[k + 1]]
                     out[name + '/xeq_pairs'] = np.stack([pr[0] - ptr[k], pr[1] - pbase[k]]).astype(np.int32)
                     out[name + '/xeq_cos'] = xeq_cos[xptr[k]:xptr[k + 1]]
-                    print('[INFO] %s: %d gate pairs with %s at cos(hf) > %g' % (name, xptr[k + 1] - xptr[k], 'graph %d' % (b0 + peer[k])
-                                                                              if peer[k] >= 0 else 'no peer', a.cross_equivalences))
+                    print('[INFO] %s: %d gate pairs with %s at cos(hf) > %s' % (name, xptr[k + 1] - xptr[k], 'graph %d' % (b0 + peer[k])
+                                                                              if peer[k] >= 0 else 'no peer',
+                                                                              ('%g' if a.cross_equivalences_max is None else '%.9g') % xeq_thr))
+                if a.cross_equivalences_max is not None:
+                    out[name + '/xeq_threshold'] = np.float32(xeq_thr)
+                if a.cross_classes is not None:
+                    out[name + '/xcl_label'] = (xcl_label[ptr[k]:ptr[k + 1]] - ptr[k & ~1]).astype(np.int32)
+                    if peer[k] > k:
+                        print('[INFO] %s: %d classes hold gates of it and of graph %d at cos(hf) > %g'
+                              % (name, int(xcl_span[k]), b0 + peer[k], a.cross_classes))
                 if eq_thr is not None:
                     out[name + '/eq_pairs'] = (eq[:, qptr[k]:qptr[k + 1]] - ptr[k]).astype(np.int32)
                     out[name + '/eq_cos'] = eq_cos[qptr[k]:qptr[k + 1]]
