@@ -725,6 +725,33 @@ int mgv_reparam_fwd(int64_t n, const float* mu, const float* logstd, const float
 /* dmu = gz + *gkl*klcoef*(-2mu); dlogstd = gz*eps*exp(logstd) + *gkl*klcoef*(2-2exp(2logstd)); gz/gkl may be NULL */
 int mgv_reparam_bwd(int64_t n, const float* mu, const float* logstd, const float* eps, const float* gz,
                     const float* gkl, float klcoef, float* dmu, float* dlogstd, void* stream);
+/* ---- the variational link heads in one pass over st = hs_decompose(hs) (digvae_model.py:134-142, trainer.py:145-148; bf16x3,
+ * csrc/var_head_x3.hip).  ST [N][ldst >= 2H] = [X_s | X_t].  Per half h: P_h = X_h Wp_h^T + bp_h with Wp_h [2H][H] = fc_h_mu.weight
+ * over fc_h_logstd.weight (wpack_h = mgv_wpack_bf16x3(Wp_h, 2H, H, H, 0), bp_h [2H] likewise), the product as mgv_linear_fwd_x3 forms
+ * it at (2H, H); mu = P[:, :H], ls = P[:, H:].  eps [N][ldeps >= 2H] = [eps_s | eps_t], or NULL: element (r, c) of half h is the
+ * generator of mgv_reparam_fwd at element r*H + c of seed + h.  Z [N][ldz >= 2H]: Z[r][hH + c] = mu + expf(ls) eps (sample = 1) or mu
+ * (sample = 0); ls is not clamped.  ML (nullable) [N][ldml >= 4H] = [mu_s | ls_s | mu_t | ls_t].  klsum double[2] is OVERWRITTEN with
+ * sum(1 + 2 ls - mu^2 - expf(ls)^2) per half: float32 terms widened at the first addition, per-workgroup sums in rows of `workspace`
+ * added in index order — no floating-point atomic, the same bytes from call to call.  workspace: 8-byte aligned, at least
+ * mgv_var_head_x3_ws_floats(H, N, 0) floats.
+ * Refusals in this order, each before anything is launched or written: H outside {32, 64} MGV_EUNSUPPORTED; N < 0 or a NULL ST, pack,
+ * bias, Z, klsum or workspace MGV_EINVAL; a stride below its width or no multiple of 4, or sample outside {0, 1} MGV_EINVAL; a
+ * misaligned or short workspace MGV_EINVAL; then N = 0 returns MGV_OK with nothing launched (klsum untouched). */
+int mgv_var_head_x3_ws_floats(int H, int64_t N, int backward);                                      /* a size; 0 for a width not served */
+int mgv_var_head_fwd_x3(int H, int64_t N, const float* ST, int ldst, const void* wpack_s, const void* wpack_t, const float* b_s,
+                        const float* b_t, const float* eps, int ldeps, uint64_t seed, int sample, float* Z, int ldz, float* ML,
+                        int ldml, double* klsum, float* workspace, int64_t workspace_floats, void* stream);
+/* its whole backward, from ST and the seed alone: P (and eps where it was generated) are recomputed exactly as the forward formed
+ * them; with gz = the half's columns of gZ [N][ldg >= 2H] (NULL: zero) and gkl float[2] on the device (NULL: zero), the upstream
+ * gradient of each half's sum:  dmu = gz + gkl[h] (-2 mu);  dls = (sample ? gz eps expf(ls) : 0) + gkl[h] (2 - 2 expf(ls)^2);
+ * dWp_h [2H][H] += dP^T X_h and dbp_h [2H] += colsum(dP) with dP = [dmu | dls] — both ACCUMULATE, deterministic through workspace rows
+ * and a fixed-order second launch as mgv_linear_wgrad_x3 — and dST[r][hH .. (h+1)H) = dP_h Wp_h (WRITTEN, lddst >= 2H) in the same pass.
+ * wtpack_h = mgv_wpack_bf16x3(Wp_h, H, 2H, H, 1).  workspace: at least mgv_var_head_x3_ws_floats(H, N, 1) floats.  Refusals as the
+ * forward's, in its order (NULL dST / dWp / dbp / transposed pack with the other NULLs); N = 0 returns MGV_OK with nothing launched. */
+int mgv_var_head_bwd_x3(int H, int64_t N, const float* ST, int ldst, const void* wpack_s, const void* wpack_t,
+                        const void* wtpack_s, const void* wtpack_t, const float* b_s, const float* b_t, const float* eps, int ldeps,
+                        uint64_t seed, int sample, const float* gZ, int ldg, const float* gkl, float* dST, int lddst, float* dWp_s,
+                        float* dWp_t, float* dbp_s, float* dbp_t, float* workspace, int64_t workspace_floats, void* stream);
 /* counts += {TP,FP,TN,FN} of pred_bin vs gt_bin (trainer.py:240-244) */
 int mgv_confusion(int64_t n, const int32_t* pred_bin, const int32_t* gt_bin, uint64_t* counts, void* stream);
 

@@ -48,4 +48,9 @@ def get_parse_args(argv=None):
     parser.add_argument('--neg_reverse', type=float, default=0.0, metavar='FRAC', help='share in [0, 1] of the negative edges that are '
                         'reversals (v, u) of true links (u, v), the hard negatives of the directed decoder; 0 = the draw of '
                         'dg_ae_model_aig.py:115-119')
+    parser.add_argument('--variational', action='store_true', help='with --model DG_AE or AE: train the model as a variational '
+                        'auto-encoder — the four heads fc_{s,t}_{mu,logstd} on the decoder\'s embeddings, the decoder on the sampled z '
+                        '(digvae_model.py:134-142), the KL term logged as |KL (trainer.py:145-148)')
+    parser.add_argument('--kl_weight', type=float, default=0.0, metavar='BETA', help='weight of the KL term in the step\'s loss; 0 = the '
+                        'reference, which computes it and never adds it (trainer.py:145-148)')
     return parser.parse_args(argv)

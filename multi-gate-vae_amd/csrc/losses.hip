@@ -5,6 +5,7 @@
 // confusion counters and the KL sum leave as one atomic per block.
 #include "mgv_launch.h"
 #include "mgv_slab.h"
+#include "mgv_gauss.h"
 #include "../../include/mgvae_hip.h"
 
 namespace mgv {
@@ -485,17 +486,7 @@ __global__ __launch_bounds__(kThreads) void k_func_bwd_pull(int64_t N, int64_t P
     }
 }
 
-// ---------------------------------------------------------------------------------- sampler + KL
-__device__ __forceinline__ uint32_t mix32(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return (uint32_t)x;
-}
-__device__ __forceinline__ float gauss_from_counter(uint64_t seed, uint64_t i) {
-    const uint32_t a = mix32(seed * 0x9E3779B97F4A7C15ULL + 2 * i), b = mix32(seed * 0x9E3779B97F4A7C15ULL + 2 * i + 1);
-    const float u1 = ((a >> 8) + 1.0f) * (1.0f / 16777216.0f), u2 = (b >> 8) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * __cosf(6.283185307179586f * u2);
-}
-
+// ---------------------------------------------------------------------------------- sampler + KL (gauss_from_counter: mgv_gauss.h)
 // z = mu + exp(logstd) * eps;  klsum += sum(1 + 2 logstd - mu^2 - exp(logstd)^2)
 __global__ __launch_bounds__(kThreads) void k_reparam_fwd(int64_t n, const float* mu, const float* ls, const float* eps,
                                                           uint64_t seed, float* eps_out, float* z, double* klsum) {

@@ -24,7 +24,9 @@ class FunctionalModel(nn.Module):
     ENCODER_ATTR = 'struct_encoder'
     GATES = ()            # ((name, gate id), ...) in the order the reference creates aggr_*/update_* modules
 
-    def __init__(self, struct_encoder, num_rounds=1, dim_hidden=128, enable_encode=True, enable_reverse=True):
+    VAR_HEADS = ('fc_s_mu', 'fc_s_logstd', 'fc_t_mu', 'fc_t_logstd')      # DirectedGVAE's names (digvae_model.py:112-115)
+
+    def __init__(self, struct_encoder, num_rounds=1, dim_hidden=128, enable_encode=True, enable_reverse=True, variational=False):
         super().__init__()
         setattr(self, self.ENCODER_ATTR, struct_encoder)
         self.decoder = DirectedInnerProductDecoder()
@@ -41,6 +43,13 @@ class FunctionalModel(nn.Module):
             setattr(self, 'update_%s_func' % name, nn.GRU(dim_hidden, dim_hidden))
         self.readout_prob = MLP(dim_hidden, self.dim_mlp, 1, num_layer=3, p_drop=0.2, norm_layer='batchnorm',
                                 act_layer='relu')
+        # variational link heads on st = hs_decompose(hs) (added functionality: the reference's DG_VAE path never ran, SURVEY.md
+        # §3.4).  Registered AFTER the reference's modules, so their seeded values and state_dict keys do not move.
+        self.variational = bool(variational)
+        if self.variational:
+            for name in self.VAR_HEADS:
+                setattr(self, name, nn.Linear(dim_hidden, dim_hidden))
+        self._klsum, self._kl_n = None, 0                      # the last recon_loss's two KL sums (device) and its node count
         self.last_confusion = None
         self.last_link_metrics = None
         self._neg_scope, self._neg_reverse = 'batch', 0.0      # set_negative_sampling
@@ -129,7 +138,10 @@ class FunctionalModel(nn.Module):
         device record of ops.link_record (float64[8]: AUC, AP, then the integer words) without a host synchronisation; `.tolist()`
         or ops.read_link_records is the caller's."""
         with torch.no_grad():
-            st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
+            if self.variational:
+                st = torch.cat(self._decoder_halves(hs), dim=1)          # the posterior means
+            else:
+                st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
             if plan is not None and (plan.E != pos_edge_index.shape[1] or plan.N != hs.shape[0]):
                 plan = None
             if neg_edge_index is None:
@@ -137,10 +149,35 @@ class FunctionalModel(nn.Module):
             return metrics.link_record(st, None, pos_edge_index, neg_edge_index)
 
     def _decoder_halves(self, hs):
-        """(s, t): the two column halves of st = hs_decompose(hs), as views (the pair kernels take a row stride)."""
+        """(s, t): the two column halves of st = hs_decompose(hs), as views (the pair kernels take a row stride); of a variational
+        model the posterior means (mu_s, mu_t) of those halves."""
+        if self.variational:
+            mu_s, _, mu_t, _ = self.latent(hs)
+            return mu_s, mu_t
         st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
         H = st.shape[1] // 2
         return st[:, :H], st[:, H:]
+
+    # ---- variational link heads ----------------------------------------------------------------------
+    def _var_heads(self):
+        return tuple(p for name in self.VAR_HEADS for p in (getattr(self, name).weight, getattr(self, name).bias))
+
+    def latent(self, hs):
+        """(mu_s, logstd_s, mu_t, logstd_t) [N, H] each, of a variational model: the four heads on st = hs_decompose(hs), without
+        gradients (column views of one array on the fused route)."""
+        if not self.variational:
+            raise ValueError('latent() needs Model(variational=True)')
+        with torch.no_grad():
+            st = ops.linear(hs.detach(), self.hs_decompose.weight, self.hs_decompose.bias)
+            return ops.var_head_latent(st, self._var_heads())
+
+    def kl_loss(self):
+        """(s_kl, t_kl) of the last recon_loss exactly as trainer.py:146-147 writes them: -0.5/N * mean_i sum_d(1 + 2 logstd - mu^2 -
+        exp(logstd)^2), i.e. -0.5 / N^2 times each half's sum (the double 1/N is the reference's)."""
+        if self._klsum is None:
+            raise ValueError('kl_loss() follows recon_loss() of a variational model')
+        c = -0.5 / self._kl_n / self._kl_n
+        return c * self._klsum[0], c * self._klsum[1]
 
     def predict_links(self, hs, k, graph_ptr=None, skip_self=True):
         """(idx [N, k] int32, score [N, k], n_above [N] int32) on st = hs_decompose(hs): every gate's k most probable fan-out targets
@@ -311,19 +348,29 @@ class FunctionalModel(nn.Module):
         return metrics.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
 
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, want_rank=False,
-                   expect_scale=1.0, graph_ptr=None, return_hs=False):
+                   expect_scale=1.0, graph_ptr=None, return_hs=False, sample=None, seed=None, eps=None):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `return_hs`: a fourth result, hs passed through the
         hs_decompose node (ops.linear_passthrough; hs itself when it needs no gradient): a second consumer of hs that reads THAT
         tensor has its gradient added inside the Linear's input-gradient kernel.  `want_rank`: also rank the very pairs the loss
         uses (same st, same sampled negatives) and leave the ops.link_record tensor in `self.last_link_metrics`.  `expect_scale`: the
         upstream gradient this loss will meet in backward (its weight in the step's total), see ops.ReconLossFn.  `graph_ptr`: the
-        batch's host graph table, read when negatives are drawn under set_negative_sampling(scope='graph')."""
+        batch's host graph table, read when negatives are drawn under set_negative_sampling(scope='graph').
+        Variational model: the decoder reads z = VarHead(st) where it reads st otherwise, and the KL sums are kept for kl_loss().
+        `sample`: add the noise (None: self.training, the VGAE convention; the reference's `sample` adds it in eval mode as well,
+        DESIGN.md §7); `seed` fixes it (tests; by default one is drawn from torch's CPU generator, as pred_prob's); `eps` [N, 2H]
+        injects it."""
         hs_pass = hs
         if return_hs and hs.requires_grad:
             st, hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         else:
             st = ops.linear(hs, self.hs_decompose.weight, self.hs_decompose.bias)
+        if self.variational:
+            sample = self.training if sample is None else bool(sample)
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if sample and eps is None else 0
+            st, self._klsum = ops.var_head(st, self._var_heads(), eps=eps, seed=seed, sample=sample)
+            self._kl_n = hs.shape[0]
         if plan is not None and (plan.E != pos_edge_index.shape[1] or plan.N != hs.shape[0]):
             plan = None
         neg_csr = None

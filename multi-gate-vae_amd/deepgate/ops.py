@@ -1287,6 +1287,115 @@ class ReparamFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# variational link heads on st = hs_decompose(hs): fc_{s,t}_{mu,logstd}, the sample and the KL sums (digvae_model.py:134-142,
+# trainer.py:145-148) — one launch forward, one backward (csrc/var_head_x3.hip), or composed from linear + ReparamFn
+# ------------------------------------------------------------------------------------------------
+# MGV_VAR_HEAD_FUSED=0 forces the composed route for a same-process A/B: tests flip this flag
+VAR_HEAD_FUSED = os.environ.get('MGV_VAR_HEAD_FUSED', '1') != '0'
+
+
+def _var_head_ws(H, N, backward, device):
+    return workspace(_hip.call_value('mgv_var_head_x3_ws_floats', H, N, int(backward)), device)
+
+
+def _var_head_packs(heads):
+    """Per half: Wp [2H, H] = fc_mu.weight over fc_logstd.weight, bp [2H] likewise.  `heads` = (Ws_mu, bs_mu, Ws_ls, bs_ls, Wt_mu,
+    bt_mu, Wt_ls, bt_ls)."""
+    out = []
+    for Wm, bm, Wl, bl in (heads[:4], heads[4:]):
+        out.append((torch.cat([check(Wm.detach().contiguous(), F32, 'W_mu'), check(Wl.detach().contiguous(), F32, 'W_logstd')]),
+                    torch.cat([check(bm.detach().contiguous(), F32, 'b_mu'), check(bl.detach().contiguous(), F32, 'b_logstd')])))
+    return out
+
+
+def _var_head_fwd(st, Wp_b, packs, eps, seed, sample, want_ml=False):
+    N, H = st.shape[0], st.shape[1] // 2
+    z = torch.empty(N, 2 * H, dtype=F32, device=st.device)
+    ml = torch.empty(N, 4 * H, dtype=F32, device=st.device) if want_ml else None
+    kl = torch.zeros(2, dtype=torch.float64, device=st.device)
+    ws = _var_head_ws(H, N, False, st.device)
+    _hip.call('mgv_var_head_fwd_x3', H, N, ptr(st), st.stride(0), ptr(packs[0]), ptr(packs[1]), ptr(Wp_b[0][1]), ptr(Wp_b[1][1]),
+              ptr(eps), 0 if eps is None else eps.stride(0), int(seed), int(bool(sample)), ptr(z), 2 * H, ptr(ml), 4 * H, ptr(kl),
+              ptr(ws), ws.numel())
+    return z, kl, ml
+
+
+class VarHeadFn(torch.autograd.Function):
+    """(z [N, 2H], klsum [2]) of st [N, 2H] = [s | t] under the eight head parameters: per half h, [mu | logstd] = X_h Wp_h^T + bp_h,
+    z = mu + exp(logstd) eps (sample) or mu, klsum[h] = sum(1 + 2 logstd - mu^2 - exp(logstd)^2).  eps [N, 2H] = [eps_s | eps_t] or
+    None: the kernel draws element r * H + c of seed (s) / seed + 1 (t), as DirectedGVAE.sample.  Nothing but st is kept for the
+    backward, which recomputes the heads and the noise."""
+
+    @staticmethod
+    def forward(ctx, st, Ws_mu, bs_mu, Ws_ls, bs_ls, Wt_mu, bt_mu, Wt_ls, bt_ls, eps, seed, sample):
+        std = _rowmajor(st.detach())
+        if std.dtype != F32 or not std.is_cuda:
+            raise HipLibraryError('st must be an fp32 GPU matrix')
+        epsd = _rowmajor(eps.detach()) if eps is not None else None
+        Wp_b = _var_head_packs((Ws_mu, bs_mu, Ws_ls, bs_ls, Wt_mu, bt_mu, Wt_ls, bt_ls))
+        packs = [linear_wpack(W) for W, _ in Wp_b]
+        z, kl, _ = _var_head_fwd(std, Wp_b, packs, epsd, seed, sample)
+        ctx.save_for_backward(std, epsd, Wp_b[0][0], Wp_b[0][1], Wp_b[1][0], Wp_b[1][1], *packs)
+        ctx.seed, ctx.sample = int(seed), bool(sample)
+        ctx.set_materialize_grads(False)
+        return z, kl.to(F32)
+
+    @staticmethod
+    def backward(ctx, gz, gkl):
+        st, eps, Wps, bps, Wpt, bpt, pack_s, pack_t = ctx.saved_tensors
+        N, H = st.shape[0], st.shape[1] // 2
+        gz = _rowmajor(gz.detach()) if gz is not None else None
+        gk = gkl.detach().to(F32).reshape(2).contiguous() if gkl is not None else None
+        tpacks = []
+        for W in (Wps, Wpt):
+            tp = torch.empty(2 * W.numel(), dtype=torch.bfloat16, device=W.device)
+            _pack_into(tp, 0, W, True)
+            tpacks.append(tp)
+        dst = torch.empty(N, 2 * H, dtype=F32, device=st.device)
+        dWs, dWt = torch.zeros_like(Wps), torch.zeros_like(Wpt)
+        dbs, dbt = torch.zeros_like(bps), torch.zeros_like(bpt)
+        ws = _var_head_ws(H, N, True, st.device)
+        _hip.call('mgv_var_head_bwd_x3', H, N, ptr(st), st.stride(0), ptr(pack_s), ptr(pack_t), ptr(tpacks[0]), ptr(tpacks[1]), ptr(bps), ptr(bpt),
+                  ptr(eps), 0 if eps is None else eps.stride(0), ctx.seed, int(ctx.sample), ptr(gz), 0 if gz is None else gz.stride(0), ptr(gk),
+                  ptr(dst), 2 * H, ptr(dWs), ptr(dWt), ptr(dbs), ptr(dbt), ptr(ws), ws.numel())
+        return dst, dWs[:H], dbs[:H], dWs[H:], dbs[H:], dWt[:H], dbt[:H], dWt[H:], dbt[H:], None, None, None
+
+
+def var_head_fused(H):
+    """Whether var_head takes the fused route at width H (csrc/mgv_launch.h X3Widths, bf16x3 mode, MGV_VAR_HEAD_FUSED)."""
+    return VAR_HEAD_FUSED and use_x3(H)
+
+
+def var_head(st, heads, eps=None, seed=0, sample=True):
+    """(z [N, 2H], klsum [2]) — VarHeadFn where var_head_fused(H) holds, else the same function composed from today's operators
+    (four ops.linear and two ReparamFn: PRECISION = f32, H = 16 / 128, MGV_VAR_HEAD_FUSED=0).  `heads` as _var_head_packs takes them."""
+    H = st.shape[1] // 2
+    if st.shape[0] > 0 and var_head_fused(H):
+        return VarHeadFn.apply(st, *heads, eps, seed, sample)
+    s, t = st[:, :H].contiguous(), st[:, H:].contiguous()          # (the plain Linear takes contiguous rows)
+    zs, kls = [], []
+    for x, (Wm, bm, Wl, bl), e, sd in ((s, heads[:4], None if eps is None else eps[:, :H], seed), (t, heads[4:], None if eps is None else eps[:, H:], seed + 1)):
+        mu, ls = linear(x, Wm, bm), linear(x, Wl, bl)
+        z, kl = ReparamFn.apply(mu, ls, e, sd)
+        zs.append(z if sample else mu)
+        kls.append(kl)
+    return torch.cat(zs, dim=1), torch.stack(kls)
+
+
+def var_head_latent(st, heads):
+    """(mu_s, logstd_s, mu_t, logstd_t) of st under the heads, without gradients: the fused forward's ML rows, or four ops.linear."""
+    H = st.shape[1] // 2
+    with torch.no_grad():
+        if st.shape[0] > 0 and var_head_fused(H):
+            std = _rowmajor(st.detach())
+            Wp_b = _var_head_packs(heads)
+            ml = _var_head_fwd(std, Wp_b, [linear_wpack(W) for W, _ in Wp_b], None, 0, False, want_ml=True)[2]
+            return ml[:, :H], ml[:, H:2 * H], ml[:, 2 * H:3 * H], ml[:, 3 * H:]
+        s, t = st[:, :H].contiguous(), st[:, H:].contiguous()
+        return (linear(s, heads[0], heads[1]), linear(s, heads[2], heads[3]), linear(t, heads[4], heads[5]), linear(t, heads[6], heads[7]))
+
+
+# ------------------------------------------------------------------------------------------------
 # optimiser
 # ------------------------------------------------------------------------------------------------
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, grad_scale, step):

@@ -55,11 +55,11 @@ class StepBranch:
         self.main.wait_stream(self.side)
 
     def take(self, model):
-        """Join, and hand over (loss, pred_bin, gt_bin): these and the model's two result tensors were allocated on the side stream
-        and are read on the main one from here on."""
+        """Join, and hand over (loss, pred_bin, gt_bin): these and the model's result tensors (of a variational model also its KL sums)
+        were allocated on the side stream and are read on the main one from here on."""
         self.join()
         out, self.result = self.result, None      # this object must not keep the step's loss graph alive (its nodes hold it)
-        for t in (*out, model.last_confusion, model.last_link_metrics):
+        for t in (*out, model.last_confusion, model.last_link_metrics, getattr(model, '_klsum', None)):
             if t is not None:
                 t.record_stream(self.main)
         return out

@@ -15,6 +15,7 @@ from torch import nn
 
 from . import metrics, ops
 from .data import CircuitBatch
+from .digvae_model import DirectedGVAE
 from .optim import FlatAdam
 from .prefetch import BatchPrefetcher
 from .step_branch import StepBranch
@@ -75,6 +76,9 @@ class Trainer():
         self.lr = lr
         self.lr_step = -1
         self.rc_prob_func_weight = list(rc_prob_func_weight)
+        # weight of the KL term of a variational model in the step's loss.  0.0 is the reference: KL is computed, reported under
+        # 'kl_loss' and never added (trainer.py:145-148)
+        self.kl_weight = float(getattr(args, 'kl_weight', 0.0) or 0.0)
         os.makedirs(save_dir, exist_ok=True)
         self.log_dir = os.path.join(save_dir, training_id)
         os.makedirs(self.log_dir, exist_ok=True)
@@ -191,9 +195,9 @@ class Trainer():
             hs, hf = self.model(batch)
             loss, pred_bin, gt_bin = self.model.recon_loss(hs, plan=batch._mgv_plan, **recon)
         loss_status = {'recon_loss': loss, 'pred_bin': pred_bin, 'gt_bin': gt_bin}
-        if 'VAE' in getattr(self.args, 'model', '') and hasattr(self.model, 'kl_loss'):
+        if getattr(self.model, 'variational', False) or ('VAE' in getattr(self.args, 'model', '') and isinstance(self.model, DirectedGVAE)):
             s_kl, t_kl = self.model.kl_loss()
-            loss_status['kl_loss'] = s_kl + t_kl          # computed, not added (as in the reference)
+            loss_status['kl_loss'] = s_kl + t_kl          # computed; added only under a positive kl_weight (weighted_loss)
         # hf has two consumers (trainer.py:155-163): the function loss first, the readout on the hf it passes through, so that the
         # two gradients meet inside the function-loss backward kernel
         loss_status['func_loss'], hf_r = ops.func_loss_passthrough(hf, batch['tt_pair_index'], batch['tt_sim'], cache=batch)
@@ -218,7 +222,10 @@ class Trainer():
 
     def weighted_loss(self, loss_status):
         w = self.rc_prob_func_weight
-        return w[0] * loss_status['recon_loss'] + w[1] * loss_status['prob_loss'] + w[2] * loss_status['func_loss']
+        loss = w[0] * loss_status['recon_loss'] + w[1] * loss_status['prob_loss'] + w[2] * loss_status['func_loss']
+        if self.kl_weight > 0 and 'kl_loss' in loss_status:
+            loss = loss + self.kl_weight * loss_status['kl_loss']
+        return loss
 
     def train_step(self, batch, want_pred=False):
         """zero_grad -> run_batch -> weighted loss -> backward -> (all-reduce) Adam (trainer.py:222-234)."""
@@ -236,14 +243,17 @@ class Trainer():
     def enqueue_metrics(self, loss_status):
         """Start the host copy of this step's 7 metrics (3 losses, TP/FP/TN/FN) into pinned memory and return the PREVIOUS
         step's values (None at the first call): the host never waits for the step it has just enqueued, so the next step's
-        launches are already queued when the GPU finishes this one.  `flush_metrics()` returns the last step's values."""
+        launches are already queued when the GPU finishes this one.  `flush_metrics()` returns the last step's values.
+        A step that has a 'kl_loss' (variational model) carries it in an eighth slot."""
         vals = torch.cat([torch.stack([loss_status['recon_loss'].detach(), loss_status['prob_loss'].detach(),
                                        loss_status['func_loss'].detach()]).double(), loss_status['confusion'].double()])
+        if 'kl_loss' in loss_status:
+            vals = torch.cat([vals, loss_status['kl_loss'].detach().double().reshape(1)])
         if not vals.is_cuda:
             prev, self._m_last = getattr(self, '_m_last', None), vals.tolist()
             return prev
-        if getattr(self, '_m_buf', None) is None:
-            self._m_buf = torch.empty(2, 7, dtype=torch.float64).pin_memory()
+        if getattr(self, '_m_buf', None) is None or self._m_buf.shape[1] != vals.numel():
+            self._m_buf = torch.empty(2, vals.numel(), dtype=torch.float64).pin_memory()
             self._m_ev = [None, None]
             self._m_n = 0
         slot = self._m_n % 2
@@ -277,14 +287,16 @@ class Trainer():
         train_loader = self._loader(train_dataset, shuffle=not self.distributed)
         val_loader = self._loader(val_dataset, shuffle=not self.distributed)
         batch_time = AverageMeter()
-        stats = {k: AverageMeter() for k in ('recon', 'prob', 'func', 'acc', 'tp', 'fp', 'tn', 'fn')}
+        stats = {k: AverageMeter() for k in ('recon', 'prob', 'func', 'acc', 'tp', 'fp', 'tn', 'fn', 'kl')}
         print('[INFO] Start training, lr = {:.4f}'.format(self.optimizer.param_groups[0]['lr']))
 
         def account(vals):
             if vals is None:
                 return
-            tot = max(sum(vals[3:]), 1.0)
-            tp, fp, tn, fn = (v / tot for v in vals[3:])
+            tot = max(sum(vals[3:7]), 1.0)
+            tp, fp, tn, fn = (v / tot for v in vals[3:7])
+            if len(vals) > 7:
+                stats['kl'].update(vals[7])
             for k, v in zip(('recon', 'prob', 'func', 'acc', 'tp', 'fp', 'tn', 'fn'),
                             (vals[0], vals[1], vals[2], tp + tn, tp, fp, tn, fn)):
                 stats[k].update(v)
@@ -339,6 +351,8 @@ class Trainer():
                     c = c[c[:, 0] > 0].double()
                     if c.shape[0] > 0:
                         rank_cols += ' |FuncAcc: {:.4f}'.format(float((c[:, 1] / c[:, 0]).mean()))
+                if getattr(self.model, 'variational', False):
+                    rank_cols = ' |KL: {:.4f}'.format(stats['kl'].avg) + rank_cols
                 if self.local_rank == 0:
                     line = self.LOG_LINE.format(phase, epoch, num_epoch, stats['recon'].avg, stats['acc'].avg * 100, stats['prob'].avg,
                                                 stats['func'].avg, batch_time.avg) + rank_cols + '\n'

@@ -104,6 +104,8 @@ def main(argv=None):
                     'that 1 - cos(hf) orders the way the truth-table distance does: name/func_acc [B] (-1 where no comparison is '
                     'eligible) and name/func_counts [B, 3] = eligible, concordant, tied (Model.function_accuracy; exact counts of what '
                     'get_function_acc samples)')
+    ap.add_argument('--variational', action='store_true', help='the checkpoint is of a model trained with train.py --variational: build '
+                    'the four heads fc_{s,t}_{mu,logstd} so that it loads in full; the link tools then decode the posterior means')
     a = ap.parse_args(argv)
     acc_gaps = [float(g) for g in a.function_acc.split(',') if g.strip()]
     rank_ks = [int(k) for k in a.link_ranking.split(',') if k.strip()]
@@ -112,7 +114,7 @@ def main(argv=None):
     dev = torch.device('cuda:0')
     enc = deepgate.digae_layer.DirectMultiGCNEncoder(dim_feature=6, dim_hidden=a.dim_hidden, s_rounds=a.rounds, t_rounds=a.rounds,
                                                      enable_reverse=True, layernorm=True)
-    model = getattr(deepgate, 'dg_ae_model_' + a.type).Model(struct_encoder=enc, dim_hidden=a.dim_hidden).to(dev)
+    model = getattr(deepgate, 'dg_ae_model_' + a.type).Model(struct_encoder=enc, dim_hidden=a.dim_hidden, variational=a.variational).to(dev)
     if a.checkpoint:
         model.load(a.checkpoint)
     model.eval()

@@ -51,9 +51,11 @@ def main(argv=None):
             dim_hidden=args.dim_hidden, dim_feature=args.dim_feature, enable_reverse=True,
             s_rounds=args.s_rounds, t_rounds=args.t_rounds, layernorm=args.layernorm)
     if 'VAE' in args.model:
-        raise SystemExit('the DG_VAE training path does not run in the reference either (SURVEY.md §3.4); '
-                         'the sampler/KL operators are available as deepgate.digvae_model.DirectedGVAE')
-    model = model_map[args.type](struct_encoder=encoder, dim_hidden=args.dim_hidden, enable_encode=True, enable_reverse=True)
+        raise SystemExit('the DG_VAE training path does not run in the reference either (SURVEY.md §3.4): train the multi-gate model '
+                         'as a variational auto-encoder with --model DG_AE --variational; the sampler/KL operators are also '
+                         'available as deepgate.digvae_model.DirectedGVAE')
+    model = model_map[args.type](struct_encoder=encoder, dim_hidden=args.dim_hidden, enable_encode=True, enable_reverse=True,
+                                 variational=args.variational)
     trainer = deepgate.Trainer(args, model, training_id=args.exp_id, save_dir=args.save_dir, batch_size=args.batch_size,
                                device='cuda:0', distributed=args.distributed)
     if args.resume:
