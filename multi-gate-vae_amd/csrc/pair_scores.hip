@@ -10,6 +10,15 @@
 // its thresholded pairs come from the symmetric form of the selection walk (k_pair_select<.., SYM>).
 // The classes of that relation come from the same walk with a union-find in place of the lists (k_sim_union, mgv_unionfind.h).
 // The rank of a true link among all candidates of its node comes from the same walk with a list of thresholds per row (k_pair_rank).
+// The same consumers on the rows of ANOTHER graph of the batch (k_cross_*) are matching across circuits.
+//
+// What decides a result exists ONCE in the file: a row's graph and the clamp of its range (row_graph, graph_rows), who is a candidate
+// (candidate<SYM>), and each consumer — the sorted lists (topk_*), the count / fill (select_*), the bins (HistRun), the unions
+// (unite_bits).  An own-graph kernel and its cross twin are two prologues and two tile ranges around the same consumer, so the same
+// bits meet the same `>` in both, and a fix to an insertion order, a fill cursor or a run merge is made and proved once.
+// Three things stand in a kernel and in its twin all the same, each for a reason the compiler gave (stated where they stand): the
+// five lines of the tile loop, the selection's one-line decision `candidate<SYM>(...) && rep > threshold`, and the histogram's flush
+// of a finished run (six lines that add to arrays the kernel declares; it decides no bin and no count).
 #include "mgv_launch.h"
 #include "mgv_unionfind.h"
 #include "../../include/mgvae_hip.h"
@@ -82,26 +91,46 @@ __device__ __forceinline__ void tile_scores(f32x4 (&acc)[4], const float (&a)[H 
 // and branches differently around it: a wave less in k_pair_fwd<32>, k_pair_topk<16> and k_sim_union<16>, 2 - 5 % on the general count
 // (NOTEBOOK 2026-10-19, eighth entry).  What decides — the rows' ranges, the tile range, who is a candidate — exists once, below.
 
+// The graph of row u: the first whose end lies behind u; -1 for a row past N or behind the last graph.
+__device__ __forceinline__ int row_graph(int64_t N, int64_t u, const int32_t* gp, int G) {
+    if (u >= N) return -1;
+    int a = 0, b = G;
+    while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
+    return a < G ? a : -1;
+}
+
+// The rows [lo, hi) of graph g, nothing for a g outside the table: whatever the table holds, no column outside [0, N) is touched.
+__device__ __forceinline__ void graph_rows(int64_t N, const int32_t* gp, int G, int g, int64_t& lo, int64_t& hi) {
+    lo = 0; hi = 0;
+    if (g >= 0 && g < G) { lo = gp[g]; hi = gp[g + 1]; }
+    lo = lo < 0 ? 0 : (lo > N ? N : lo);
+    hi = hi < lo ? lo : (hi > N ? N : hi);
+}
+
 // The candidate columns [rlo[i], rhi[i]) of row u0 + i, i < 64: the row's own graph (the whole batch without a table, nothing for a row
 // past N), and in rgi — only where the caller keeps that table (GI) — the graph's index.  The caller's barrier publishes the tables.
 template <bool GI = false>
 __device__ __forceinline__ void row_ranges(int64_t N, int64_t u0, const int32_t* gp, int G, int* rlo, int* rhi, int* rgi = nullptr) {
     if (threadIdx.x >= kPairTile) return;
     const int64_t u = u0 + threadIdx.x;
-    int64_t lo = 0, hi = 0;
-    int gi = 0;
-    if (u < N) {
-        if (gp == nullptr) { hi = N; }
-        else {
-            int a = 0, b = G;                              // first graph whose end lies behind u
-            while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-            if (a < G) { lo = gp[a]; hi = gp[a + 1]; gi = a; }
-            lo = lo < 0 ? 0 : (lo > N ? N : lo);           // whatever the table holds, no column outside [0, N) is touched
-            hi = hi < lo ? lo : (hi > N ? N : hi);
-        }
-    }
+    const int g = gp != nullptr ? row_graph(N, u, gp, G) : -1;
+    int64_t lo = 0, hi = u < N ? N : 0;
+    if (gp != nullptr) graph_rows(N, gp, G, g, lo, hi);
     rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
-    if constexpr (GI) rgi[threadIdx.x] = gi;               // gi < max(G, 1)
+    if constexpr (GI) rgi[threadIdx.x] = g < 0 ? 0 : g;    // < max(G, 1)
+}
+
+// The same tables where the candidates of a row of graph g are ALL rows of graph peer[g] (the k_cross_* kernels): nothing for a row
+// past N, a row behind the last graph, peer = -1 or a peer outside the table.  rgi stays the ROW's graph.
+template <bool GI = false>
+__device__ __forceinline__ void cross_ranges(int64_t N, int64_t u0, const int32_t* gp, int G, const int32_t* peer, int* rlo, int* rhi,
+                                             int* rgi = nullptr) {
+    if (threadIdx.x >= kPairTile) return;
+    const int g = row_graph(N, u0 + threadIdx.x, gp, G);
+    int64_t lo, hi;
+    graph_rows(N, gp, G, g < 0 ? -1 : peer[g], lo, hi);
+    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
+    if constexpr (GI) rgi[threadIdx.x] = g < 0 ? 0 : g;
 }
 
 // The columns [clo, chi) that hold a candidate of any of the 64 rows (clo >= chi: none, nothing to walk).
@@ -252,25 +281,86 @@ __global__ __launch_bounds__(kThreads) void k_pair_bwd(int64_t A, int64_t B, con
 // order of the lists: raw dot product descending, ties by ascending node id
 __device__ __forceinline__ bool pair_better(float v, int i, float kv, int ki) { return v > kv || (v == kv && i < ki); }
 
-// One workgroup per 64 rows u; it walks the column tiles that meet the rows' graphs.  Each wave leaves its 16 x 16 score blocks in
-// LDS, where 4 lanes per row scan them in ascending column order against the row's k-th best and insert into the row's sorted list
-// (LDS).  A row only ever sees the columns of its own graph.
+// The top-k consumer.  Each wave leaves its 16 x 16 score blocks in LDS (sc), where 4 lanes per row — lane (lane >> 2, sub = lane & 3)
+// scans for row srow = 16 w + (lane >> 2) of the tile — scan them in ascending column order against the row's k-th best and insert
+// into the row's sorted list (lv / li, LDS).  A row only ever sees the columns of its range [mylo, myhi).
+// Three functions of scalars by reference and plain pointers to the LDS arrays, the lane's indices among them: the kernels that call
+// them have the registers and waves they had with this text in place (NOTEBOOK 2026-10-20, tenth entry).
+constexpr int kTopkScLd = 17;          // row stride of sc
+
+// the lists of the wave's rows start empty, initialised by their own wave
+__device__ __forceinline__ void topk_init(float* lv, int* li, const int& srow, const int& sub) {
+    for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
+}
+
+// the wave's block of columns cb .. cb + 15: counted against the threshold (cnt) and offered to the lists of row su
+__device__ __forceinline__ void topk_block(const f32x4& acc, const int64_t& cb, const int64_t& su, const int& mylo, const int& myhi,
+                                           const int& k, const int& sigmoid, const float& threshold, const int& skip_self, float* sc,
+                                           float* lv, int* li, int& cnt, const int& w, const int& r, const int& q, const int& srow,
+                                           const int& sub) {
+    wave_lds_fence();                              // the previous block's reads are done
+#pragma unroll
+    for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * kTopkScLd + r] = acc[g];
+    wave_lds_fence();
+    for (int st = 0; st < 4; ++st) {
+        const int64_t col = cb + 4 * st + sub;
+        const float v = sc[srow * kTopkScLd + 4 * st + sub];
+        float rep;
+        const bool valid = candidate<false>(v, col, su, mylo, myhi, skip_self, sigmoid, rep);
+        cnt += (valid && rep > threshold) ? 1 : 0;
+        const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
+        if (__ballot(pass) == 0ull) continue;
+        for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
+            if (pass && sub == turn) {
+                float* L = lv + srow * kTopkMax;
+                int* I = li + srow * kTopkMax;
+                if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
+                    int pos = k - 1;
+                    while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
+                        L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
+                    }
+                    L[pos] = v; I[pos] = (int)col;
+                }
+            }
+            wave_lds_fence();
+        }
+    }
+}
+
+// after the walk: the row's four counts meet, and row su < N writes n_above and its k entries (-1 / -inf where the list is short).
+// The loop is kept rolled: unrolled inside this function it costs k_cross_topk<16> 12 VGPRs and a wave.
+__device__ __forceinline__ void topk_write(const int64_t& N, const int64_t& su, const int& k, const int& sigmoid, int& cnt, const float* lv,
+                                           const int* li, int32_t* idx, float* score, int32_t* n_above, const int& srow, const int& sub) {
+    wave_lds_fence();
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    if (su < N) {
+        if (sub == 0) n_above[su] = cnt;
+#pragma unroll 1
+        for (int j = sub; j < k; j += 4) {
+            const int id = li[srow * kTopkMax + j];
+            const float v = lv[srow * kTopkMax + j];
+            idx[su * k + j] = id == INT_MAX ? -1 : id;
+            score[su * k + j] = id == INT_MAX ? -INFINITY : (sigmoid ? sigmoidf_(v) : v);
+        }
+    }
+}
+
+// One workgroup per 64 rows u; it walks the column tiles that meet the rows' graphs.
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                         int G, int k, int sigmoid, float threshold, int skip_self, int32_t* idx,
                                                         float* score, int32_t* n_above) {
-    constexpr int LDS_SC = 17;
     __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
-    __shared__ float sc[kPairTile * LDS_SC];
+    __shared__ float sc[kPairTile * kTopkScLd];
     __shared__ float lv[kPairTile * kTopkMax];
     __shared__ int li[kPairTile * kTopkMax];
     __shared__ int rlo[kPairTile], rhi[kPairTile];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
     row_ranges(N, u0, gp, G, rlo, rhi);
-    // the wave's rows: lane (row = lane >> 2, sub = lane & 3) in the scan, list rows initialised by their own wave
     const int srow = 16 * w + (lane >> 2), sub = lane & 3;
-    for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
+    topk_init(lv, li, srow, sub);
     __syncthreads();
     int64_t clo, chi;
     col_span(N, rlo, rhi, clo, chi);
@@ -294,49 +384,12 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                wave_lds_fence();                              // the previous block's reads are done
-#pragma unroll
-                for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * LDS_SC + r] = acc[c][g];
-                wave_lds_fence();
                 const int64_t cb = ct * kPairTile + 16 * c;
-                for (int st = 0; st < 4; ++st) {
-                    const int64_t col = cb + 4 * st + sub;
-                    const float v = sc[srow * LDS_SC + 4 * st + sub];
-                    float rep;
-                    const bool valid = candidate<false>(v, col, su, mylo, myhi, skip_self, sigmoid, rep);
-                    cnt += (valid && rep > threshold) ? 1 : 0;
-                    const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
-                    if (__ballot(pass) == 0ull) continue;
-                    for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
-                        if (pass && sub == turn) {
-                            float* L = lv + srow * kTopkMax;
-                            int* I = li + srow * kTopkMax;
-                            if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
-                                int pos = k - 1;
-                                while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
-                                    L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
-                                }
-                                L[pos] = v; I[pos] = (int)col;
-                            }
-                        }
-                        wave_lds_fence();
-                    }
-                }
+                topk_block(acc[c], cb, su, mylo, myhi, k, sigmoid, threshold, skip_self, sc, lv, li, cnt, w, r, q, srow, sub);
             }
         }
     }
-    wave_lds_fence();
-    cnt += __shfl_xor(cnt, 1, 64);
-    cnt += __shfl_xor(cnt, 2, 64);
-    if (su < N) {
-        if (sub == 0) n_above[su] = cnt;
-        for (int j = sub; j < k; j += 4) {
-            const int id = li[srow * kTopkMax + j];
-            const float v = lv[srow * kTopkMax + j];
-            idx[su * k + j] = id == INT_MAX ? -1 : id;
-            score[su * k + j] = id == INT_MAX ? -INFINITY : (sigmoid ? sigmoidf_(v) : v);
-        }
-    }
+    topk_write(N, su, k, sigmoid, cnt, lv, li, idx, score, n_above, srow, sub);
 }
 
 // ---------------------------------------------------------------------------------- thresholded links as per-row lists
@@ -351,6 +404,69 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
 //                 only slots in [row_ptr[u], min(row_ptr[u+1], cap)) that are >= 0; what has no room is dropped.
 //   SYM = true  : s = t = unit rows (mgv_sim_select_*; trainer.py:158-160 in the arithmetic of digae_layer.py:31-33): row u lists only
 //                 v > u, on half the tiles (tile_span<true>, candidate<true>).
+//
+// The selection consumer: the lane's four rows 4 q + g of its wave — candidate range, slots, cursor (select_rows) — what a decided
+// entry of a tile does with them (select_entry), and the counts at the end (select_counts).  The entry is the unit, with its row's
+// state as scalars by reference: a function of the whole tile that takes the five arrays (as arguments, or as members of a struct)
+// keeps them in memory until after it is inlined, and the general forms of k_pair_select then need 24 - 53 VGPRs more and lose a wave
+// in four.  The decision itself — `candidate<SYM>(...) && rep > threshold`, one line on the one statement of `candidate` — stands in
+// the kernels' loops over (c, g), as the unions' chains do: behind the call the 16 float compares of a tile of the general forms go
+// into VCC one after the other (v_cmp_lt_f32_e32 for _e64), the form that cost k_sim_union 1.6 - 4.9 % (NOTEBOOK 2026-10-19, eighth
+// entry; 2026-10-20, tenth entry).
+template <bool FILL>
+__device__ __forceinline__ void select_rows(const int64_t& N, const int64_t& u0, const int* rlo, const int* rhi, const int64_t* row_ptr,
+                                            const int64_t& cap, int (&lo)[4], int (&hi)[4], int (&cnt)[4], int64_t (&base)[4],
+                                            uint64_t (&room)[4]) {
+    const int w = threadIdx.x >> 6, q = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int lr = 16 * w + 4 * q + g;
+        lo[g] = rlo[lr]; hi[g] = rhi[lr]; cnt[g] = 0;
+        base[g] = 0; room[g] = 0;
+        if (FILL && u0 + lr < N) {
+            const int64_t b = row_ptr[u0 + lr], e0 = row_ptr[u0 + lr + 1], e = e0 < cap ? e0 : cap;
+            base[g] = b;
+            room[g] = e > b ? (uint64_t)e - (uint64_t)b : 0ull;     // exact for any b < e
+        }
+    }
+}
+
+// one decided entry of the tile where it lies: the count or the fill of its row (cnt: the row's count or cursor)
+template <bool FILL>
+__device__ __forceinline__ void select_entry(const bool& pass, const float& rep, const int64_t& col, int& cnt,
+                                             const int64_t& base, const uint64_t& room, int32_t* col_out, float* score_out) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    if constexpr (!FILL) {
+        cnt += pass ? 1 : 0;
+    } else {
+        const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
+        const uint64_t i = (uint64_t)(unsigned)cnt + (uint64_t)__popc(bits & ((1u << r) - 1u));
+        cnt += __popc(bits);
+        if (pass && i < room) {                     // i < room: base + i < min(row_ptr[u+1], cap), no overflow
+            const int64_t pos = base + (int64_t)i;
+            if (pos >= 0) {
+                col_out[pos] = (int32_t)col;
+                if (score_out != nullptr) score_out[pos] = rep;
+            }
+        }
+    }
+}
+
+// the counts of a row's 16 lanes add up -> n_sel[u]
+__device__ __forceinline__ void select_counts(const int64_t& N, const int64_t& row0, const int (&cnt)[4], int32_t* n_sel) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        int n = cnt[g];
+        n += __shfl_xor(n, 1, 64);
+        n += __shfl_xor(n, 2, 64);
+        n += __shfl_xor(n, 4, 64);
+        n += __shfl_xor(n, 8, 64);
+        const int64_t u = row0 + 4 * q + g;
+        if (r == 0 && u < N) n_sel[u] = n;
+    }
+}
+
 template <int H, bool FILL, bool SYM = false>
 __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                           int G, int sigmoid, float threshold, int skip_self, int32_t* n_sel,
@@ -364,21 +480,10 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
     int64_t clo, chi;
     col_span(N, rlo, rhi, clo, chi);
     const int64_t row0 = u0 + 16 * w;
-    // the lane's four rows 4 q + g: candidate range, slots, cursor
     int mylo[4], myhi[4], cnt[4];
     int64_t base[4];
     uint64_t room[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int lr = 16 * w + 4 * q + g;
-        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; cnt[g] = 0;
-        base[g] = 0; room[g] = 0;
-        if (FILL && u0 + lr < N) {
-            const int64_t b = row_ptr[u0 + lr], e0 = row_ptr[u0 + lr + 1], e = e0 < cap ? e0 : cap;
-            base[g] = b;
-            room[g] = e > b ? (uint64_t)e - (uint64_t)b : 0ull;     // exact for any b < e
-        }
-    }
+    select_rows<FILL>(N, u0, rlo, rhi, row_ptr, cap, mylo, myhi, cnt, base, room);
     float a[H / 4];
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     if (clo < chi) {
@@ -401,33 +506,12 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
                     float rep;
                     const bool pass = candidate<SYM>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], skip_self, sigmoid, rep) &&
                                       rep > threshold;
-                    if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
-                    const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
-                    const uint64_t i = (uint64_t)(unsigned)cnt[g] + (uint64_t)__popc(bits & ((1u << r) - 1u));
-                    cnt[g] += __popc(bits);
-                    if (pass && i < room[g]) {                  // i < room: base + i < min(row_ptr[u+1], cap), no overflow
-                        const int64_t pos = base[g] + (int64_t)i;
-                        if (pos >= 0) {
-                            col_out[pos] = (int32_t)col;
-                            if (score_out != nullptr) score_out[pos] = rep;
-                        }
-                    }
+                    select_entry<FILL>(pass, rep, col, cnt[g], base[g], room[g], col_out, score_out);
                 }
             }
         }
     }
-    if (!FILL) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            int n = cnt[g];
-            n += __shfl_xor(n, 1, 64);
-            n += __shfl_xor(n, 2, 64);
-            n += __shfl_xor(n, 4, 64);
-            n += __shfl_xor(n, 8, 64);
-            const int64_t u = row0 + 4 * q + g;
-            if (r == 0 && u < N) n_sel[u] = n;
-        }
-    }
+    if (!FILL) select_counts(N, row0, cnt, n_sel);
 }
 
 // ---------------------------------------------------------------------------------- classes straight from the walk
@@ -437,6 +521,20 @@ __global__ __launch_bounds__(kThreads) void k_pair_select(int64_t N, const float
 // are exactly those of the list mgv_sim_select_fill writes.  Outside the MFMA section: a lane first decides its 16 entries of the tile
 // into a bit mask, then unites the set bits; uf_unite starts with the two finds and leaves when the roots agree, which at a low
 // threshold is nearly always.
+
+// The lane's decisions of column tile ct as a mask — bit 4 c + g: the entry (row row0 + 4 q + g, column 16 c + r) — united one set bit
+// after the other.  DIAG: an entry may be a row's own column (the cross walk under a self-peer), which unites nothing.
+template <bool DIAG>
+__device__ __forceinline__ void unite_bits(unsigned bits, const int64_t& row0, const int64_t& ct, int32_t* parent, int32_t* status) {
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    while (bits != 0) {
+        const int b = __ffs(bits) - 1;
+        bits &= bits - 1;
+        const int u = (int)(row0 + 4 * q + (b & 3)), v = (int)(ct * kPairTile + 16 * (b >> 2) + r);
+        if (!DIAG || u != v) uf_unite(parent, u, v, status);
+    }
+}
+
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* y, int ldy, const int32_t* gp, int G, float threshold,
                                                         int32_t* parent, int32_t* status) {
@@ -477,11 +575,7 @@ __global__ __launch_bounds__(kThreads) void k_sim_union(int64_t N, const float* 
                     bits |= pass ? 1u << (4 * c + g) : 0u;
                 }
             }
-            while (bits != 0) {                                 // row < col < myhi <= N: both ids inside parent
-                const int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                uf_unite(parent, (int)(row0 + 4 * q + (b & 3)), (int)(ct * kPairTile + 16 * (b >> 2) + r), status);
-            }
+            unite_bits<false>(bits, row0, ct, parent, status);  // row < col < myhi <= N: both ids inside parent
         }
     }
 }
@@ -510,6 +604,71 @@ constexpr int kHistMaxEdges = 256;
 constexpr int kHistTable = 512;        // >= 2^p - 1 for every B <= kHistMaxEdges
 constexpr int kHistSlots = 2;          // the tile's first and last graph
 
+// The histogram consumer: the two tables in LDS, the hist rows of the tile's first and last graph, and the lane's run.  Scalars only,
+// so it lives in registers (no scratch in any kernel); the ranges and graphs of the lane's four rows stay arrays of the kernel and
+// come to row() one row at a time, for the reason given at select_entry.  What a finished run does — flush: one add to the LDS
+// counters of the first or the last graph, or to hist — is a lambda of the kernel that declares those arrays, handed to row() and
+// finish(): as a member on pointers kept in the struct, the three adds are generic when the compiler merges them into ONE flat atomic
+// on a selected address, LDS counters included (2.4 - 3.0 % on mgv_cross_hist at 64 and 256 edges, NOTEBOOK 2026-10-20, tenth entry).
+struct HistRun {
+    int B, B1, top, gfirst, glast;
+    int run_gi = 0, run_bin = 0, run_n = 0;   // run_n candidates of bin run_bin of graph run_gi that no atomic has seen yet
+
+    // the caller's barrier publishes both tables
+    static __device__ __forceinline__ void tables(float* el, unsigned long long* lh, const float* edges, int B) {
+        for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
+        for (int i = threadIdx.x; i < kHistSlots * (B + 1); i += kThreads) lh[i] = 0ull;
+    }
+
+    // behind that barrier; rgi: the graph of each of the tile's rows
+    __device__ __forceinline__ HistRun(int B_, int top_, int64_t N, int64_t u0, const int* rgi) : B(B_), B1(B_ + 1), top(top_) {
+        const int64_t left = N - 1 - u0;                   // u0 < N: the tile's last row inside N
+        gfirst = rgi[0]; glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
+    }
+
+    // the lane's four entries acc[c][g] of row u in column tile ct (columns 16 c + r); [lo, hi) and gi: the row's candidates and its graph.
+    // Row by row: a run lasts as long as the row's scores stay in one bin.
+    template <bool SYM, typename Flush>
+    __device__ __forceinline__ void row(const f32x4 (&acc)[4], const int& g, const int64_t& ct, const int64_t& u, const int& lo,
+                                        const int& hi, const int& gi, const int& skip_self, const int& sigmoid, const float* el,
+                                        const Flush& flush) {
+        const int r = threadIdx.x & 15;
+        bool valid[4], any = false;
+        float rep[4];
+        int pos[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            valid[c] = candidate<SYM>(acc[c][g], ct * kPairTile + 16 * c + r, u, lo, hi, skip_self, sigmoid, rep[c]);
+            any = any || valid[c];
+            pos[c] = 0;
+        }
+        if (__ballot(any) == 0ull) return;                 // the wave has no candidate in these rows of this tile
+        for (int step = top; step > 0; step >>= 1) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (!valid[c]) continue;
+            const int bin = pos[c] < B ? pos[c] : B;       // an ascending table never gives more; nothing else is indexed
+            if (run_n > 0 && run_gi == gi && run_bin == bin) { ++run_n; continue; }
+            flush();
+            run_gi = gi; run_bin = bin; run_n = 1;
+        }
+    }
+
+    // after the walk, by every thread of the workgroup: the last run, then one global add per non-zero LDS counter
+    template <typename Flush>
+    __device__ __forceinline__ void finish(unsigned long long* lh, unsigned long long* hist, const Flush& flush) {
+        flush();
+        __syncthreads();
+        for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) {
+            const unsigned long long n = lh[i];
+            if (n != 0ull) atomicAdd(&hist[(int64_t)(i < B1 ? gfirst : glast) * B1 + (i < B1 ? i : i - B1)], n);
+        }
+    }
+};
+
 template <int H, bool SYM>
 __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* gp,
                                                         int G, int sigmoid, int skip_self, const float* edges, int B, int top,
@@ -520,31 +679,26 @@ __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* 
     __shared__ unsigned long long lh[kHistSlots * (kHistMaxEdges + 1)];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
-    const int B1 = B + 1;
     row_ranges<true>(N, u0, gp, G, rlo, rhi, rgi);         // rgi: a row of hist
-    for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
-    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) lh[i] = 0ull;
+    HistRun::tables(el, lh, edges, B);
     __syncthreads();
     int64_t clo, chi;
     col_span(N, rlo, rhi, clo, chi);
     const int64_t row0 = u0 + 16 * w;
-    const int64_t left = N - 1 - u0;                       // u0 < N: the tile's last row inside N
-    const int gfirst = rgi[0], glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
+    HistRun run(B, top, N, u0, rgi);
+    auto flush = [&]() {
+        if (run.run_n > 0) {
+            if (run.run_gi == run.gfirst) atomicAdd(&lh[run.run_bin], (unsigned long long)run.run_n);
+            else if (run.run_gi == run.glast) atomicAdd(&lh[run.B1 + run.run_bin], (unsigned long long)run.run_n);
+            else atomicAdd(&hist[(int64_t)run.run_gi * run.B1 + run.run_bin], (unsigned long long)run.run_n);
+        }
+    };
     int mylo[4], myhi[4], mygi[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int lr = 16 * w + 4 * q + g;
         mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; mygi[g] = rgi[lr];
     }
-    // the lane's run: run_n candidates of bin run_bin of graph run_gi that no atomic has seen yet
-    int run_gi = 0, run_bin = 0, run_n = 0;
-    auto flush = [&]() {
-        if (run_n > 0) {
-            if (run_gi == gfirst) atomicAdd(&lh[run_bin], (unsigned long long)run_n);
-            else if (run_gi == glast) atomicAdd(&lh[B1 + run_bin], (unsigned long long)run_n);
-            else atomicAdd(&hist[(int64_t)run_gi * B1 + run_bin], (unsigned long long)run_n);
-        }
-    };
     float a[H / 4];
     load_row_frags<H>(a, s, lds, row0 + r, row0 + r < N, q);
     if (clo < chi) {
@@ -560,39 +714,11 @@ __global__ __launch_bounds__(kThreads) void k_pair_hist(int64_t N, const float* 
             f32x4 acc[4];
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {                      // row by row: a run lasts as long as the row's scores stay in one bin
-                bool valid[4], any = false;
-                float rep[4];
-                int pos[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    valid[c] = candidate<SYM>(acc[c][g], ct * kPairTile + 16 * c + r, row0 + 4 * q + g, mylo[g], myhi[g], skip_self, sigmoid,
-                                              rep[c]);
-                    any = any || valid[c];
-                    pos[c] = 0;
-                }
-                if (__ballot(any) == 0ull) continue;           // the wave has no candidate in these rows of this tile
-                for (int step = top; step > 0; step >>= 1) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (!valid[c]) continue;
-                    const int bin = pos[c] < B ? pos[c] : B;   // an ascending table never gives more; nothing else is indexed
-                    if (run_n > 0 && run_gi == mygi[g] && run_bin == bin) { ++run_n; continue; }
-                    flush();
-                    run_gi = mygi[g]; run_bin = bin; run_n = 1;
-                }
-            }
+            for (int g = 0; g < 4; ++g)
+                run.template row<SYM>(acc, g, ct, row0 + 4 * q + g, mylo[g], myhi[g], mygi[g], skip_self, sigmoid, el, flush);
         }
     }
-    flush();
-    __syncthreads();
-    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) {
-        const unsigned long long n = lh[i];
-        if (n != 0ull) atomicAdd(&hist[(int64_t)(i < B1 ? gfirst : glast) * B1 + (i < B1 ? i : i - B1)], n);
-    }
+    run.finish(lh, hist, flush);
 }
 
 // ---------------------------------------------------------------------------------- ranks: counts against each row's own thresholds
@@ -733,24 +859,8 @@ __global__ __launch_bounds__(kThreads) void k_pair_rank(int64_t N, const float* 
 // far apart, so the column tiles are not one range but a few.  cross_spans leaves them in LDS as ascending disjoint spans of column
 // tiles, and the tile loop — the same five lines — stands once inside a loop over the spans; a column tile that holds no candidate of
 // any of the 64 rows is never loaded or scored.  With one span (two large graphs) the loop is the one k_pair_topk runs.
-// The existing kernels are left as they are on purpose: their register allocation moves with the range logic (NOTEBOOK 2026-10-19).
-
-// The candidate columns [rlo[i], rhi[i]) of row u0 + i: the rows of the peer of the row's graph, clamped into [0, N] as row_ranges
-// clamps; nothing for a row past N, a row behind the last graph, peer = -1 or a peer outside the table.
-__device__ __forceinline__ void cross_ranges(int64_t N, int64_t u0, const int32_t* gp, int G, const int32_t* peer, int* rlo, int* rhi) {
-    if (threadIdx.x >= kPairTile) return;
-    const int64_t u = u0 + threadIdx.x;
-    int64_t lo = 0, hi = 0;
-    if (u < N) {
-        int a = 0, b = G;                                  // first graph whose end lies behind u
-        while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-        const int p = a < G ? peer[a] : -1;
-        if (p >= 0 && p < G) { lo = gp[p]; hi = gp[p + 1]; }
-        lo = lo < 0 ? 0 : (lo > N ? N : lo);               // whatever the tables hold, no column outside [0, N) is touched
-        hi = hi < lo ? lo : (hi > N ? N : hi);
-    }
-    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi;
-}
+// Each kernel below is cross_ranges and cross_spans, that loop, and the CONSUMER of its own-graph twin — topk_*, select_*, HistRun,
+// unite_bits, with candidate<false> on the raw score and no skip_self — called, not restated (NOTEBOOK 2026-10-20, tenth entry).
 
 // The column tiles that hold a candidate of any of the 64 rows: *ns ascending, disjoint, non-adjacent spans [ta[j], tb[j]).  Wave 0
 // does it behind the barrier that publishes the ranges; the caller's next barrier publishes the spans.  Rows of one graph follow each
@@ -786,9 +896,8 @@ __device__ __forceinline__ void cross_spans(const int* rlo, const int* rhi, int*
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_cross_topk(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
                                                          int k, float threshold, int32_t* idx, float* score, int32_t* n_above) {
-    constexpr int LDS_SC = 17;
     __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
-    __shared__ float sc[kPairTile * LDS_SC];
+    __shared__ float sc[kPairTile * kTopkScLd];
     __shared__ float lv[kPairTile * kTopkMax];
     __shared__ int li[kPairTile * kTopkMax];
     __shared__ int rlo[kPairTile], rhi[kPairTile], ta[kPairTile], tb[kPairTile], ns;
@@ -796,7 +905,7 @@ __global__ __launch_bounds__(kThreads) void k_cross_topk(int64_t N, const float*
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
     cross_ranges(N, u0, gp, G, peer, rlo, rhi);
     const int srow = 16 * w + (lane >> 2), sub = lane & 3;
-    for (int j = sub; j < kTopkMax; j += 4) { lv[srow * kTopkMax + j] = -INFINITY; li[srow * kTopkMax + j] = INT_MAX; }
+    topk_init(lv, li, srow, sub);
     __syncthreads();
     cross_spans(rlo, rhi, ta, tb, &ns);
     __syncthreads();
@@ -820,48 +929,12 @@ __global__ __launch_bounds__(kThreads) void k_cross_topk(int64_t N, const float*
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                wave_lds_fence();                              // the previous block's reads are done
-#pragma unroll
-                for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * LDS_SC + r] = acc[c][g];
-                wave_lds_fence();
                 const int64_t cb = ct * kPairTile + 16 * c;
-                for (int st = 0; st < 4; ++st) {
-                    const int64_t col = cb + 4 * st + sub;
-                    const float v = sc[srow * LDS_SC + 4 * st + sub];
-                    float rep;
-                    const bool valid = candidate<false>(v, col, su, mylo, myhi, no, no, rep);
-                    cnt += (valid && rep > threshold) ? 1 : 0;
-                    const bool pass = valid && pair_better(v, (int)col, lv[srow * kTopkMax + k - 1], li[srow * kTopkMax + k - 1]);
-                    if (__ballot(pass) == 0ull) continue;
-                    for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
-                        if (pass && sub == turn) {
-                            float* L = lv + srow * kTopkMax;
-                            int* I = li + srow * kTopkMax;
-                            if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
-                                int pos = k - 1;
-                                while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
-                                    L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
-                                }
-                                L[pos] = v; I[pos] = (int)col;
-                            }
-                        }
-                        wave_lds_fence();
-                    }
-                }
+                topk_block(acc[c], cb, su, mylo, myhi, k, no, threshold, no, sc, lv, li, cnt, w, r, q, srow, sub);
             }
         }
     }
-    wave_lds_fence();
-    cnt += __shfl_xor(cnt, 1, 64);
-    cnt += __shfl_xor(cnt, 2, 64);
-    if (su < N) {
-        if (sub == 0) n_above[su] = cnt;
-        for (int j = sub; j < k; j += 4) {
-            const int id = li[srow * kTopkMax + j];
-            idx[su * k + j] = id == INT_MAX ? -1 : id;
-            score[su * k + j] = id == INT_MAX ? -INFINITY : lv[srow * kTopkMax + j];
-        }
-    }
+    topk_write(N, su, k, no, cnt, lv, li, idx, score, n_above, srow, sub);
 }
 
 // k_pair_select's consumer — the decision where the score lies, FILL = false: counts, FILL = true: ballot, prefix popcount and the row's
@@ -880,21 +953,10 @@ __global__ __launch_bounds__(kThreads) void k_cross_select(int64_t N, const floa
     __syncthreads();
     const int64_t row0 = u0 + 16 * w;
     const int spans = ns, no = 0;
-    // the lane's four rows 4 q + g: candidate range, slots, cursor
     int mylo[4], myhi[4], cnt[4];
     int64_t base[4];
     uint64_t room[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int lr = 16 * w + 4 * q + g;
-        mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; cnt[g] = 0;
-        base[g] = 0; room[g] = 0;
-        if (FILL && u0 + lr < N) {
-            const int64_t b = row_ptr[u0 + lr], e0 = row_ptr[u0 + lr + 1], e = e0 < cap ? e0 : cap;
-            base[g] = b;
-            room[g] = e > b ? (uint64_t)e - (uint64_t)b : 0ull;     // exact for any b < e
-        }
-    }
+    select_rows<FILL>(N, u0, rlo, rhi, row_ptr, cap, mylo, myhi, cnt, base, room);
     float a[H / 4];
     load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
     for (int sp = 0; sp < spans; ++sp) {
@@ -915,53 +977,12 @@ __global__ __launch_bounds__(kThreads) void k_cross_select(int64_t N, const floa
                 for (int g = 0; g < 4; ++g) {
                     float rep;
                     const bool pass = candidate<false>(acc[c][g], col, row0 + 4 * q + g, mylo[g], myhi[g], no, no, rep) && rep > threshold;
-                    if constexpr (!FILL) { cnt[g] += pass ? 1 : 0; continue; }
-                    const unsigned bits = (unsigned)(__ballot(pass) >> (16 * q)) & 0xffffu;    // the row's block, bit = column
-                    const uint64_t i = (uint64_t)(unsigned)cnt[g] + (uint64_t)__popc(bits & ((1u << r) - 1u));
-                    cnt[g] += __popc(bits);
-                    if (pass && i < room[g]) {                  // i < room: base + i < min(row_ptr[u+1], cap), no overflow
-                        const int64_t pos = base[g] + (int64_t)i;
-                        if (pos >= 0) {
-                            col_out[pos] = (int32_t)col;
-                            if (score_out != nullptr) score_out[pos] = rep;
-                        }
-                    }
+                    select_entry<FILL>(pass, rep, col, cnt[g], base[g], room[g], col_out, score_out);
                 }
             }
         }
     }
-    if (!FILL) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            int n = cnt[g];
-            n += __shfl_xor(n, 1, 64);
-            n += __shfl_xor(n, 2, 64);
-            n += __shfl_xor(n, 4, 64);
-            n += __shfl_xor(n, 8, 64);
-            const int64_t u = row0 + 4 * q + g;
-            if (r == 0 && u < N) n_sel[u] = n;
-        }
-    }
-}
-
-// cross_ranges with the row's graph index beside its range (rgi[i] < max(G, 1): a row of hist), as row_ranges<true> leaves it.  A
-// function of its own: the three kernels above keep the cross_ranges they were compiled with.
-__device__ __forceinline__ void cross_ranges_gi(int64_t N, int64_t u0, const int32_t* gp, int G, const int32_t* peer, int* rlo, int* rhi,
-                                                int* rgi) {
-    if (threadIdx.x >= kPairTile) return;
-    const int64_t u = u0 + threadIdx.x;
-    int64_t lo = 0, hi = 0;
-    int gi = 0;
-    if (u < N) {
-        int a = 0, b = G;                                  // first graph whose end lies behind u
-        while (a < b) { const int m = (a + b) >> 1; if ((int64_t)gp[m + 1] <= u) a = m + 1; else b = m; }
-        const int p = a < G ? peer[a] : -1;
-        if (a < G) gi = a;
-        if (p >= 0 && p < G) { lo = gp[p]; hi = gp[p + 1]; }
-        lo = lo < 0 ? 0 : (lo > N ? N : lo);               // whatever the tables hold, no column outside [0, N) is touched
-        hi = hi < lo ? lo : (hi > N ? N : hi);
-    }
-    rlo[threadIdx.x] = (int)lo; rhi[threadIdx.x] = (int)hi; rgi[threadIdx.x] = gi;
+    if (!FILL) select_counts(N, row0, cnt, n_sel);
 }
 
 // ---------------------------------------------------------------------------------- cross classes straight from the walk
@@ -1018,12 +1039,7 @@ __global__ __launch_bounds__(kThreads) void k_cross_union(int64_t N, const float
                     bits |= pass ? 1u << (4 * c + g) : 0u;
                 }
             }
-            while (bits != 0) {                                 // row < N and mylo <= col < myhi <= N: both ids inside parent
-                const int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                const int u = (int)(row0 + 4 * q + (b & 3)), v = (int)(ct * kPairTile + 16 * (b >> 2) + r);
-                if (u != v) uf_unite(parent, u, v, status);
-            }
+            unite_bits<true>(bits, row0, ct, parent, status);   // row < N and mylo <= col < myhi <= N: both ids inside parent
         }
     }
 }
@@ -1040,7 +1056,7 @@ __global__ __launch_bounds__(kThreads) void k_cross_union(int64_t N, const float
 // 4,112 B = 41,240 B with the counters' alignment; 24,856 B at H = 64, 16,664 B at H = 32, 12,568 B at H = 16.  Registers and waves
 // per SIMD as the compiler's resource report has them (-Rpass-analysis=kernel-resource-usage): H = 128: 153 VGPRs + 16 AGPRs, 2 waves;
 // H = 64: 111 + 16, 4 waves; H = 32: 88 + 16, 4 waves; H = 16: 77 + 16, 5 waves — against 2 / 3 / 4 / 5 of k_cross_select<H, false>
-// (174, 116, 85 and 70 VGPRs + 16): the histogram costs the count walk no occupancy at any width.  Registers bound it, not LDS: the
+// (176, 116, 85 and 69 VGPRs + 16): the histogram costs the count walk no occupancy at any width.  Registers bound it, not LDS: the
 // waves the registers allow are at most five workgroups per CU, 5 x 12,568 B at H = 16 and 2 x 41,240 B at H = 128 of its 160 KB.
 template <int H>
 __global__ __launch_bounds__(kThreads) void k_cross_hist(int64_t N, const float* y, int ldy, const int32_t* gp, int G, const int32_t* peer,
@@ -1051,32 +1067,27 @@ __global__ __launch_bounds__(kThreads) void k_cross_hist(int64_t N, const float*
     __shared__ unsigned long long lh[kHistSlots * (kHistMaxEdges + 1)];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
     const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
-    const int B1 = B + 1;
-    cross_ranges_gi(N, u0, gp, G, peer, rlo, rhi, rgi);    // rgi: a row of hist
-    for (int i = threadIdx.x; i < kHistTable; i += kThreads) el[i] = i < B ? edges[i] : INFINITY;
-    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) lh[i] = 0ull;
+    cross_ranges<true>(N, u0, gp, G, peer, rlo, rhi, rgi); // rgi: a row of hist
+    HistRun::tables(el, lh, edges, B);
     __syncthreads();
     cross_spans(rlo, rhi, ta, tb, &ns);
     __syncthreads();
     const int64_t row0 = u0 + 16 * w;
-    const int64_t left = N - 1 - u0;                       // u0 < N: the tile's last row inside N
-    const int gfirst = rgi[0], glast = rgi[left < kPairTile - 1 ? (int)left : kPairTile - 1];
     const int spans = ns, no = 0;
+    HistRun run(B, top, N, u0, rgi);
+    auto flush = [&]() {
+        if (run.run_n > 0) {
+            if (run.run_gi == run.gfirst) atomicAdd(&lh[run.run_bin], (unsigned long long)run.run_n);
+            else if (run.run_gi == run.glast) atomicAdd(&lh[run.B1 + run.run_bin], (unsigned long long)run.run_n);
+            else atomicAdd(&hist[(int64_t)run.run_gi * run.B1 + run.run_bin], (unsigned long long)run.run_n);
+        }
+    };
     int mylo[4], myhi[4], mygi[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int lr = 16 * w + 4 * q + g;
         mylo[g] = rlo[lr]; myhi[g] = rhi[lr]; mygi[g] = rgi[lr];
     }
-    // the lane's run: run_n candidates of bin run_bin of graph run_gi that no atomic has seen yet
-    int run_gi = 0, run_bin = 0, run_n = 0;
-    auto flush = [&]() {
-        if (run_n > 0) {
-            if (run_gi == gfirst) atomicAdd(&lh[run_bin], (unsigned long long)run_n);
-            else if (run_gi == glast) atomicAdd(&lh[B1 + run_bin], (unsigned long long)run_n);
-            else atomicAdd(&hist[(int64_t)run_gi * B1 + run_bin], (unsigned long long)run_n);
-        }
-    };
     float a[H / 4];
     load_row_frags<H>(a, y, ldy, row0 + r, row0 + r < N, q);
     for (int sp = 0; sp < spans; ++sp) {
@@ -1091,38 +1102,11 @@ __global__ __launch_bounds__(kThreads) void k_cross_hist(int64_t N, const float*
             f32x4 acc[4];
             tile_scores<H>(acc, a, tl, r, q);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {                      // row by row: a run lasts as long as the row's scores stay in one bin
-                bool valid[4], any = false;
-                float rep[4];
-                int pos[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    valid[c] = candidate<false>(acc[c][g], ct * kPairTile + 16 * c + r, row0 + 4 * q + g, mylo[g], myhi[g], no, no, rep[c]);
-                    any = any || valid[c];
-                    pos[c] = 0;
-                }
-                if (__ballot(any) == 0ull) continue;           // the wave has no candidate in these rows of this tile
-                for (int step = top; step > 0; step >>= 1) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) pos[c] += rep[c] > el[pos[c] + step - 1] ? step : 0;   // <= 2 top - 2 < kHistTable
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (!valid[c]) continue;
-                    const int bin = pos[c] < B ? pos[c] : B;   // an ascending table never gives more; nothing else is indexed
-                    if (run_n > 0 && run_gi == mygi[g] && run_bin == bin) { ++run_n; continue; }
-                    flush();
-                    run_gi = mygi[g]; run_bin = bin; run_n = 1;
-                }
-            }
+            for (int g = 0; g < 4; ++g)
+                run.template row<false>(acc, g, ct, row0 + 4 * q + g, mylo[g], myhi[g], mygi[g], no, no, el, flush);
         }
     }
-    flush();
-    __syncthreads();
-    for (int i = threadIdx.x; i < kHistSlots * B1; i += kThreads) {
-        const unsigned long long n = lh[i];
-        if (n != 0ull) atomicAdd(&hist[(int64_t)(i < B1 ? gfirst : glast) * B1 + (i < B1 ? i : i - B1)], n);
-    }
+    run.finish(lh, hist, flush);
 }
 
 // ---------------------------------------------------------------------------------- unit rows
@@ -1234,85 +1218,6 @@ static void launch_row_tiles(K kernel, int64_t N, hipStream_t st, A... args) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((N + mgv::kPairTile - 1) / mgv::kPairTile)), dim3(mgv::kThreads), 0, st, args...);
 }
 
-extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
-                             int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
-    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // node ids and idx offsets are int32 on the host side
-    bool launch;
-    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    MGV_CHECK_ARG(idx != nullptr && score != nullptr && n_above != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_pair_topk<w>, N, st, N, s, lds, t, ldt, graph_ptr, G, k, sigmoid, threshold, skip_self, idx, score, n_above);
-    });
-}
-
-// the two count entries; sym: s = t = unit rows, and `sigmoid` / `skip_self` come in as 0
-static int select_count_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
-                            float threshold, int skip_self, bool sym, int32_t* n_sel, hipStream_t st) {
-    bool launch;
-    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    MGV_CHECK_ARG(n_sel != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_select<w, false, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, n_sel, nullptr, 0, nullptr, nullptr); };
-        if (sym) walk(std::true_type{}); else walk(std::false_type{});
-    });
-}
-
-// the two fill entries, as select_count_run
-static int select_fill_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
-                           float threshold, int skip_self, bool sym, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score,
-                           hipStream_t st) {
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(cap >= 0);
-    bool launch;
-    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
-    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_select<w, true, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, nullptr, row_ptr, cap, col, score); };
-        if (sym) walk(std::true_type{}); else walk(std::false_type{});
-    });
-}
-
-extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
-                                     int sigmoid, float threshold, int skip_self, int32_t* n_sel, void* stream) {
-    return select_count_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, false, n_sel, (hipStream_t)stream);
-}
-
-extern "C" int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
-                                    int sigmoid, float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col,
-                                    float* score, void* stream) {
-    return select_fill_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, threshold, skip_self, false, row_ptr, cap, col, score,
-                           (hipStream_t)stream);
-}
-
-extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm, void* stream) {
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(N >= 0);
-    if (N == 0) return MGV_OK;
-    MGV_CHECK_ARG(mgv::pair_rows_ok(x, ldx, H) && mgv::pair_rows_ok(y, ldy, H));
-    hipStream_t st = (hipStream_t)stream;
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        constexpr int HH = w, rows = mgv::kThreads / (HH / 4);
-        hipLaunchKernelGGL(mgv::k_row_unit<HH>, dim3(mgv::grid_for((N + rows - 1) / rows, 8)), dim3(mgv::kThreads), 0, st, N, x, ldx, eps, y, ldy, norm);
-    });
-}
-
-extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
-                                    int32_t* n_sel, void* stream) {
-    return select_count_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, threshold, 0, true, n_sel, (hipStream_t)stream);
-}
-
-extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
-                                   const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
-    return select_fill_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, threshold, 0, true, row_ptr, cap, col, score, (hipStream_t)stream);
-}
-
 // the arguments the cross entries share, in the order of the walk entries: the width, both tables present, pair_walk_args on (y, y),
 // then every entry of peer in [-1, G) — the table is read back whole (G int32s, one more small blocking copy beside graph_ptr's ends)
 static int cross_walk_args(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, hipStream_t st,
@@ -1332,72 +1237,180 @@ static int cross_walk_args(int H, int64_t N, const float* y, int ldy, const int3
     return MGV_OK;
 }
 
-extern "C" int mgv_cross_topk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, int k,
-                              float threshold, int32_t* idx, float* score, int32_t* n_above, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+// What the entries of one walk share, in its three forms.  general: rows s against rows t, each row's candidates its own graph (the
+// whole batch without a table).  sym: s = t = unit rows, row u takes only v > u; `sigmoid` and `skip_self` are 0.  cross: s = t = unit
+// rows, the candidates of a row of graph g are the rows of graph peer[g]; `sigmoid` and `skip_self` are 0.
+// The form selects the argument check and the kernel; every check sequence behind it exists once, in the *_run helpers below.
+enum class Walk { general, sym, cross };
+struct WalkIn {
+    Walk form;
+    int H;
+    int64_t N;
+    const float* s;
+    int lds;
+    const float* t;
+    int ldt;
+    const int32_t* graph_ptr;
+    int G;
+    const int32_t* peer;               // cross only
+    int sigmoid, skip_self;
+    hipStream_t st;
+};
+
+static WalkIn pair_walk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                        int skip_self, void* stream) {
+    return {Walk::general, H, N, s, lds, t, ldt, graph_ptr, G, nullptr, sigmoid, skip_self, (hipStream_t)stream};
+}
+
+static WalkIn sym_walk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, void* stream) {
+    return {Walk::sym, H, N, y, ldy, y, ldy, graph_ptr, G, nullptr, 0, 0, (hipStream_t)stream};
+}
+
+static WalkIn cross_walk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, void* stream) {
+    return {Walk::cross, H, N, y, ldy, y, ldy, graph_ptr, G, peer, 0, 0, (hipStream_t)stream};
+}
+
+static int walk_args(const WalkIn& in, bool* launch) {
+    if (in.form == Walk::cross) return cross_walk_args(in.H, in.N, in.s, in.lds, in.graph_ptr, in.G, in.peer, in.st, launch);
+    return pair_walk_args(in.H, in.N, in.s, in.lds, in.t, in.ldt, in.graph_ptr, in.G, in.st, launch);
+}
+
+static int topk_run(const WalkIn& in, int k, float threshold, int32_t* idx, float* score, int32_t* n_above) {
+    if (!mgv::pair_h_ok(in.H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(k >= 1 && k <= mgv::kTopkMax);
-    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kTopkMax);          // as mgv_pair_topk
+    MGV_CHECK_ARG(in.N >= 0 && in.N <= 0x7fffffffLL / mgv::kTopkMax);    // node ids and idx offsets are int32 on the host side
     bool launch;
-    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
+    const int rc = walk_args(in, &launch);
     if (rc != MGV_OK || !launch) return rc;
     MGV_CHECK_ARG(idx != nullptr && score != nullptr && n_above != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_cross_topk<w>, N, st, N, y, ldy, graph_ptr, G, peer, k, threshold, idx, score, n_above);
+    return launch_width(mgv::AllWidths{}, in.H, [&](auto w) {
+        if (in.form == Walk::cross) {
+            launch_row_tiles(mgv::k_cross_topk<w>, in.N, in.st, in.N, in.s, in.lds, in.graph_ptr, in.G, in.peer, k, threshold, idx, score,
+                             n_above);
+        } else {
+            launch_row_tiles(mgv::k_pair_topk<w>, in.N, in.st, in.N, in.s, in.lds, in.t, in.ldt, in.graph_ptr, in.G, k, in.sigmoid, threshold,
+                             in.skip_self, idx, score, n_above);
+        }
     });
+}
+
+// the selection kernel of a form: FILL = false counts into n_sel, FILL = true fills col / score
+template <int W, bool FILL>
+static void launch_select(const WalkIn& in, float threshold, int32_t* n_sel, const int64_t* row_ptr, int64_t cap, int32_t* col,
+                          float* score) {
+    auto own = [&](auto sym) {
+        launch_row_tiles(mgv::k_pair_select<W, FILL, sym>, in.N, in.st, in.N, in.s, in.lds, in.t, in.ldt, in.graph_ptr, in.G, in.sigmoid,
+                         threshold, in.skip_self, n_sel, row_ptr, cap, col, score);
+    };
+    if (in.form == Walk::cross) {
+        launch_row_tiles(mgv::k_cross_select<W, FILL>, in.N, in.st, in.N, in.s, in.lds, in.graph_ptr, in.G, in.peer, threshold, n_sel,
+                         row_ptr, cap, col, score);
+    } else if (in.form == Walk::sym) {
+        own(std::true_type{});
+    } else {
+        own(std::false_type{});
+    }
+}
+
+// the three count entries
+static int select_count_run(const WalkIn& in, float threshold, int32_t* n_sel) {
+    bool launch;
+    const int rc = walk_args(in, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(n_sel != nullptr);
+    return launch_width(mgv::AllWidths{}, in.H,
+                        [&](auto w) { launch_select<w, false>(in, threshold, n_sel, nullptr, 0, nullptr, nullptr); });
+}
+
+// the three fill entries
+static int select_fill_run(const WalkIn& in, float threshold, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score) {
+    if (!mgv::pair_h_ok(in.H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(cap >= 0);
+    bool launch;
+    const int rc = walk_args(in, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
+    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
+    return launch_width(mgv::AllWidths{}, in.H, [&](auto w) { launch_select<w, true>(in, threshold, nullptr, row_ptr, cap, col, score); });
+}
+
+extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
+                             int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
+    return topk_run(pair_walk(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, stream), k, threshold, idx, score, n_above);
+}
+
+extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                     int sigmoid, float threshold, int skip_self, int32_t* n_sel, void* stream) {
+    return select_count_run(pair_walk(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, stream), threshold, n_sel);
+}
+
+extern "C" int mgv_pair_select_fill(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,
+                                    int sigmoid, float threshold, int skip_self, const int64_t* row_ptr, int64_t cap, int32_t* col,
+                                    float* score, void* stream) {
+    return select_fill_run(pair_walk(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, stream), threshold, row_ptr, cap, col, score);
+}
+
+extern "C" int mgv_row_unit(int H, int64_t N, const float* x, int ldx, float eps, float* y, int ldy, float* norm, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(N >= 0);
+    if (N == 0) return MGV_OK;
+    MGV_CHECK_ARG(mgv::pair_rows_ok(x, ldx, H) && mgv::pair_rows_ok(y, ldy, H));
+    hipStream_t st = (hipStream_t)stream;
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        constexpr int HH = w, rows = mgv::kThreads / (HH / 4);
+        hipLaunchKernelGGL(mgv::k_row_unit<HH>, dim3(mgv::grid_for((N + rows - 1) / rows, 8)), dim3(mgv::kThreads), 0, st, N, x, ldx, eps, y, ldy, norm);
+    });
+}
+
+extern "C" int mgv_sim_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
+                                    int32_t* n_sel, void* stream) {
+    return select_count_run(sym_walk(H, N, y, ldy, graph_ptr, G, stream), threshold, n_sel);
+}
+
+extern "C" int mgv_sim_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold,
+                                   const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
+    return select_fill_run(sym_walk(H, N, y, ldy, graph_ptr, G, stream), threshold, row_ptr, cap, col, score);
+}
+
+extern "C" int mgv_cross_topk(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer, int k,
+                              float threshold, int32_t* idx, float* score, int32_t* n_above, void* stream) {
+    return topk_run(cross_walk(H, N, y, ldy, graph_ptr, G, peer, stream), k, threshold, idx, score, n_above);
 }
 
 extern "C" int mgv_cross_select_count(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
                                       float threshold, int32_t* n_sel, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    bool launch;
-    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    MGV_CHECK_ARG(n_sel != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_cross_select<w, false>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, n_sel, nullptr, 0, nullptr, nullptr);
-    });
+    return select_count_run(cross_walk(H, N, y, ldy, graph_ptr, G, peer, stream), threshold, n_sel);
 }
 
 extern "C" int mgv_cross_select_fill(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
                                      float threshold, const int64_t* row_ptr, int64_t cap, int32_t* col, float* score, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(cap >= 0);
+    return select_fill_run(cross_walk(H, N, y, ldy, graph_ptr, G, peer, stream), threshold, row_ptr, cap, col, score);
+}
+
+// the two class entries (sym or cross): the walk unites in `parent` what the fill of that form would list
+static int union_run(const WalkIn& in, float threshold, int32_t* parent, int32_t* status) {
     bool launch;
-    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
-    if (rc != MGV_OK || !launch) return rc;
-    if (cap == 0) return MGV_OK;                                          // no slot: nothing can be written
-    MGV_CHECK_ARG(row_ptr != nullptr && col != nullptr);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_cross_select<w, true>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, nullptr, row_ptr, cap, col, score);
+    const int rc = walk_args(in, &launch);
+    if (rc != MGV_OK) return rc;
+    MGV_CHECK_ARG(status != nullptr && (in.N == 0 || parent != nullptr));
+    if (!launch) return MGV_OK;
+    return launch_width(mgv::AllWidths{}, in.H, [&](auto w) {
+        if (in.form == Walk::cross) {
+            launch_row_tiles(mgv::k_cross_union<w>, in.N, in.st, in.N, in.s, in.lds, in.graph_ptr, in.G, in.peer, threshold, parent, status);
+        } else {
+            launch_row_tiles(mgv::k_sim_union<w>, in.N, in.st, in.N, in.s, in.lds, in.graph_ptr, in.G, threshold, parent, status);
+        }
     });
 }
 
 extern "C" int mgv_sim_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, float threshold, int32_t* parent,
                              int32_t* status, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    bool launch;
-    const int rc = pair_walk_args(H, N, y, ldy, y, ldy, graph_ptr, G, st, &launch);
-    if (rc != MGV_OK) return rc;
-    MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
-    if (!launch) return MGV_OK;
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_sim_union<w>, N, st, N, y, ldy, graph_ptr, G, threshold, parent, status);
-    });
+    return union_run(sym_walk(H, N, y, ldy, graph_ptr, G, stream), threshold, parent, status);
 }
 
 extern "C" int mgv_cross_union(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
                                float threshold, int32_t* parent, int32_t* status, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    bool launch;
-    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
-    if (rc != MGV_OK) return rc;
-    MGV_CHECK_ARG(status != nullptr && (N == 0 || parent != nullptr));
-    if (!launch) return MGV_OK;
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_cross_union<w>, N, st, N, y, ldy, graph_ptr, G, peer, threshold, parent, status);
-    });
+    return union_run(cross_walk(H, N, y, ldy, graph_ptr, G, peer, stream), threshold, parent, status);
 }
 
 // the table of a profile entry (1 <= B <= kHistMaxEdges, edges not NULL) must ascend strictly and hold no NaN: it is read back, like the
@@ -1419,59 +1432,52 @@ static int hist_top(int B) {
     return top;
 }
 
-// the two profile entries: checks in the order of the selection entries, then the table; *launch = false: hist is zero and nothing is left to do
-static int pair_hist_run(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
-                         int skip_self, bool sym, const float* edges, int B, int64_t* hist, hipStream_t st) {
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+// the three profile entries: checks in the order of the selection entries, then the table; *launch = false: hist is zero and nothing is
+// left to do.  hist has a row per graph and one row without a table; the cross form, whose table is never NULL, has none at G = 0.
+static int hist_run(const WalkIn& in, const float* edges, int B, int64_t* hist) {
+    if (!mgv::pair_h_ok(in.H)) return MGV_EUNSUPPORTED;
     MGV_CHECK_ARG(B >= 1 && B <= mgv::kHistMaxEdges && edges != nullptr && hist != nullptr);
     bool launch;
-    const int rc = pair_walk_args(H, N, s, lds, t, ldt, graph_ptr, G, st, &launch);
+    const int rc = walk_args(in, &launch);
     if (rc != MGV_OK) return rc;
-    const int ok = hist_edges_check(edges, B, st);
+    const int ok = hist_edges_check(edges, B, in.st);
     if (ok != MGV_OK) return ok;
-    const int64_t rows = G > 1 ? G : 1;
-    hipError_t err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)rows * (size_t)(B + 1), st);
-    if (err != hipSuccess) return (int)err;
-    if (!launch) return MGV_OK;
-    const int top = hist_top(B);
-    unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        auto walk = [&](auto form) { launch_row_tiles(mgv::k_pair_hist<w, form>, N, st, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, edges, B, top, h); };
-        if (sym) walk(std::true_type{}); else walk(std::false_type{});
-    });
-}
-
-extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
-                             int skip_self, const float* edges, int B, int64_t* hist, void* stream) {
-    return pair_hist_run(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, false, edges, B, hist, (hipStream_t)stream);
-}
-
-extern "C" int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B,
-                            int64_t* hist, void* stream) {
-    return pair_hist_run(H, N, y, ldy, y, ldy, graph_ptr, G, 0, 0, true, edges, B, hist, (hipStream_t)stream);
-}
-
-// the cross profile: the checks of the profile entries for edges, B and hist, those of the cross entries for the rest
-extern "C" int mgv_cross_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
-                              const float* edges, int B, int64_t* hist, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
-    MGV_CHECK_ARG(B >= 1 && B <= mgv::kHistMaxEdges && edges != nullptr && hist != nullptr);
-    bool launch;
-    const int rc = cross_walk_args(H, N, y, ldy, graph_ptr, G, peer, st, &launch);
-    if (rc != MGV_OK) return rc;
-    const int ok = hist_edges_check(edges, B, st);
-    if (ok != MGV_OK) return ok;
-    if (G > 0) {
-        hipError_t err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)G * (size_t)(B + 1), st);
+    const int64_t rows = in.form == Walk::cross ? in.G : (in.G > 1 ? in.G : 1);
+    if (rows > 0) {
+        hipError_t err = hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)rows * (size_t)(B + 1), in.st);
         if (err != hipSuccess) return (int)err;
     }
     if (!launch) return MGV_OK;
     const int top = hist_top(B);
     unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
-        launch_row_tiles(mgv::k_cross_hist<w>, N, st, N, y, ldy, graph_ptr, G, peer, edges, B, top, h);
+    return launch_width(mgv::AllWidths{}, in.H, [&](auto w) {
+        auto own = [&](auto sym) {
+            launch_row_tiles(mgv::k_pair_hist<w, sym>, in.N, in.st, in.N, in.s, in.lds, in.t, in.ldt, in.graph_ptr, in.G, in.sigmoid,
+                             in.skip_self, edges, B, top, h);
+        };
+        if (in.form == Walk::cross) {
+            launch_row_tiles(mgv::k_cross_hist<w>, in.N, in.st, in.N, in.s, in.lds, in.graph_ptr, in.G, in.peer, edges, B, top, h);
+        } else if (in.form == Walk::sym) {
+            own(std::true_type{});
+        } else {
+            own(std::false_type{});
+        }
     });
+}
+
+extern "C" int mgv_pair_hist(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int sigmoid,
+                             int skip_self, const float* edges, int B, int64_t* hist, void* stream) {
+    return hist_run(pair_walk(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, stream), edges, B, hist);
+}
+
+extern "C" int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const float* edges, int B,
+                            int64_t* hist, void* stream) {
+    return hist_run(sym_walk(H, N, y, ldy, graph_ptr, G, stream), edges, B, hist);
+}
+
+extern "C" int mgv_cross_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph_ptr, int G, const int32_t* peer,
+                              const float* edges, int B, int64_t* hist, void* stream) {
+    return hist_run(cross_walk(H, N, y, ldy, graph_ptr, G, peer, stream), edges, B, hist);
 }
 
 extern "C" int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,

@@ -318,6 +318,54 @@ def test_feature_extract_cross_classes_and_cross_equivalences_max(tmp_path, caps
     assert 'graph0: %d classes hold gates of it and of graph 1 at cos(hf) > 0.999' % spanning in text
 
 
+# ------------------------------------------------------------------------------------------------ the identity peer: the own-graph walk
+def _own(H):
+    """match_case with peer[g] = g: every row's candidates are the rows of its own graph, itself included."""
+    c = _case(H, 'involution')
+    return dict(c, peer=list(range(c['G'])))
+
+
+@pytest.mark.parametrize('H', HS)
+def test_hist_under_the_identity_peer_is_the_own_graph_hist(H):
+    """mgv_cross_hist with peer[g] = g against mgv_pair_hist(y, y, sigmoid = 0, skip_self = 0) on the same unit rows and edges, entry for
+    entry; tables of 1, 64 and 256 edges: a search of 1, 7 and 9 steps."""
+    dev = _dev()
+    c = _own(H)
+    (Hh, N, y, ldy, gpd, G, _), keep = _operands(dev, c)
+    for B in (1, 64, 256):
+        edges = np.asarray([0.25], dtype=np.float32) if B == 1 else np.linspace(-1.0, 1.01, B).astype(np.float32)
+        cross, intact = _hist(dev, c, edges)
+        e = torch.from_numpy(edges).to(dev)
+        h = Guarded(G * (B + 1), I64, dev)
+        _call('mgv_pair_hist', Hh, N, y, ldy, y, ldy, gpd, G, 0, 0, _ptr(e), B, _ptr(h.v))
+        own = h.v.cpu().view(G, B + 1)
+        print('XW identity hist H=%d B=%d | %d candidates | %d bins differ' % (H, B, int(own.sum()), int((cross != own).sum())))
+        assert cross.dtype == I64 and torch.equal(cross, own) and intact and h.intact(), B
+        assert int(own.sum()) > 0
+
+
+@pytest.mark.parametrize('H', HS)
+def test_union_under_the_identity_peer_gives_the_labels_of_the_own_graph_union(H):
+    """mgv_cross_union with peer[g] = g on a fresh forest, then mgv_cc_labels, against mgv_sim_union: the cross walk meets every pair
+    from both sides and the diagonal besides, and the components are the same."""
+    dev = _dev()
+    c = _own(H)
+    args, keep = _operands(dev, c)
+    N = c['N']
+    for thr in (0.999, 0.25):
+        cross, status, intact = _union(dev, c, thr, False)
+        parent, st, label = Guarded(N, I32, dev), Guarded(4, I32, dev), Guarded(N, I32, dev)
+        _call('mgv_cc_init', N, _ptr(parent.v), _ptr(st.v))
+        _call('mgv_sim_union', *args[:6], float(thr), _ptr(parent.v), _ptr(st.v))
+        _call('mgv_cc_labels', N, _ptr(parent.v), _ptr(label.v), None)
+        own = label.v.cpu()
+        classes = int((own == torch.arange(N)).sum())
+        print('XW identity union H=%d thr=%g | %d classes of %d nodes | %d labels differ' % (H, thr, classes, N, int((cross != own).sum())))
+        assert torch.equal(cross, own) and status == [0, 0, 0, 0] and st.v.tolist() == [0, 0, 0, 0], thr
+        assert intact and parent.intact() and st.intact() and label.intact()
+        assert classes < N                                  # the threshold unites somebody: the case has copies
+
+
 # ------------------------------------------------------------------------------------------------ refusals
 def test_refusals_are_return_codes_before_anything_is_launched_or_zeroed():
     dev = _dev()
