@@ -632,15 +632,15 @@ DIGCN_WIDTHS = (16, 32, 64, 128)          # csrc/mgv_launch.h AllWidths
 def digcn_scales(plan, reverse, alpha, beta, self_loops):
     """(r, c) of a DirectedGCNConv over plan.csr(reverse): r[i] = din(i)^-alpha, c[j] = dout(j)^-beta (digae_layer.py:98-105), one
     launch, kept on the plan per (direction, alpha, beta, self_loops)."""
-    cache = plan.__dict__.setdefault('_digcn_scales', {})
     key = (bool(reverse), float(alpha), float(beta), bool(self_loops))
-    if key not in cache:
+
+    def build():
         lp, op = plan.csr(reverse)[0], plan.csr(not reverse)[0]
         check(lp, I32, 'list_ptr'); check(op, I32, 'opp_ptr')
         rc = torch.empty(2, max(plan.N, 1), dtype=F32, device=lp.device)
         _hip.call('mgv_digcn_scales', plan.N, ptr(lp), ptr(op), key[1], key[2], int(key[3]), ptr(rc[0]), ptr(rc[1]))
-        cache[key] = (rc[0], rc[1])
-    return cache[key]
+        return (rc[0], rc[1])
+    return plan.cache.get('digcn_scales', key, build)
 
 
 def _digcn_gather(y, plan, reverse, outer, inner, mask, self_loops, relu):
@@ -783,12 +783,12 @@ PACKED_ROWS = {'0': 0, '2': 2}.get(os.environ.get('MGV_PACKED_ROWS', '1'), 1)
 
 def _sweep_rows(plan, forward=False):
     """(pointer, ints per row) of the rows the level kernels read; `forward`: a sweep forward (counts the plan's steps)."""
-    if PACKED_ROWS and forward and plan.__dict__.get('_order_rows') is None:
-        steps = plan.__dict__.get('_sweep_steps', 0)
-        plan._sweep_steps = steps + 1
+    if PACKED_ROWS and forward and plan.cache.peek('order_rows') is None:
+        steps = plan.cache.peek('sweep_steps') or 0
+        plan.cache.put('sweep_steps', None, steps + 1, level_derived=True)
         if PACKED_ROWS == 2 or steps >= 1:
             plan.order_rows                  # (built here, on the step's stream: 0.43 ms once; the first step's backward keeps the span rows)
-    if PACKED_ROWS and plan.__dict__.get('_order_rows') is not None:
+    if PACKED_ROWS and plan.cache.peek('order_rows') is not None:
         return ptr(plan.order_rows), 32
     return ptr(plan.order_span), 4
 

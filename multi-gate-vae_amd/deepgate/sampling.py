@@ -157,9 +157,8 @@ def negative_sampling_device(plan, num_neg_samples=None, generator=None, graph_p
     (v, u) of listed edges (u, v) — the candidates link_ranking and predict_links rank a link against, where the reference's draw
     (dg_ae_model_aig.py:115-119) crosses graphs.  Same seed, same count; with neither given, today's calls and today's bits."""
     N, dev = plan.N, plan.device
-    if getattr(plan, 'num_self_loops', None) is None:
-        plan.count_self_loops()              # (one host read-back per plan; GraphPlan.warm does it on the prefetcher's stream for fresh batches)
-    E = (plan.E - plan.num_self_loops) + N if num_neg_samples is None else int(num_neg_samples)
+    loops = plan.count_self_loops()          # (one host read-back per plan; GraphPlan.warm does it on the prefetcher's stream for fresh batches)
+    E = (plan.E - loops) + N if num_neg_samples is None else int(num_neg_samples)
     R = reverse_count(reverse, E if plan.E > 0 else 0)          # (no edge to reverse: no reversed slot)
     base = generator.initial_seed() if generator is not None else torch.initial_seed()
     seed = (base * 0x9E3779B97F4A7C15 + next(_CALLS) * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF

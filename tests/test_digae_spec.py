@@ -173,7 +173,9 @@ def test_no_colour_tables_for_an_encoder_without_half_rounds():
     assert half(None) == [8]
     plan = deepgate_plan()
     plan.warm(torch.zeros(plan.N, dtype=torch.uint8), [])
-    assert getattr(plan, '_stage1', None) is None and getattr(plan, '_quotient', None) is None
+    assert 'first_stage' not in plan.cache and 'quotient' not in plan.cache and 'tagged' not in plan.cache
+    plan.warm(torch.zeros(plan.N, dtype=torch.uint8), 0)     # (the same call with half rounds to expect does build the first-stage table)
+    assert 'first_stage' in plan.cache
 
 
 def deepgate_plan():

@@ -150,10 +150,10 @@ def test_prefetched_batches_arrive_with_their_quotient_stages_built():
     pf.close()
     from deepgate.graph_plan import GraphPlan
     for b in batches:
-        built = b._mgv_plan._quotient
-        assert built[0] is b._mgv_plan.xcls and 4 in built[1]      # built by the worker, not by the call below
-        q = b._mgv_plan.quotient(b._mgv_plan.xcls, 4)
-        assert q is built[1][4] and len(q) >= 2 and 'sum_levels' in q[-1], len(q)
+        built = b._mgv_plan.cache.peek('quotient', 4)
+        assert built is not None                                   # built by the worker, not by the call below
+        q = b._mgv_plan.quotient(b._mgv_plan.xcls, 4)              # (for this xcls: the call hits only on the tensor the stages were built from)
+        assert q is built and len(q) >= 2 and 'sum_levels' in q[-1], len(q)
         alone = GraphPlan(b.edge_index, b.x.shape[0]).quotient(b._mgv_plan.xcls, 4)
         assert [s_['C'] for s_ in q] == [s_['C'] for s_ in alone]
 

@@ -274,9 +274,9 @@ def _same_tables(a, b, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize('case', ['aig_hubs', 'xmg', 'long_runs'])
 def test_device_built_stage_tables_equal_the_torch_composition(case):
-    """GraphPlan._quotient_dev (every table of a refinement stage by the plan builder's kernels: radix sort of the keys, runs ->
+    """plan_device.quotient_stages (every table of a refinement stage by the plan builder's kernels: radix sort of the keys, runs ->
     colours, representatives' lists, stable sort by previous colour, segment tables level by level) against the torch composition
-    of the same tables in GraphPlan.quotient, on the same device plan: the same colour NUMBERING and every table equal, field by
+    of the same tables (plan_torch.quotient_stages around the device's keys and check), on the same device plan: the same colour NUMBERING and every table equal, field by
     field.  Cases: twin hubs whose lists go to the sort-based check; five gate types; few colours with hundreds of thousands of
     members (several table levels, partial rows, the radix path of the stable sort)."""
     if not torch.cuda.is_available():
@@ -307,7 +307,7 @@ def test_device_built_stage_tables_equal_the_torch_composition(case):
     try:
         GraphPlan.QUOTIENT_DEVICE = True
         got = plan.quotient(xcls, stages_n)
-        plan._quotient = None
+        plan.cache.drop('quotient')
         GraphPlan.QUOTIENT_DEVICE = False
         ref = plan.quotient(xcls, stages_n)
     finally:

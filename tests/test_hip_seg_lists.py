@@ -261,7 +261,7 @@ def test_parameter_gradients_do_not_depend_on_the_route(name, stages):
     import deepgate
     from deepgate import ops
     plan, xcls, quot = _plan(dev, name)
-    plan._quotient[1][4] = quot[stages]                  # what the encoder's request for 2R = 4 stages finds
+    plan.cache.put('quotient', 4, quot[stages], held=(xcls,))       # what the encoder's request for 2R = 4 stages finds
     H = 64
     torch.manual_seed(23)
     enc = deepgate.digae_layer.MultiGCNEncoder(2, H, 6, True, True).to(dev)
@@ -271,15 +271,15 @@ def test_parameter_gradients_do_not_depend_on_the_route(name, stages):
     try:
         for flag in (True, False):
             ops.SEG_LISTS = flag
-            plan.__dict__.pop('_seg_entries', None)
+            plan.cache.drop('seg_entries')
             enc.zero_grad(set_to_none=True)
             out = enc(None, None, plan=plan, classes=(rows, xcls))
             (out * gy).sum().backward()
             res[flag] = [out.detach()] + [q.grad.detach().clone() for q in enc.parameters()]
-            assert ('_seg_entries' in plan.__dict__) == flag     # the list is built when, and only when, the route reads it
+            assert ('seg_entries' in plan.cache) == flag     # the list is built when, and only when, the route reads it
     finally:
         ops.SEG_LISTS = old
-        plan._quotient[1][4] = quot[4]
+        plan.cache.put('quotient', 4, quot[4], held=(xcls,))
     names = ['out'] + [k for k, _ in enc.named_parameters()]
     assert all(float(g.abs().max()) > 0 for g in res[True][1:])
     for nm, a, b in zip(names, res[True], res[False]):

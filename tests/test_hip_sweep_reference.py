@@ -371,8 +371,7 @@ def _through_ops(name, H, mm):
     dev = _dev()
     c, r64 = _case(name, H)
     plan = W.plan_of(c, dev)
-    plan.__dict__.pop('_order_rows', None)
-    plan.__dict__.pop('_sweep_steps', None)
+    plan.cache.drop('order_rows', 'sweep_steps')
     leaf = lambda t: t.to(dev).clone().requires_grad_(True)       # noqa: E731
     hs, u, Wvc, bvc, bih = (leaf(c[k]) for k in ('hs', 'attn_u', 'Wvc', 'bvc', 'bih'))
     r2 = c['h_prev'] is not None

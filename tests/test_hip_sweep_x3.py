@@ -118,7 +118,7 @@ def test_packed_sweep_rows_and_span_rows_give_the_same_sweep(T, levels, per):
     try:
         for packed in (2, 0):                # 2: packed rows from a plan's first step on (the default builds them at its second step)
             ops.PACKED_ROWS = packed
-            plan.__dict__.pop('_order_rows', None)
+            plan.cache.drop('order_rows')
             hs = hs0.clone().requires_grad_(True)
             par = [p.clone().requires_grad_(True) for p in par0]
             hf = ops.FuncSweepFn.apply(plan, hs, *par)
@@ -130,13 +130,12 @@ def test_packed_sweep_rows_and_span_rows_give_the_same_sweep(T, levels, per):
     # the default: span rows on a plan's first step, packed rows from its second step on
     ops.PACKED_ROWS = 1
     try:
-        plan.__dict__.pop('_order_rows', None)
-        plan.__dict__.pop('_sweep_steps', None)
+        plan.cache.drop('order_rows', 'sweep_steps')
         for step in range(2):
             hs = hs0.clone().requires_grad_(True)
             par = [p.clone().requires_grad_(True) for p in par0]
             hf = ops.FuncSweepFn.apply(plan, hs, *par)
-            assert (plan.__dict__.get('_order_rows') is not None) == (step == 1)
+            assert (plan.cache.peek('order_rows') is not None) == (step == 1)
             (hf * ghf).sum().backward()
             assert torch.equal(hf.detach(), results[0][0])
     finally:

@@ -251,7 +251,7 @@ def test_level_caches_are_dropped_when_levels_are_set_again():
     cid2 = cid.clone()
     assert p.tagged_idx(False, cid2) is not t1               # another tensor (even at a reused address): rebuilt
     p.set_levels(gate, lv, [1])                              # gate 2 no longer has an aggregator
-    assert '_slot_nodes' not in p.__dict__ and '_heavy_seg' not in p.__dict__ and '_tagged' not in p.__dict__
+    assert 'slot_nodes' not in p.cache and 'heavy_segments' not in p.cache and 'tagged' not in p.cache
     assert [s.tolist() for s in p.slot_nodes()] == [[2, 4]]
 
 

@@ -190,9 +190,9 @@ def test_first_stage_classes_equal_the_torch_composition(name):
         x = _xcls(N)
     plan = _plan(src, dst, N)
     in_ptr = R.csr(src, dst, N)[0]
-    for cap in (256, 1 << 15, 3):
-        plan._stage1 = None
-        got, want = plan.first_stage_classes(torch.from_numpy(x), max_classes=cap), R.first_stage(in_ptr, x, cap)
+    xt = torch.from_numpy(x)
+    for cap in (256, 1 << 15, 3):                        # (one tensor, three caps: the cap is part of the cache's key)
+        got, want = plan.first_stage_classes(xt, max_classes=cap), R.first_stage(in_ptr, x, cap)
         assert (got is None) == (want is None), cap
         if want is not None:
             assert got[1] == want[1]
@@ -205,6 +205,53 @@ def test_first_stage_classes_equal_the_torch_composition(name):
         assert C == want[1] and np.array_equal(cid, want[0]) and np.array_equal(cls_deg, np.diff(want[2])) and np.array_equal(cls_x, want[4])
     if name == 'degrees':
         assert set(np.diff(in_ptr)[:256].tolist()) == set(range(256))
+
+
+def test_the_table_cache_hits_on_objects_and_drops_the_level_derived_kinds():
+    """GraphPlan.cache on dag5: an entry hits only for the very tensors its key was derived from (equal contents under another
+    identity miss) and then returns the stored object; set_levels drops exactly the kinds declared level-derived where they are
+    built; the cap is part of first_stage_classes' key (256, 32768 and 3 in a row: three right answers without a reset)."""
+    g = LEVELLED['dag5']
+    plan = _plan(g['src'], g['dst'], g['N'])
+    gate, level = torch.from_numpy(np.asarray(g['gate'], dtype=np.float32)), torch.from_numpy(np.asarray(g['level'], dtype=np.int64))
+    plan.set_levels(gate, level, g['gate_ids'])
+    assert len(plan.cache) == 0 and 'quotient' not in plan.cache and plan.cache.peek('quotient', 2) is None
+    x = _xcls(g['N'])
+    xt, twin = torch.from_numpy(x), torch.from_numpy(x.copy())
+    q = plan.quotient(xt, 2, force=True)
+    assert len(q) == 2 and plan.quotient(xt, 2, force=True) is q and plan.cache.peek('quotient', 2) is q
+    q2 = plan.quotient(twin, 2, force=True)
+    assert q2 is not q and torch.equal(q2[-1]['cid'], q[-1]['cid']) and plan.cache.peek('quotient', 2) is q2
+    cid = q[0]['cid']
+    tagged = plan.tagged_idx(True, cid)
+    assert plan.tagged_idx(True, cid) is tagged and plan.tagged_idx(True, cid.clone()) is not tagged
+    entries = plan.seg_entries(q[-1]['rev'], *q[-1]['sum_levels'])
+    assert plan.seg_entries(q[-1]['rev'], *q[-1]['sum_levels']) is entries
+    order, tables = q[-1]['sum_levels']
+    again = plan.seg_entries(q[-1]['rev'], order.clone(), tables)
+    assert again is not entries and torch.equal(again[0], entries[0]) and torch.equal(again[1], entries[1])
+    in_ptr = R.csr(g['src'], g['dst'], g['N'])[0]
+    for cap in (256, 1 << 15, 3):
+        got, want = plan.first_stage_classes(xt, max_classes=cap), R.first_stage(in_ptr, x, cap)
+        assert (got is None) == (want is None) == (cap == 3), cap
+        assert plan.first_stage_classes(xt, max_classes=cap) is got and (want is None or got[1] == want[1])
+    assert plan.first_stage_classes(twin) is not plan.first_stage_classes(xt)
+    plan.count_self_loops(), plan.heavy(True), plan.heavy_segments(True, active_by_level=True), plan.slot_nodes(), plan.order_rows
+    plan.cache.put('sweep_steps', None, 1, level_derived=True)     # (as ops._sweep_rows counts a plan's forward sweeps)
+    from deepgate.prefetch import _record_all
+    seen = set()
+    _record_all(plan.__dict__, None, seen)               # (the prefetcher's walk over a plan's tensors reaches the cached tables and ends there)
+    assert id(entries) in seen and len(seen) < 200
+    level_derived = {'tagged', 'heavy_segments', 'slot_nodes', 'order_rows', 'sweep_steps'}
+    kept = {'quotient', 'seg_entries', 'first_stage', 'self_loops', 'heavy'}
+    kinds = lambda: {k for k in level_derived | kept if k in plan.cache}
+    assert kinds() == level_derived | kept
+    heavy, rows = plan.heavy(True), plan.order_rows
+    plan.set_levels(gate, level, g['gate_ids'])
+    assert kinds() == kept and plan.heavy(True) is heavy and plan.quotient(twin, 2, force=True) is q2
+    assert plan.cache.peek('sweep_steps') is None and plan.order_rows is not rows and torch.equal(plan.order_rows, rows)
+    plan.cache.drop('quotient', 'heavy')
+    assert kinds() == (kept | {'order_rows'}) - {'quotient', 'heavy'}
 
 
 SEG_COUNTS = {64: [0, 1, 64, 65, 4096, 4097, 3, 0], 2: [0, 1, 2, 3, 4, 5, 9, 0, 7]}

@@ -20,4 +20,4 @@ for rep in range(2):
     _, t4 = T(lambda: p.warm(xcls))
     _, t5 = T(lambda: ops.pair_lists(batch.tt_pair_index, batch.x.shape[0]))
     print('        warm (tagged lists, heavy rows) %.1f ms, pair lists %.1f ms' % (t4, t5))
-    p._stage1 = None; p.__dict__.pop('_tagged', None); p.__dict__.pop('_heavy', None); p.__dict__.pop('_heavy_seg', None)
+    p.cache.drop('first_stage', 'tagged', 'heavy', 'heavy_segments')
