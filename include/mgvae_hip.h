@@ -183,6 +183,22 @@ int mgv_linear_bwd_x3_supported(int M, int K);
 int mgv_linear_bwd_x3(int64_t N, const float* X1, int K1, int ld1, const float* X2, int K2, int ld2, const float* dY, int lddy,
                       int M, const void* wtpack_bf16, float* dW, float* db, float* dX1, int ldx1, float* dX2, int ldx2,
                       const float* R, int ldr, float* workspace, int64_t workspace_floats, void* stream);
+/* The hs seam at H = 64 in one pass each way.  Forward: HS[N][64] = [S | T] Wl^T + bl and ST[N][128] = HS Wd^T + bd, bit for bit
+ * what mgv_linear_fwd_x3 gives for the two layers (wlpack = mgv_wpack_bf16x3(Wl, 64, 128, 128, 0), wdpack = mgv_wpack_bf16x3(Wd, 128,
+ * 64, 64, 0); bl, bd nullable; S, T row-strided, lds, ldt >= 64, ldhs >= 64, ldst >= 128, multiples of 4).
+ * Backward: dhs = dST Wd + gHS (gHS nullable: the gradient of hs's other consumers) is formed per tile and never written; dS | dT =
+ * dhs Wl, dWl += dhs^T [S | T], dbl += colsum(dhs) carry the bits of mgv_linear_bwd_x3 on (64, 128) fed that dhs by
+ * mgv_linear_bwd_x3 on (128, 64) with R = gHS.  dWd += dST^T HS and dbd += colsum(dST) are summed over this kernel's partition of the
+ * tiles over workgroups and may differ from the stand-alone launch in rounding.  dbl, dbd nullable; all four ACCUMULATE.
+ * wltpack = mgv_wpack_bf16x3(Wl, 128, 64, 128, 1), wdtpack = mgv_wpack_bf16x3(Wd, 64, 128, 64, 1).  workspace: at least
+ * mgv_linear_pair_bwd_x3_ws_floats(N) floats, a shorter one is refused with MGV_EINVAL; N = 0 returns MGV_OK; both launch nothing. */
+int mgv_linear_pair_fwd_x3(int64_t N, const float* S, int lds, const float* T, int ldt, const void* wlpack_bf16, const float* bl,
+                           const void* wdpack_bf16, const float* bd, float* HS, int ldhs, float* ST, int ldst, void* stream);
+int mgv_linear_pair_bwd_x3_ws_floats(int64_t N);
+int mgv_linear_pair_bwd_x3(int64_t N, const float* dST, int lddst, const float* gHS, int ldghs, const float* HS, int ldhs,
+                           const float* S, int lds, const float* T, int ldt, const void* wltpack_bf16, const void* wdtpack_bf16,
+                           float* dS, int ldds, float* dT, int lddt, float* dWl, float* dbl, float* dWd, float* dbd,
+                           float* workspace, int64_t workspace_floats, void* stream);
 /* agg[i] = sum_{j in nbr(i)} h[j] added in list order, deg[i] = |nbr(i)| (deg may be NULL): the scatter-add half of
  * MessagePassing.propagate as used by AggConv called on its own (gcn_conv.py:34).  H in {16, 32, 64, 128} here and in the
  * row-sum entries below; any other H (0 and other non-multiples of 4 included) returns MGV_EUNSUPPORTED before anything is computed. */

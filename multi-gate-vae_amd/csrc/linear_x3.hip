@@ -436,7 +436,459 @@ int launch_linear_bwd_x3(const LinX3Args& a, int64_t ws_floats, hipStream_t st) 
     MGV_LAUNCH_RET();
 }
 
+// ---------------------------------------------------------------------------------------------- the hs seam (H = 64)
+// hs = hs_linear([s|t]) and st = hs_decompose(hs) meet at hs: run as two Linears, hs is written and read straight back, and in the
+// backward so is dhs.  The pair kernels make one pass each way: the forward forms st from the hs tile it still holds in LDS, the
+// backward forms dhs = dst Wd + ghs per tile and feeds it to hs_linear's backward without a trip through memory.  Every product is
+// the one the stand-alone kernels make (same planes, same k-step order, same mma_x3 chain), so the results carry the same bits.
+struct LinPairArgs {
+    int64_t N;
+    const float* S; int lds;  const float* T; int ldt;      // the two 64-column inputs of hs_linear, row-strided
+    const __bf16* wl; const float* bl;                       // forward: pack of Wl [64 x 128]; backward: of its [128 x 64] transposed view
+    const __bf16* wd; const float* bd;                       // forward: pack of Wd [128 x 64]; backward: of its [64 x 128] transposed view
+    float* HS; int ldhs; float* ST; int ldst;                // forward outputs
+    const float* dST; int lddst; const float* gHS; int ldghs; const float* hs; int ldh;      // backward inputs (gHS nullable)
+    float* dS; int ldds; float* dT; int lddt;
+    float* slab_l; float* slab_d;                            // per-workgroup partials of (dWl, dbl) and (dWd, dbd)
+    int want_dbl, want_dbd;
+};
+
+struct PairFwdGeom {
+    using GL = LinFwdGeom<64, 128>;                          // hs = [s|t] Wl^T + bl
+    using GD = LinFwdGeom<128, 64>;                          // st = hs Wd^T + bd
+    // the hs planes lie over the head of the (dead) s|t planes; the staged st tile over their tail and the staged hs tile
+    static constexpr int o_st = 2 * GD::PB;
+    static constexpr int smem_bytes = GL::smem_bytes;
+    static constexpr int NT = 512, PF = kTileRows * 128 / 4 / NT;
+    static_assert(o_st + kTileRows * GD::LDY * 4 <= smem_bytes && o_st <= GL::o_y && o_st % 16 == 0, "the staged st tile must fit behind the hs planes");
+};
+
+// 8 waves: the hs product as 4 column tiles x 2 row halves, the st product as 8 column tiles (which wave forms an entry does not
+// change its bits: every entry is one zero-initialised accumulator over ascending k-steps).  Two workgroups per CU.
+__global__ __launch_bounds__(PairFwdGeom::NT) __attribute__((amdgpu_waves_per_eu(4))) void k_linear_pair_fwd_x3(LinPairArgs a) {
+    using P = PairFwdGeom;
+    using GL = P::GL;
+    using GD = P::GD;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    __bf16* x_hi = reinterpret_cast<__bf16*>(smem_raw);
+    __bf16* x_lo = reinterpret_cast<__bf16*>(smem_raw + GL::PB);
+    float* s_y = reinterpret_cast<float*>(smem_raw + GL::o_y);
+    __bf16* h_hi = reinterpret_cast<__bf16*>(smem_raw);
+    __bf16* h_lo = reinterpret_cast<__bf16*>(smem_raw + GD::PB);
+    float* s_st = reinterpret_cast<float*>(smem_raw + P::o_st);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int wc = w % 4, wr = w / 4;
+    // this wave's weight fragments of both layers, for the whole launch
+    bf16x8 lh[GL::KS], ll[GL::KS], dh[GD::KS], dl[GD::KS];
+#pragma unroll
+    for (int ks = 0; ks < GL::KS; ++ks) {
+        const int wo = (wc * GL::KS + ks) * 512 + lane * 8;
+        lh[ks] = ldfrag(a.wl + wo); ll[ks] = ldfrag(a.wl + 64 * 128 + wo);
+    }
+#pragma unroll
+    for (int ks = 0; ks < GD::KS; ++ks) {
+        const int wo = (w * GD::KS + ks) * 512 + lane * 8;
+        dh[ks] = ldfrag(a.wd + wo); dl[ks] = ldfrag(a.wd + 128 * 64 + wo);
+    }
+    const float bias_l = a.bl ? a.bl[wc * 16 + r] : 0.f, bias_d = a.bd ? a.bd[w * 16 + r] : 0.f;
+    const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
+    f32x4 pf[P::PF];
+    auto prefetch = [&](int64_t tile) {
+        const int64_t first = tile * kTileRows;
+#pragma unroll
+        for (int u = 0; u < P::PF; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            if (first + row < a.N) pf[u] = *reinterpret_cast<const f32x4*>(c4 < 64 ? a.S + (first + row) * a.lds + c4 : a.T + (first + row) * a.ldt + (c4 - 64));
+            else pf[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    int64_t tile = blockIdx.x;
+    if (tile < ntiles) prefetch(tile);
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t first = tile * kTileRows;
+#pragma unroll
+        for (int u = 0; u < P::PF; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            bf16x4 hi, lo;
+            split4(f4x(pf[u]), hi, lo);
+            st_bf4(x_hi + row * GL::LDP + c4, hi); st_bf4(x_lo + row * GL::LDP + c4, lo);
+        }
+        lds_barrier();
+        if (tile + gridDim.x < ntiles) prefetch(tile + gridDim.x);
+        {   // hs as k_linear_fwd_x3<64, 128> forms it
+            f32x4 acc[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < GL::KS; ++ks)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int off = ((wr * 2 + i) * 16 + r) * GL::LDP + 32 * ks + 8 * q;
+                    mma_x3(acc[i], ldfrag(x_hi + off), ldfrag(x_lo + off), lh[ks], ll[ks]);
+                }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s_y[((wr * 2 + i) * 16 + q * 4 + e) * GL::LDY + wc * 16 + r] = acc[i][e] + bias_l;
+        }
+        lds_barrier();      // the staged hs tile is whole; nobody reads the s|t planes any more
+        // hs rows out, and the same fp32 values split into the planes the decompose product reads (what its own kernel makes of
+        // the rows it loads back: the round trip through memory is exact)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 16, c4 = (f % 16) * 4;
+            const float4 v = ld4(s_y + row * GL::LDY + c4);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
+            st_bf4(h_hi + row * GD::LDP + c4, hi); st_bf4(h_lo + row * GD::LDP + c4, lo);
+            if (first + row < a.N) st4(a.HS + (first + row) * a.ldhs + c4, v);
+        }
+        lds_barrier();
+        {   // st as k_linear_fwd_x3<128, 64> forms it
+            f32x4 acc[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < GD::KS; ++ks)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int off = (i * 16 + r) * GD::LDP + 32 * ks + 8 * q;
+                    mma_x3(acc[i], ldfrag(h_hi + off), ldfrag(h_lo + off), dh[ks], dl[ks]);
+                }
+            // (the staged st tile lies clear of the hs planes; what it covers was last read before the two barriers above)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s_st[(i * 16 + q * 4 + e) * GD::LDY + w * 16 + r] = acc[i][e] + bias_d;
+        }
+        lds_barrier();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            if (first + row < a.N) st4(a.ST + (first + row) * a.ldst + c4, ld4(s_st + row * GD::LDY + c4));
+        }
+        lds_barrier();      // the next tile's s|t planes overwrite the staged st rows
+    }
+}
+
+// Backward of the pair on the grid, tile walk and slab rows of k_linear_bwd_x3<64, 128, 8, 2, 2> (hs_linear's backward), per tile:
+//   dWd += dst^T hs, dbd += colsum(dst)                 as k_linear_bwd_x3<128, 64, 8, 4, 1> accumulates them
+//   dhs  = dst Wd + ghs                                  its DX phase with ghs as the residual, kept in LDS, split into planes
+//   dWl += dhs^T [s|t], dbl += colsum(dhs), ds|dt = dhs Wl      as k_linear_bwd_x3<64, 128, 8, 2, 2> makes them from a dhs it loads
+// ds|dt, dWl and dbl carry the bits of the two launches.  dWd and dbd are summed over THIS kernel's partition of the tiles over
+// workgroups, which need not be the stand-alone decompose backward's: they may differ from it in rounding.
+// LDS (bytes): R1 [0, 34816) the dst planes, then the staged dhs, then the s|t planes, then the staged ds|dt; R2 [34816, 53248) the
+// hs planes, then the dhs planes; behind them the Wd^T fragments of k-steps >= 1 (k-step 0 and all of Wl^T live in registers).
+// Loads in flight: dst and hs of the NEXT tile during the second half of a tile, s|t and ghs of THIS tile during its first half.
+// One workgroup per CU at a time (amdgpu_waves_per_eu(2): 240 VGPRs, none spilled) on the two-per-CU grid whose slab rows it keeps:
+// held to the 128 registers of two resident workgroups it spills 117 of them and takes 4.75 ms at N = 4,194,304 against 1.57 ms.
+struct PairBwdGeom {
+    static constexpr int NW = 8, NT = 64 * NW;
+    using WL = LinWgGeom<64, 128, NW, 2>;                    // dWl: dY = dhs (LDG = 72), X = s|t (LDX = 136)
+    using WD = LinWgGeom<128, 64, NW, 4>;                    // dWd: dY = dst (LDG = 136), X = hs (LDX = 72)
+    using DL = LinDxGeom<64, 128, NW>;                       // ds|dt = dhs Wl
+    using DD = LinDxGeom<128, 64, NW>;                       // dhs = dst Wd
+    static constexpr int KSR = 1, KSL = DD::KS - KSR, WTL = DD::WPC * KSL * 512;
+    static constexpr int o_r2 = 2 * WD::GPB, o_wt = o_r2 + 2 * WD::XPB;
+    static constexpr int smem_bytes = o_wt + 2 * WTL * 2;
+    static_assert(2 * WL::XPB == 2 * WD::GPB && 2 * WL::GPB == 2 * WD::XPB, "the two layers' planes share R1 and R2");
+    static_assert(kTileRows * DD::LDY * 4 <= o_r2 && kTileRows * DL::LDY * 4 <= o_r2, "the staged tiles must fit R1");
+    static_assert(2 * NT * 16 <= o_r2, "the column-sum partials must fit R1");
+    static constexpr int slab_l = 64 * 128 + 64, slab_d = 128 * 64 + 128;
+};
+
+__global__ __launch_bounds__(PairBwdGeom::NT) __attribute__((amdgpu_waves_per_eu(2))) void k_linear_pair_bwd_x3(LinPairArgs a) {
+    using P = PairBwdGeom;
+    using WL = P::WL;
+    using WD = P::WD;
+    using DL = P::DL;
+    using DD = P::DD;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    // R1
+    __bf16* g_hi = reinterpret_cast<__bf16*>(smem_raw);                          // dst planes
+    __bf16* g_lo = reinterpret_cast<__bf16*>(smem_raw + WD::GPB);
+    float* s_dhs = reinterpret_cast<float*>(smem_raw);                           // staged dst Wd
+    __bf16* x_hi = reinterpret_cast<__bf16*>(smem_raw);                          // s|t planes
+    __bf16* x_lo = reinterpret_cast<__bf16*>(smem_raw + WL::XPB);
+    float* s_dx = reinterpret_cast<float*>(smem_raw);                            // staged ds|dt
+    // R2
+    __bf16* h_hi = reinterpret_cast<__bf16*>(smem_raw + P::o_r2);                // hs planes
+    __bf16* h_lo = reinterpret_cast<__bf16*>(smem_raw + P::o_r2 + WD::XPB);
+    __bf16* e_hi = reinterpret_cast<__bf16*>(smem_raw + P::o_r2);                // dhs planes
+    __bf16* e_lo = reinterpret_cast<__bf16*>(smem_raw + P::o_r2 + WL::GPB);
+    __bf16* s_wt = reinterpret_cast<__bf16*>(smem_raw + P::o_wt);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int it0l = (w / WL::WJ) * WL::ITW, jt0l = (w % WL::WJ) * WL::JTW;
+    const int it0d = (w / WD::WJ) * WD::ITW, jt0d = (w % WD::WJ) * WD::JTW;
+    const int dwc = w % DD::WPC, dwr = w / DD::WPC;          // dhs: column tile dwc, row tiles dwr * 2 ..; ds|dt: column tile w, all rows
+    f32x4 accl[WL::ITW][WL::JTW], accd[WD::ITW][WD::JTW];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { accl[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; accd[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    static_assert(WL::ITW == 2 && WL::JTW == 2 && WD::ITW == 2 && WD::JTW == 2, "2 x 2 output tiles per wave, both layers");
+    float4 dbl = zero4(), dbd = zero4();
+    // transposed weight fragments: Wl^T (both k-steps) and k-step 0 of Wd^T in registers, the rest of Wd^T in LDS
+    bf16x8 th[DL::KS], tl[DL::KS];
+#pragma unroll
+    for (int ks = 0; ks < DL::KS; ++ks) {
+        const int wo = (w * DL::KS + ks) * 512 + lane * 8;
+        th[ks] = ldfrag(a.wl + wo); tl[ks] = ldfrag(a.wl + 64 * 128 + wo);
+    }
+    const bf16x8 uh = ldfrag(a.wd + (dwc * DD::KS) * 512 + lane * 8), ul = ldfrag(a.wd + 128 * 64 + (dwc * DD::KS) * 512 + lane * 8);
+    for (int c = tid; c < 2 * P::WTL / 8; c += P::NT) {     // (the first tile barrier publishes it)
+        const int plane = c / (P::WTL / 8), blk = (c % (P::WTL / 8)) / 64, ct = blk / P::KSL, ks = P::KSR + blk % P::KSL;
+        *reinterpret_cast<bf16x8*>(s_wt + c * 8) = ldfrag(a.wd + plane * 128 * 64 + (ct * DD::KS + ks) * 512 + (c % 64) * 8);
+    }
+    auto wt_lds = [&](int plane, int ks) { return ldfrag(s_wt + plane * P::WTL + (dwc * P::KSL + ks - P::KSR) * 512 + lane * 8); };
+    const int64_t ntiles = (a.N + kTileRows - 1) / kTileRows;
+    f32x4 pa[4], pb[2];          // dst and hs of a tile, then its s|t and ghs
+    auto fetch_gh = [&](int64_t tile) {
+        const int64_t first = tile * kTileRows;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = tid + u * P::NT;
+            const int64_t row = first + f / 32; const int c4 = (f % 32) * 4;
+            pa[u] = row < a.N ? *reinterpret_cast<const f32x4*>(a.dST + row * a.lddst + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + u * P::NT;
+            const int64_t row = first + f / 16; const int c4 = (f % 16) * 4;
+            pb[u] = row < a.N ? *reinterpret_cast<const f32x4*>(a.hs + row * a.ldh + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto fetch_xr = [&](int64_t tile) {
+        const int64_t first = tile * kTileRows;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = tid + u * P::NT;
+            const int64_t row = first + f / 32; const int c4 = (f % 32) * 4;
+            pa[u] = row < a.N ? *reinterpret_cast<const f32x4*>(c4 < 64 ? a.S + row * a.lds + c4 : a.T + row * a.ldt + (c4 - 64)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + u * P::NT;
+            const int64_t row = first + f / 16; const int c4 = (f % 16) * 4;
+            pb[u] = (a.gHS && row < a.N) ? *reinterpret_cast<const f32x4*>(a.gHS + row * a.ldghs + c4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    int64_t tile = blockIdx.x;
+    if (tile < ntiles) fetch_gh(tile);
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t first = tile * kTileRows;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            const float4 v = f4x(pa[u]);
+            dbd = add4(dbd, v);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
+            st_bf4(g_hi + row * WD::LDG + c4, hi); st_bf4(g_lo + row * WD::LDG + c4, lo);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 16, c4 = (f % 16) * 4;
+            bf16x4 hi, lo;
+            split4(f4x(pb[u]), hi, lo);
+            st_bf4(h_hi + row * WD::LDX + c4, hi); st_bf4(h_lo + row * WD::LDX + c4, lo);
+        }
+        lds_barrier();
+        fetch_xr(tile);
+        // dWd += dst^T hs
+#pragma unroll
+        for (int ks = 0; ks < kTileRows / 32; ++ks) {
+            bf16x8 bh[2], bl[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                bh[j] = ldfrag_tr2(h_hi, WD::LDX, 32 * ks, (jt0d + j) * 16);
+                bl[j] = ldfrag_tr2(h_lo, WD::LDX, 32 * ks, (jt0d + j) * 16);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const bf16x8 ah = ldfrag_tr2(g_hi, WD::LDG, 32 * ks, (it0d + i) * 16), al = ldfrag_tr2(g_lo, WD::LDG, 32 * ks, (it0d + i) * 16);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma_x3(accd[i][j], ah, al, bh[j], bl[j]);
+            }
+        }
+        {   // dst Wd, as the DX phase of the decompose backward forms it
+            f32x4 dacc[DD::RTW];
+#pragma unroll
+            for (int i = 0; i < DD::RTW; ++i) dacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < DD::KS; ++ks)
+#pragma unroll
+                for (int i = 0; i < DD::RTW; ++i) {
+                    const int off = ((dwr * DD::RTW + i) * 16 + r) * WD::LDG + 32 * ks + 8 * q;
+                    const bf16x8 gh = ldfrag(g_hi + off), gl = ldfrag(g_lo + off);
+                    if (ks < P::KSR) mma_x3(dacc[i], gh, gl, uh, ul);
+                    else mma_x3(dacc[i], gh, gl, wt_lds(0, ks), wt_lds(1, ks));
+                }
+            lds_barrier();      // nobody reads the dst and hs planes any more
+#pragma unroll
+            for (int i = 0; i < DD::RTW; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s_dhs[((dwr * DD::RTW + i) * 16 + q * 4 + e) * DD::LDY + dwc * 16 + r] = dacc[i][e] + 0.f;
+        }
+        lds_barrier();
+        // dhs = dst Wd + ghs in the stand-alone kernel's store-phase expression; the thread-to-entry map and the column sums are
+        // those of hs_linear's backward loading dhs from memory
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 16, c4 = (f % 16) * 4;
+            float4 v = ld4(s_dhs + row * DD::LDY + c4);
+            if (a.gHS) v = add4(v, f4x(pb[u]));
+            dbl = add4(dbl, v);
+            bf16x4 hi, lo;
+            split4(v, hi, lo);
+            st_bf4(e_hi + row * WL::LDG + c4, hi); st_bf4(e_lo + row * WL::LDG + c4, lo);
+        }
+        lds_barrier();          // the staged dhs is read; the s|t planes take its place
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            bf16x4 hi, lo;
+            split4(f4x(pa[u]), hi, lo);
+            st_bf4(x_hi + row * WL::LDX + c4, hi); st_bf4(x_lo + row * WL::LDX + c4, lo);
+        }
+        lds_barrier();
+        if (tile + gridDim.x < ntiles) fetch_gh(tile + gridDim.x);
+        // dWl += dhs^T [s|t]
+#pragma unroll
+        for (int ks = 0; ks < kTileRows / 32; ++ks) {
+            bf16x8 bh[2], bl[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                bh[j] = ldfrag_tr2(x_hi, WL::LDX, 32 * ks, (jt0l + j) * 16);
+                bl[j] = ldfrag_tr2(x_lo, WL::LDX, 32 * ks, (jt0l + j) * 16);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const bf16x8 ah = ldfrag_tr2(e_hi, WL::LDG, 32 * ks, (it0l + i) * 16), al = ldfrag_tr2(e_lo, WL::LDG, 32 * ks, (it0l + i) * 16);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) mma_x3(accl[i][j], ah, al, bh[j], bl[j]);
+            }
+        }
+        {   // ds|dt = dhs Wl, as the DX phase of hs_linear's backward forms it
+            f32x4 dacc[DL::RTW];
+#pragma unroll
+            for (int i = 0; i < DL::RTW; ++i) dacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < DL::KS; ++ks)
+#pragma unroll
+                for (int i = 0; i < DL::RTW; ++i) {
+                    const int off = (i * 16 + r) * WL::LDG + 32 * ks + 8 * q;
+                    mma_x3(dacc[i], ldfrag(e_hi + off), ldfrag(e_lo + off), th[ks], tl[ks]);
+                }
+            lds_barrier();      // nobody reads the s|t planes any more
+#pragma unroll
+            for (int i = 0; i < DL::RTW; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s_dx[(i * 16 + q * 4 + e) * DL::LDY + w * 16 + r] = dacc[i][e] + 0.f;
+        }
+        lds_barrier();
+#pragma unroll
+        for (int u = 0; u < DL::PF; ++u) {
+            const int f = tid + u * P::NT;
+            const int row = f / 32, c4 = (f % 32) * 4;
+            if (first + row < a.N) {
+                const float4 v = ld4(s_dx + row * DL::LDY + c4);
+                if (c4 < 64) st4(a.dS + (first + row) * a.ldds + c4, v);
+                else st4(a.dT + (first + row) * a.lddt + (c4 - 64), v);
+            }
+        }
+        lds_barrier();          // the next tile's dst planes overwrite the staged rows
+    }
+    // per-workgroup partials to this workgroup's slab rows (plain stores); k_slab_sum adds the rows in a fixed order
+    float* sl = a.slab_l + (int64_t)blockIdx.x * P::slab_l;
+    float* sd = a.slab_d + (int64_t)blockIdx.x * P::slab_d;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sl[((it0l + i) * 16 + q * 4 + e) * 128 + (jt0l + j) * 16 + r] = accl[i][j][e];
+                sd[((it0d + i) * 16 + q * 4 + e) * 64 + (jt0d + j) * 16 + r] = accd[i][j][e];
+            }
+    // column sums: one float4 per thread into R1, then a fixed-order sum over the threads of a column quad (the stand-alone order)
+    float4* s_part = reinterpret_cast<float4*>(smem_raw);
+    s_part[tid] = dbl; s_part[P::NT + tid] = dbd;
+    __syncthreads();
+    if (a.want_dbl && tid < 64) {
+        const int c4 = tid / 4, e = tid % 4;
+        float sum = 0.f;
+        for (int t = c4; t < P::NT; t += 16) { const float4 v = s_part[t]; sum += e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+        sl[64 * 128 + tid] = sum;
+    }
+    if (a.want_dbd && tid < 128) {
+        const int c4 = tid / 4, e = tid % 4;
+        float sum = 0.f;
+        for (int t = c4; t < P::NT; t += 32) { const float4 v = s_part[P::NT + t]; sum += e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+        sd[128 * 64 + tid] = sum;
+    }
+}
+
+inline int pair_bwd_grid(int64_t N) {      // the grid of hs_linear's backward (two workgroups of 8 waves per CU)
+    return grid_for((N + kTileRows - 1) / kTileRows, 2);
+}
+
 }  // namespace mgv
+
+extern "C" int mgv_linear_pair_fwd_x3(int64_t N, const float* S, int lds, const float* T, int ldt, const void* wlpack_bf16, const float* bl,
+                                      const void* wdpack_bf16, const float* bd, float* HS, int ldhs, float* ST, int ldst, void* stream) {
+    MGV_CHECK_ARG(N >= 0 && S && T && wlpack_bf16 && wdpack_bf16 && HS && ST);
+    MGV_CHECK_ARG(lds >= 64 && lds % 4 == 0 && ldt >= 64 && ldt % 4 == 0 && ldhs >= 64 && ldhs % 4 == 0 && ldst >= 128 && ldst % 4 == 0);
+    if (N == 0) return MGV_OK;
+    mgv::LinPairArgs a{};
+    a.N = N; a.S = S; a.lds = lds; a.T = T; a.ldt = ldt; a.wl = static_cast<const __bf16*>(wlpack_bf16); a.bl = bl;
+    a.wd = static_cast<const __bf16*>(wdpack_bf16); a.bd = bd; a.HS = HS; a.ldhs = ldhs; a.ST = ST; a.ldst = ldst;
+    using P = mgv::PairFwdGeom;
+    mgv::allow_lds<mgv::k_linear_pair_fwd_x3>();
+    const int grid = mgv::grid_for((N + mgv::kTileRows - 1) / mgv::kTileRows, 2);      // 16 waves per CU
+    hipLaunchKernelGGL(mgv::k_linear_pair_fwd_x3, dim3(grid), dim3(P::NT), P::smem_bytes, static_cast<hipStream_t>(stream), a);
+    MGV_LAUNCH_RET();
+}
+
+// floats of workspace mgv_linear_pair_bwd_x3 needs: per workgroup one row of (dWl, dbl) and one of (dWd, dbd) partials
+extern "C" int mgv_linear_pair_bwd_x3_ws_floats(int64_t N) {
+    if (N < 0) return 0;
+    return mgv::pair_bwd_grid(N) * (mgv::PairBwdGeom::slab_l + mgv::PairBwdGeom::slab_d);
+}
+
+extern "C" int mgv_linear_pair_bwd_x3(int64_t N, const float* dST, int lddst, const float* gHS, int ldghs, const float* HS, int ldhs,
+                                      const float* S, int lds, const float* T, int ldt, const void* wltpack_bf16, const void* wdtpack_bf16,
+                                      float* dS, int ldds, float* dT, int lddt, float* dWl, float* dbl, float* dWd, float* dbd,
+                                      float* workspace, int64_t workspace_floats, void* stream) {
+    MGV_CHECK_ARG(N >= 0 && dST && HS && S && T && wltpack_bf16 && wdtpack_bf16 && dS && dT && dWl && dWd);
+    MGV_CHECK_ARG(lddst >= 128 && lddst % 4 == 0 && (gHS == nullptr || (ldghs >= 64 && ldghs % 4 == 0)) && ldhs >= 64 && ldhs % 4 == 0);
+    MGV_CHECK_ARG(lds >= 64 && lds % 4 == 0 && ldt >= 64 && ldt % 4 == 0 && ldds >= 64 && ldds % 4 == 0 && lddt >= 64 && lddt % 4 == 0);
+    if (N == 0) return MGV_OK;
+    using P = mgv::PairBwdGeom;
+    const int grid = mgv::pair_bwd_grid(N);
+    if (workspace == nullptr || workspace_floats < (int64_t)grid * (P::slab_l + P::slab_d)) return MGV_EINVAL;
+    mgv::LinPairArgs a{};
+    a.N = N; a.dST = dST; a.lddst = lddst; a.gHS = gHS; a.ldghs = ldghs; a.hs = HS; a.ldh = ldhs; a.S = S; a.lds = lds; a.T = T; a.ldt = ldt;
+    a.wl = static_cast<const __bf16*>(wltpack_bf16); a.wd = static_cast<const __bf16*>(wdtpack_bf16);
+    a.dS = dS; a.ldds = ldds; a.dT = dT; a.lddt = lddt;
+    a.slab_l = workspace; a.slab_d = workspace + (int64_t)grid * P::slab_l; a.want_dbl = dbl != nullptr; a.want_dbd = dbd != nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    mgv::allow_lds<mgv::k_linear_pair_bwd_x3>();
+    hipLaunchKernelGGL(mgv::k_linear_pair_bwd_x3, dim3(grid), dim3(P::NT), P::smem_bytes, st, a);
+    mgv::launch_slab_sum<float, float>(a.slab_l, grid, P::slab_l, 64 * 128, dWl, st);
+    if (dbl) mgv::launch_slab_sum<float, float>(a.slab_l + 64 * 128, grid, P::slab_l, 64, dbl, st);
+    mgv::launch_slab_sum<float, float>(a.slab_d, grid, P::slab_d, 128 * 64, dWd, st);
+    if (dbd) mgv::launch_slab_sum<float, float>(a.slab_d + 128 * 64, grid, P::slab_d, 128, dbd, st);
+    MGV_LAUNCH_RET();
+}
 
 extern "C" int mgv_linear_x3_supported(int M, int K) {
     return (M == 64 && K == 128) || (M == 128 && K == 64) || (M == 64 && K == 64) || (M == 64 && K == 32) || (M == 32 && K == 64) ||

@@ -69,11 +69,17 @@ class FunctionalModel(nn.Module):
         rows = torch.eye(6, dtype=torch.float32, device=dev)          # one_hot(x[:,1], 6) rows
         enc = getattr(self, self.ENCODER_ATTR)
         s, t = enc(None, None, G.edge_index, plan=plan, classes=(rows, plan.xcls))
-        hs = ops.linear(s, self.hs_linear.weight, self.hs_linear.bias, x2=t)
+        st = None
+        if branch is not None and ops.linear_pair_ok(s, t, self.hs_linear.weight, self.hs_decompose.weight):
+            # hs and st = hs_decompose(hs) in one pass in front of the fork (ops.LinearPairFn): the branch starts at the sampler
+            # (of a variational model, at its link heads)
+            hs, st = ops.linear_pair(s, t, self.hs_linear.weight, self.hs_linear.bias, self.hs_decompose.weight, self.hs_decompose.bias)
+        else:
+            hs = ops.linear(s, self.hs_linear.weight, self.hs_linear.bias, x2=t)
         hs_in = hs
         if branch is not None:
-            with branch.fork(hs):
-                hs_in = branch.took(*self.recon_loss(hs, plan=plan, return_hs=True, **branch.recon_args))
+            with branch.fork(hs if st is None else st):
+                hs_in = branch.took(*self.recon_loss(hs, plan=plan, return_hs=True, st=st, **branch.recon_args))
         hf = ops.FuncSweepFn.apply(plan, hs_in, *self._sweep_params())
         if branch is not None:
             hf = branch.sweep_out(hf)
@@ -348,7 +354,7 @@ class FunctionalModel(nn.Module):
         return metrics.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
 
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, want_rank=False,
-                   expect_scale=1.0, graph_ptr=None, return_hs=False, sample=None, seed=None, eps=None):
+                   expect_scale=1.0, graph_ptr=None, return_hs=False, sample=None, seed=None, eps=None, st=None):
         """`plan` (optional): the batch's GraphPlan when pos_edge_index is the batch's own edge set (any
         order) — the positive half of the backward then needs no atomics.  `return_hs`: a fourth result, hs passed through the
         hs_decompose node (ops.linear_passthrough; hs itself when it needs no gradient): a second consumer of hs that reads THAT
@@ -359,11 +365,12 @@ class FunctionalModel(nn.Module):
         Variational model: the decoder reads z = VarHead(st) where it reads st otherwise, and the KL sums are kept for kl_loss().
         `sample`: add the noise (None: self.training, the VGAE convention; the reference's `sample` adds it in eval mode as well,
         DESIGN.md §7); `seed` fixes it (tests; by default one is drawn from torch's CPU generator, as pred_prob's); `eps` [N, 2H]
-        injects it."""
+        injects it.  `st`: hs_decompose(hs) where the caller has it already (ops.linear_pair made it with hs); hs then has no
+        consumer here and comes back as it is."""
         hs_pass = hs
-        if return_hs and hs.requires_grad:
+        if st is None and return_hs and hs.requires_grad:
             st, hs_pass = ops.linear_passthrough(hs, self.hs_decompose.weight, self.hs_decompose.bias)
-        else:
+        elif st is None:
             st = ops.linear(hs, self.hs_decompose.weight, self.hs_decompose.bias)
         if self.variational:
             sample = self.training if sample is None else bool(sample)

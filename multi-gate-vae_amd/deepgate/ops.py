@@ -468,6 +468,52 @@ def _rowmajor(t):
     return t.contiguous()
 
 
+def _linear_backward(x1, x2, W, has_b, needs, gy, g_pass=None):
+    """(gx1, gx2, gW, gb) of y = [x1 | x2] W^T + b for the upstream gy; `needs` as ctx.needs_input_grad of (x1, x2, W, b); g_pass
+    (optional) is added to gx1 in the input-gradient kernel's store phase."""
+    gy = _rowmajor(gy).contiguous()      # (a column slice of a wider gradient, e.g. behind torch.cat, arrives row-strided)
+    N, K1 = x1.shape
+    K2 = 0 if x2 is None else x2.shape[1]
+    M = W.shape[0]
+    gx1 = gx2 = gW = gb = None
+    def dgrad(Ws, Kx, res=None):    # gy [N, M] x Ws [M, Kx]: the transposed weight view is packed straight from W
+        if _lin_x3(Kx, M):
+            pack = torch.empty(2 * Ws.numel(), dtype=torch.bfloat16, device=W.device)
+            _pack_into(pack, 0, Ws, True)
+            return _lin_fwd(gy, None, None, None, Kx, wpack=pack, res=res)
+        return _lin_fwd(gy, None, Ws.t().contiguous(), None, Kx, res=res)
+    want_w = needs[2] or (has_b and needs[3])
+    if (FUSED_LINEAR_BWD and want_w and needs[0] and (x2 is None or needs[1]) and _lin_bwd_x3(M, K1 + K2)
+            and _lin_x3(K1, M) and (x2 is None or _lin_x3(K2, M))):
+        # input and weight gradients in one pass over gy (the same bits as the separate launches below)
+        pack = torch.empty(2 * W.numel(), dtype=torch.bfloat16, device=W.device)
+        _pack_into(pack, 0, W, True)
+        res = _rowmajor(check(g_pass.detach(), F32, 'g_pass')) if g_pass is not None else None
+        gx1 = torch.empty(N, K1, dtype=F32, device=W.device)
+        gx2 = torch.empty(N, K2, dtype=F32, device=W.device) if x2 is not None else None
+        gW = torch.zeros_like(W)
+        gb = torch.zeros(M, dtype=F32, device=W.device) if has_b else None
+        ws = workspace(_hip.call_value('mgv_linear_wgrad_x3_ws_floats', M, K1 + K2, N), W.device)
+        _hip.call('mgv_linear_bwd_x3', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0), ptr(gy), gy.stride(0),
+                  M, ptr(pack), ptr(gW), ptr(gb), ptr(gx1), K1, ptr(gx2), K2, ptr(res), 0 if res is None else res.stride(0), ptr(ws), ws.numel())
+        return gx1, gx2, gW, gb
+    if needs[0]:
+        gx1 = dgrad(W[:, :K1], K1, res=g_pass.detach() if g_pass is not None else None)
+    if x2 is not None and needs[1]:
+        gx2 = dgrad(W[:, K1:], K2)
+    if want_w:
+        gW = torch.zeros_like(W)
+        gb = torch.zeros(M, dtype=F32, device=W.device) if has_b else None
+        if _lin_x3(M, K1 + K2):
+            ws = workspace(_hip.call_value('mgv_linear_wgrad_x3_ws_floats', M, K1 + K2, N), W.device)
+            _hip.call('mgv_linear_wgrad_x3', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0),
+                      ptr(gy), gy.stride(0), M, ptr(gW), ptr(gb), ptr(ws), ws.numel())
+        else:
+            _hip.call('mgv_linear_wgrad', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0),
+                      ptr(gy), gy.stride(0), M, ptr(gW), ptr(gb))
+    return gx1, gx2, gW, gb
+
+
 class LinearFn(torch.autograd.Function):
     """y = [x1 | x2] W^T + b on the MFMA row-streaming kernel (x2 optional: fuses torch.cat).
     `passthrough`: also return x1 itself; a second consumer of x1 that reads THIS output hands its gradient to this node's
@@ -489,47 +535,7 @@ class LinearFn(torch.autograd.Function):
         x1, x2, W = ctx.saved_tensors
         if gy is None:                     # only the pass-through output was used
             return g_pass, None, None, None, None
-        gy = _rowmajor(gy).contiguous()      # (a column slice of a wider gradient, e.g. behind torch.cat, arrives row-strided)
-        N, K1 = x1.shape
-        K2 = 0 if x2 is None else x2.shape[1]
-        M = W.shape[0]
-        gx1 = gx2 = gW = gb = None
-        def dgrad(Ws, Kx, res=None):    # gy [N, M] x Ws [M, Kx]: the transposed weight view is packed straight from W
-            if _lin_x3(Kx, M):
-                pack = torch.empty(2 * Ws.numel(), dtype=torch.bfloat16, device=W.device)
-                _pack_into(pack, 0, Ws, True)
-                return _lin_fwd(gy, None, None, None, Kx, wpack=pack, res=res)
-            return _lin_fwd(gy, None, Ws.t().contiguous(), None, Kx, res=res)
-        want_w = ctx.needs_input_grad[2] or (ctx.has_b and ctx.needs_input_grad[3])
-        if (FUSED_LINEAR_BWD and want_w and ctx.needs_input_grad[0] and (x2 is None or ctx.needs_input_grad[1]) and _lin_bwd_x3(M, K1 + K2)
-                and _lin_x3(K1, M) and (x2 is None or _lin_x3(K2, M))):
-            # input and weight gradients in one pass over gy (the same bits as the separate launches below)
-            pack = torch.empty(2 * W.numel(), dtype=torch.bfloat16, device=W.device)
-            _pack_into(pack, 0, W, True)
-            res = _rowmajor(check(g_pass.detach(), F32, 'g_pass')) if g_pass is not None else None
-            gx1 = torch.empty(N, K1, dtype=F32, device=W.device)
-            gx2 = torch.empty(N, K2, dtype=F32, device=W.device) if x2 is not None else None
-            gW = torch.zeros_like(W)
-            gb = torch.zeros(M, dtype=F32, device=W.device) if ctx.has_b else None
-            ws = workspace(_hip.call_value('mgv_linear_wgrad_x3_ws_floats', M, K1 + K2, N), W.device)
-            _hip.call('mgv_linear_bwd_x3', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0), ptr(gy), gy.stride(0),
-                      M, ptr(pack), ptr(gW), ptr(gb), ptr(gx1), K1, ptr(gx2), K2, ptr(res), 0 if res is None else res.stride(0), ptr(ws), ws.numel())
-            return gx1, gx2, gW, gb, None
-        if ctx.needs_input_grad[0]:
-            gx1 = dgrad(W[:, :K1], K1, res=g_pass.detach() if g_pass is not None else None)
-        if x2 is not None and ctx.needs_input_grad[1]:
-            gx2 = dgrad(W[:, K1:], K2)
-        if want_w:
-            gW = torch.zeros_like(W)
-            gb = torch.zeros(M, dtype=F32, device=W.device) if ctx.has_b else None
-            if _lin_x3(M, K1 + K2):
-                ws = workspace(_hip.call_value('mgv_linear_wgrad_x3_ws_floats', M, K1 + K2, N), W.device)
-                _hip.call('mgv_linear_wgrad_x3', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0),
-                          ptr(gy), gy.stride(0), M, ptr(gW), ptr(gb), ptr(ws), ws.numel())
-            else:
-                _hip.call('mgv_linear_wgrad', N, ptr(x1), K1, x1.stride(0), ptr(x2), K2, 0 if x2 is None else x2.stride(0),
-                          ptr(gy), gy.stride(0), M, ptr(gW), ptr(gb))
-        return gx1, gx2, gW, gb, None
+        return _linear_backward(x1, x2, W, ctx.has_b, ctx.needs_input_grad, gy, g_pass) + (None,)
 
 
 def linear(x, W, b=None, x2=None):
@@ -539,6 +545,85 @@ def linear(x, W, b=None, x2=None):
 def linear_passthrough(x, W, b=None):
     """(y, x'): x' is x; feed x' to the other consumer of x and its gradient is added inside this Linear's input-gradient kernel."""
     return LinearFn.apply(x, None, W, b, True)
+
+
+# MGV_LINEAR_PAIR=0 keeps hs_linear and hs_decompose on their own launches for a same-process A/B: tests flip this flag
+LINEAR_PAIR = os.environ.get('MGV_LINEAR_PAIR', '1') != '0'
+# The pair serves batches from this many rows on: the size from which a step is bound by memory and not by launches (the boundary of
+# GraphPlan.QUOTIENT_MIN_NODES).  Below it the seam's passes cost nothing that can be measured, and the reconstruction branch keeps
+# the launch sequence tests/test_hip_step_branch.py and tests/test_hip_variational_model.py pin on their small batches.
+LINEAR_PAIR_MIN_ROWS = 131072
+
+
+def linear_pair_ok(s, t, Wl, Wd):
+    """Whether (hs, st) = linear_pair(s, t, ...) serves these tensors: a training pass at H = 64 in bf16x3 mode on the GPU."""
+    return (LINEAR_PAIR and s.shape[0] >= LINEAR_PAIR_MIN_ROWS and PRECISION == 'x3' and s.is_cuda and torch.is_grad_enabled() and tuple(Wl.shape) == (64, 128)
+            and tuple(Wd.shape) == (128, 64) and s.shape[1] == 64 and t.shape[1] == 64
+            and any(x.requires_grad for x in (s, t, Wl, Wd)))
+
+
+def _grad_in(g):
+    """An upstream gradient as the launchers take it: fp32 on the GPU (any row stride _rowmajor accepts)."""
+    if not g.is_cuda or g.dtype != F32:
+        raise HipLibraryError('gradient must be an fp32 GPU tensor (got %s on %s)' % (g.dtype, g.device))
+    return _rowmajor(g.detach())
+
+
+class LinearPairFn(torch.autograd.Function):
+    """(hs, st) = (hs_linear([s | t]), hs_decompose(hs)) in one pass over the rows (mgv_linear_pair_fwd_x3: the bits of the two
+    Linears), and their backward in one pass too: dhs = g_st Wd + g_hs lives per tile inside mgv_linear_pair_bwd_x3 and never in
+    memory.  A backward that gets no g_st, or that does not want every gradient, runs on the Linears' own kernels."""
+
+    @staticmethod
+    def forward(ctx, s, t, Wl, bl, Wd, bd):
+        sd, td = _rowmajor(s.detach()), _rowmajor(t.detach())
+        Wld, Wdd = Wl.detach().contiguous(), Wd.detach().contiguous()
+        check(sd, F32, 's'); check(td, F32, 't')
+        bld = check(bl.detach().contiguous(), F32, 'bl') if bl is not None else None
+        bdd = check(bd.detach().contiguous(), F32, 'bd') if bd is not None else None
+        N = sd.shape[0]
+        hs = torch.empty(N, 64, dtype=F32, device=sd.device)
+        st = torch.empty(N, 128, dtype=F32, device=sd.device)
+        _hip.call('mgv_linear_pair_fwd_x3', N, ptr(sd), sd.stride(0), ptr(td), td.stride(0), ptr(linear_wpack(check(Wld, F32, 'Wl'))), ptr(bld),
+                  ptr(linear_wpack(check(Wdd, F32, 'Wd'))), ptr(bdd), ptr(hs), 64, ptr(st), 128)
+        ctx.save_for_backward(sd, td, Wld, Wdd, hs)
+        ctx.has_b = (bl is not None, bd is not None)
+        ctx.set_materialize_grads(False)
+        return hs, st
+
+    @staticmethod
+    def backward(ctx, g_hs, g_st):
+        s, t, Wl, Wd, hs = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        has_bl, has_bd = ctx.has_b
+        if g_st is None or not (FUSED_LINEAR_BWD and all(need[:3]) and need[4]):
+            # the two Linears' own backward launches: hs_decompose's (g_hs rides in as its residual), then hs_linear's on that dhs
+            dhs, gWd, gbd = g_hs, None, None
+            if g_st is not None:
+                dhs, _, gWd, gbd = _linear_backward(hs, None, Wd, has_bd, (True, False, need[4], need[5]), g_st, g_hs)
+            if dhs is None:
+                return None, None, None, None, None, None
+            return _linear_backward(s, t, Wl, has_bl, need[:4], dhs) + (gWd, gbd)
+        dev = Wl.device
+        N = s.shape[0]
+        g_st = _grad_in(g_st)
+        g_hs = _grad_in(g_hs) if g_hs is not None else None
+        packs = torch.empty(4 * Wl.numel(), dtype=torch.bfloat16, device=dev)
+        _pack_into(packs, _pack_into(packs, 0, Wl, True), Wd, True)
+        gs, gt = torch.empty(N, 64, dtype=F32, device=dev), torch.empty(N, 64, dtype=F32, device=dev)
+        gWl, gWd = torch.zeros_like(Wl), torch.zeros_like(Wd)
+        gbl = torch.zeros(64, dtype=F32, device=dev) if has_bl else None
+        gbd = torch.zeros(128, dtype=F32, device=dev) if has_bd else None
+        ws = workspace(_hip.call_value('mgv_linear_pair_bwd_x3_ws_floats', N), dev)
+        _hip.call('mgv_linear_pair_bwd_x3', N, ptr(g_st), g_st.stride(0), ptr(g_hs), 0 if g_hs is None else g_hs.stride(0), ptr(hs), 64,
+                  ptr(s), s.stride(0), ptr(t), t.stride(0), ptr(packs), _hip.ctypes.c_void_p(packs.data_ptr() + 4 * Wl.numel()),
+                  ptr(gs), 64, ptr(gt), 64, ptr(gWl), ptr(gbl), ptr(gWd), ptr(gbd), ptr(ws), ws.numel())
+        return gs, gt, gWl, gbl, gWd, gbd
+
+
+def linear_pair(s, t, Wl, bl, Wd, bd):
+    """(hs, st) = (Linear(Wl, bl)([s | t]), Linear(Wd, bd)(hs)): call only where linear_pair_ok(s, t, Wl, Wd)."""
+    return LinearPairFn.apply(s, t, Wl, bl, Wd, bd)
 
 
 class RoundGhFn(torch.autograd.Function):
