@@ -562,11 +562,17 @@ def linear_pair_ok(s, t, Wl, Wd):
             and any(x.requires_grad for x in (s, t, Wl, Wd)))
 
 
+def _rows_in(t, name):
+    """A row matrix as the pair launchers take it: fp32 on the GPU, any row stride _rowmajor accepts (a column slice of a wider
+    matrix stays a view; anything else is copied)."""
+    if not t.is_cuda or t.dtype != F32:
+        raise HipLibraryError('%s must be an fp32 GPU tensor (got %s on %s)' % (name, t.dtype, t.device))
+    return _rowmajor(t.detach())
+
+
 def _grad_in(g):
-    """An upstream gradient as the launchers take it: fp32 on the GPU (any row stride _rowmajor accepts)."""
-    if not g.is_cuda or g.dtype != F32:
-        raise HipLibraryError('gradient must be an fp32 GPU tensor (got %s on %s)' % (g.dtype, g.device))
-    return _rowmajor(g.detach())
+    """An upstream gradient as the launchers take it."""
+    return _rows_in(g, 'gradient')
 
 
 class LinearPairFn(torch.autograd.Function):
@@ -576,9 +582,8 @@ class LinearPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, s, t, Wl, bl, Wd, bd):
-        sd, td = _rowmajor(s.detach()), _rowmajor(t.detach())
+        sd, td = _rows_in(s, 's'), _rows_in(t, 't')      # (check() refused the column slices _rowmajor had just let through)
         Wld, Wdd = Wl.detach().contiguous(), Wd.detach().contiguous()
-        check(sd, F32, 's'); check(td, F32, 't')
         bld = check(bl.detach().contiguous(), F32, 'bl') if bl is not None else None
         bdd = check(bd.detach().contiguous(), F32, 'bd') if bd is not None else None
         N = sd.shape[0]

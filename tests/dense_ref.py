@@ -9,6 +9,10 @@ which also asserts the properties of the builders and shows that the planted def
                                     the weights and bias of slot tile_slot[t]; tile_list (or None) names the tiles; 'named' = the node
                                     rows some listed tile names (the others must not be touched).  A tile of count 0 is ALLOWED by the
                                     header: it names no row and adds nothing.
+  pair(S, T, Wl, bl, Wd, bd, ...)   the hs seam of mgv_linear_pair_fwd_x3 / _bwd_x3, composed of linear(): HS = [S | T] Wl^T + bl,
+                                    ST = HS Wd^T + bd (of its own HS, and 'ST_given' of an HS handed in); with HS given, dhs = dST Wd + gHS
+                                    (an fp32 value in the kernel before it is split into planes), dS | dT = dhs Wl, dWl = dhs^T [S | T],
+                                    dbl = colsum(dhs), dWd = dST^T HS, dbd = colsum(dST)
   wpack(W, transpose)               the bf16 hi / lo bit patterns of mgv_wpack_bf16x3, fragment order
   gather_sum / seg_sum / class_expand / class_pull_sum
 
@@ -59,6 +63,8 @@ GEOMETRY = {
                       'linear_x3.hip launch_linear_fwd_x3: per_cu = min(4, 160 KiB / smem_bytes)'),
     'linear_wgrad_x3': (lambda s: min(1024 // (64 * X3_WGRAD_WAVES[s]), LDS_BYTES // x3_wgrad_smem(*s)), lambda s: TILE,
                         'linear_x3.hip launch_linear_wgrad_x3: per_cu = min(1024 / NT, 160 KiB / smem_bytes)'),
+    'linear_pair_fwd_x3': (lambda s: 2, lambda s: TILE, 'linear_x3.hip mgv_linear_pair_fwd_x3: grid = grid_for(ntiles, 2)'),
+    'linear_pair_bwd_x3': (lambda s: 2, lambda s: TILE, 'linear_x3.hip pair_bwd_grid: grid_for(ntiles, 2), the grid of hs_linear\'s backward'),
     'gather_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_gather_sum: row_grid<H>(N, 16) = grid_for(ceil(N / rows_per_block), 16)'),
     'seg_sum': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_seg_sum: row_grid<H>(n_seg, 16) = grid_for(ceil(n_seg / rows_per_block), 16)'),
     'class_expand': (lambda H: 16, lambda H: THREADS // (H // 4), 'dense.hip mgv_class_expand: row_grid<H>(N, 16) = grid_for(ceil(N / rows_per_block), 16)'),
@@ -231,6 +237,94 @@ def linear(X1, X2, W, b=None, R=None, dY=None, dtype=F64, mm='exact', mutate=Non
     return out
 
 
+PAIR = (64, 128)                   # the pair kernels serve one shape (Wl 64 x 128, Wd 128 x 64): the `shape` of their GEOMETRY entries
+PAIR_OUT = ('dS', 'dT', 'dWl', 'dbl', 'dWd', 'dbd')
+PAIR_SLAB = 64 * 128 + 64 + 128 * 64 + 128          # linear_x3.hip PairBwdGeom::slab_l + slab_d: workspace floats per workgroup
+
+
+def stale_rows(N, g):
+    """Row r of the second tile a workgroup of a grid of g visits -> the same row of its first tile (the row its stale registers
+    hold); the other rows themselves."""
+    rows = torch.arange(N)
+    second = (rows >= g * TILE) & (rows < 2 * g * TILE)
+    rows[second] -= g * TILE
+    return rows
+
+
+def last_visit_rows(N, g):
+    """[N][1] bool: the rows of the tile its workgroup (of a grid of g, round-robin) visits last."""
+    nt = (N + TILE - 1) // TILE
+    return (torch.arange(N) // TILE + g >= nt)[:, None]
+
+
+def pair(S_, T_, Wl, bl=None, Wd=None, bd=None, dST=None, gHS=None, HS=None, dtype=F64, mm='exact', mutate=None):
+    """{'HS', 'ST' (of that HS), 'ST_given' (HS handed in: of it); with dST: 'dhs', 'dS', 'dT', 'dWl', 'dbl', 'dWd', 'dbd' of the
+    backward whose given input is HS (None: this run's own HS); float64 without a defect: 'S'}.  Every product is linear()'s; what
+    the kernels keep unstored between two products (hs in LDS, dhs in LDS) is the float32 value linear() returns, handed on as it is.
+    S: |X| |Wl|^T + |bl| for HS, that scale times |Wd|^T + |bd| for ST, |HS| |Wd|^T + |bd| for ST_given; Sdhs = |dST| |Wd| + |gHS|,
+    and dS | dT, dWl, dbl take Sdhs as their operand's magnitude: Sdhs |Wl|, Sdhs^T |S | T|, colsum(Sdhs); dWd |dST|^T |HS|, dbd
+    colsum |dST|.
+    Defects (g = the grid): ('stale_fwd', g) S | T of the second tile a workgroup visits from its first tile's rows;
+    ('stale_bwd_gh', g) dST and HS so; ('stale_bwd_x', g) S | T of the backward so; ('stale_bwd_ghs', g) gHS alone so;
+    ('last_visit', out, g) a workgroup's sum `out` (dWd, dWl, dbl, dbd) kept from the tile it visits last only; ('no_ghs',) gHS
+    not added to dhs; ('dbl_no_ghs',); ('st_unbiased',) ST from hs before bl was added; ('drop_last_row',) the last row neither
+    written nor summed; ('drop_hilo_dhs',) the hi.lo term missing from dST Wd; ('dbd_half',) rows 32 .. 63 of each tile not in dbd."""
+    assert mm == 'exact' or dtype == F32
+    kind = mutate[0] if mutate else None
+    N = S_.shape[0]
+    drop = ('drop_last_row',) if kind == 'drop_last_row' else None
+    lin = lambda *a, **k: linear(*a, dtype=dtype, mm=mm, **k)      # noqa: E731
+    stale = stale_rows(N, mutate[1]) if kind and kind.startswith('stale') else None
+    Sf, Tf = (S_[stale], T_[stale]) if kind == 'stale_fwd' else (S_, T_)
+    f1 = lin(Sf, Tf, Wl, bl, mutate=drop)
+    out = {'HS': f1['Y']}
+
+    def st_of(h):
+        if kind == 'st_unbiased' and bl is not None:
+            h = (h.to(dtype) - bl.to(dtype)).to(F64)
+        return lin(h, None, Wd, bd, mutate=drop)
+
+    f2 = st_of(f1['Y'])
+    out['ST'] = f2['Y']
+    fg = None
+    if HS is not None:
+        fg = st_of(HS)
+        out['ST_given'] = fg['Y']
+    if dST is not None:
+        Hg = f1['Y'] if HS is None else HS
+        G, Hb, Xs, Xt, R = dST, Hg, S_, T_, None if kind == 'no_ghs' else gHS
+        if kind == 'stale_bwd_gh':
+            G, Hb = dST[stale], Hg[stale]
+        if kind == 'stale_bwd_x':
+            Xs, Xt = S_[stale], T_[stale]
+        if kind == 'stale_bwd_ghs' and R is not None:
+            R = gHS[stale]
+        d = lin(G, None, Wd.t(), None, R, mutate=('drop_hilo',) if kind == 'drop_hilo_dhs' else None)
+        dhs = d['Y']                                           # fp32 in the kernel: split into planes and summed into dbl as it is
+        bd_ = lin(Hb, None, Wd, None, None, G, mutate=drop)    # dWd, dbd
+        bl_ = lin(Xs, Xt, Wl, None, None, dhs, mutate=drop)    # dS | dT, dWl, dbl
+        out.update(dhs=dhs, dS=bl_['dX'][:, :64], dT=bl_['dX'][:, 64:], dWl=bl_['dW'], dbl=bl_['db'], dWd=bd_['dW'], dbd=bd_['db'])
+        if kind == 'last_visit' or kind == 'dbd_half':
+            which = mutate[1] if kind == 'last_visit' else 'dbd'
+            keep = last_visit_rows(N, mutate[2]) if kind == 'last_visit' else ((torch.arange(N) % TILE) < 32)[:, None]
+            if which in ('dWd', 'dbd'):
+                out[which] = lin(Hb, None, Wd, None, None, (G.to(dtype) * keep).to(F64))['dW' if which == 'dWd' else 'db']
+            else:
+                out[which] = lin(Xs, Xt, Wl, None, None, (dhs.to(dtype) * keep).to(F64))['dW' if which == 'dWl' else 'db']
+        if kind == 'dbl_no_ghs':
+            out['dbl'] = lin(Xs, Xt, Wl, None, None, lin(G, None, Wd.t())['Y'])['db']
+    if dtype == F64 and mutate is None:
+        aWd = Wd.to(F64).abs()
+        S = {'HS': f1['S']['Y'], 'ST': f1['S']['Y'] @ aWd.t() + (0 if bd is None else bd.to(F64).abs())}
+        if fg is not None:
+            S['ST_given'] = fg['S']['Y']
+        if dST is not None:
+            sc = linear(S_, T_, Wl, None, None, d['S']['Y'])['S']
+            S.update(dhs=d['S']['Y'], dS=sc['dX'][:, :64], dT=sc['dX'][:, 64:], dWl=sc['dW'], dbl=sc['db'], dWd=bd_['S']['dW'], dbd=bd_['S']['db'])
+        out['S'] = S
+    return out
+
+
 def tile_nodes(tables, listed=True):
     """(node of every row of the listed tiles, its tile's slot), in list order (int64).  listed=False: of all tiles."""
     order, ts, tc, slot = (tables[k].long() for k in ('order', 'tile_start', 'tile_count', 'tile_slot'))
@@ -385,11 +479,13 @@ def _gen(*key):
     return np.random.Generator(np.random.PCG64([int(k) for k in key]))
 
 
-def scaled_rows(g, n, w, last_on_top=False):
+def scaled_rows(g, n, w, last_on_top=False, first_on_top=0):
     """[n][w] float32 standard normal, every row times its own power of ten from [-3, 3]; last_on_top: the last row gets 10^3 (a
     partial tile's last row is then the largest term of every sum over the rows: with a random scale it can be too small for its loss
-    to show in dW)."""
+    to show in dW); first_on_top: so do that many first rows (one row past the grid cap ONE workgroup visits a second tile: what it
+    carries over from its first, 64 rows of 32,769, must weigh enough in a sum over all rows for its loss to show)."""
     e = g.uniform(-3, 3, (n, 1))
+    e[:first_on_top] = 3
     if last_on_top:
         e[n - 1] = 3
     return torch.from_numpy((g.standard_normal((n, w)) * 10.0 ** e).astype(np.float32))
@@ -440,6 +536,51 @@ def linear_case(M, K, N, K1=None, strided=False, bias=True, res=False, seed=0, c
 def linear_ref(c, dtype=F64, mm='exact', mutate=None, want_grad=True):
     v = lambda o: None if o is None else o.v       # noqa: E731
     return linear(v(c['X1']), v(c['X2']), c['W'], c['b'], v(c['R']), v(c['dY']) if want_grad else None, dtype, mm, mutate)
+
+
+def pair_case(N, strided=False, bias=True, ghs=True, coherent=False, seed=0):
+    """S, T [N][64], dST [N][128], gHS [N][64] (or None), every row of each its own power of ten, the last row 10^3 in all four (each
+    is an operand of a sum over the rows; past the grid cap the 64 rows of tile 0 as well); Wl 64 x 128 and Wd 128 x 64 0.2 g, bl and bd g (or None).  strided: every row matrix a
+    column slice of a wider NaN-holding one; the device test lays out its outputs, and the HS it hands to the backward, the same
+    way.  coherent: as linear_case: rows >= 0 and every weight (1 + 2^-9) 2^j, j by output row."""
+    g = _gen(seed, N, 6412864)
+    # past the grid cap the rows of tile 0 are on top too: at cap_rows + 1 it is the one tile whose sums a workgroup carries into a
+    # second visit, and with random scales its share of a sum over 32,769 rows is 1.6x the bound of dbl (measured: not 10x)
+    top = TILE if N > cap_rows('linear_pair_bwd_x3', PAIR) else 0
+    rows = lambda w: (lambda t: t.abs() if coherent else t)(scaled_rows(g, N, w, True, top))      # noqa: E731
+    f = lambda *s: torch.from_numpy(g.standard_normal(s).astype(np.float32))      # noqa: E731
+    coh = lambda M, K: ((1 + 2.0 ** -9) * 2.0 ** (torch.arange(M) % 5 - 2).to(F32))[:, None].repeat(1, K)      # noqa: E731
+    S_, T_, dST, gHS = rows(64), rows(64), rows(128), rows(64)
+    Wl, Wd, bl, bd = 0.2 * f(64, 128), 0.2 * f(128, 64), f(64), f(128)
+    if coherent:
+        Wl, Wd = coh(64, 128), coh(128, 64)
+    return {'N': N, 'strided': strided, 'S': Operand(S_, strided), 'T': Operand(T_, strided), 'dST': Operand(dST, strided),
+            'gHS': Operand(gHS, strided) if ghs else None, 'Wl': Wl, 'Wd': Wd, 'bl': bl if bias else None, 'bd': bd if bias else None}
+
+
+def pair_ref(c, HS=None, dtype=F64, mm='exact', mutate=None, want_grad=True):
+    return pair(c['S'].v, c['T'].v, c['Wl'], c['bl'], c['Wd'], c['bd'], c['dST'].v if want_grad else None,
+                None if c['gHS'] is None else c['gHS'].v, HS, dtype, mm, mutate)
+
+
+def pair_runs(c):
+    """(float64 run, bf16x3-emulation run, tau per output) of a pair case, the backward's given HS the emulation's own forward
+    result (float32 values, as the device's are) in both runs."""
+    hs = pair_ref(c, None, F32, 'x3', want_grad=False)['HS']
+    r64, rx3 = pair_ref(c, hs), pair_ref(c, hs, F32, 'x3')
+    return r64, rx3, taus(r64, rx3, 'x3')
+
+
+# The clauses of the two entries' MGV_CHECK_ARG lines (linear_x3.hip), one override of a valid call each: (entry, argument, value).
+# Pointers: None.  ldghs is looked at only where gHS is given: the last two rows are ACCEPTED forms and are listed apart.
+PAIR_REFUSALS = (
+    [('mgv_linear_pair_fwd_x3', k, None) for k in ('S', 'T', 'wlpack_bf16', 'wdpack_bf16', 'HS', 'ST')]
+    + [('mgv_linear_pair_fwd_x3', k, w) for k, lo in (('lds', 64), ('ldt', 64), ('ldhs', 64), ('ldst', 128)) for w in (lo - 4, lo + 2)]
+    + [('mgv_linear_pair_fwd_x3', 'N', -1), ('mgv_linear_pair_bwd_x3', 'N', -1)]
+    + [('mgv_linear_pair_bwd_x3', k, None) for k in ('dST', 'HS', 'S', 'T', 'wltpack_bf16', 'wdtpack_bf16', 'dS', 'dT', 'dWl', 'dWd')]
+    + [('mgv_linear_pair_bwd_x3', k, w) for k, lo in (('lddst', 128), ('ldghs', 64), ('ldhs', 64), ('lds', 64), ('ldt', 64), ('ldds', 64), ('lddt', 64))
+       for w in (lo - 4, lo + 2)])
+PAIR_GHS_NULL_ACCEPTS = (60, 66, 0)      # ldghs with gHS NULL: not a fault
 
 
 GROUPED_COUNTS = (64, 1, 63, 0, 64, 63, 1, 64, 0, 63, 64, 5)      # rows of the hand-built tiles (tile t: GROUPED_COUNTS[t % 12])

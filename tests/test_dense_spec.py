@@ -44,6 +44,57 @@ def test_linear_is_torch_linear_under_autograd(K1, bias, res, strided):
                    for k in ('X1', 'dY') + (('X2',) if c['X2'] is not None else ()) + (('R',) if res else ()))
 
 
+@pytest.mark.parametrize('strided', [False, True])
+@pytest.mark.parametrize('ghs', [False, True])
+@pytest.mark.parametrize('bias', [False, True])
+def test_pair_is_two_torch_linears_under_autograd(bias, ghs, strided):
+    """dense_ref.pair in float64: hs = linear([s | t]), st = linear(hs), the loss <st, dST> + <hs, gHS>; also 'ST_given' and the
+    backward's weight gradient of an HS handed in (the pair's backward takes hs as an input of its own)."""
+    c = DR.pair_case(129, strided=strided, bias=bias, ghs=ghs)
+    r = DR.pair_ref(c)
+    d = lambda t: None if t is None else t.to(F64).requires_grad_(True)       # noqa: E731
+    S, T, Wl, bl, Wd, bd = (d(t) for t in (c['S'].v, c['T'].v, c['Wl'], c['bl'], c['Wd'], c['bd']))
+    hs = torch.nn.functional.linear(torch.cat([S, T], 1), Wl, bl)
+    hs.retain_grad()
+    st = torch.nn.functional.linear(hs, Wd, bd)
+    loss = (st * c['dST'].v.to(F64)).sum()
+    if ghs:
+        loss = loss + (hs * c['gHS'].v.to(F64)).sum()
+    loss.backward()
+    want = {'HS': hs.detach(), 'ST': st.detach(), 'dhs': hs.grad, 'dS': S.grad, 'dT': T.grad, 'dWl': Wl.grad, 'dWd': Wd.grad}
+    if bias:
+        want.update(dbl=bl.grad, dbd=bd.grad)
+    else:
+        assert float((r['dbl'] - hs.grad.sum(0)).abs().max()) <= 1e-13 * float(r['S']['dbl'].max())
+        assert float((r['dbd'] - c['dST'].v.to(F64).sum(0)).abs().max()) == 0
+    for k, w in want.items():
+        q = DR.ratio(r[k], w, r['S'][k])
+        assert q <= 1e-13, (k, q)
+    assert set(r['S']) == set(want) | {'dbl', 'dbd'} and all(bool((s > 0).all()) for s in r['S'].values())
+    # an HS handed in: a perturbed copy, so that it is told apart from the run's own
+    given = (hs.detach() * 1.25).to(F32).to(F64)
+    rg = DR.pair_ref(c, given)
+    assert DR.ratio(rg['ST_given'], torch.nn.functional.linear(given, Wd.detach(), None if bd is None else bd.detach()), rg['S']['ST_given']) <= 1e-13
+    assert DR.ratio(rg['dWd'], c['dST'].v.to(F64).t() @ given, rg['S']['dWd']) <= 1e-13
+    assert all(torch.equal(rg[k], r[k]) for k in ('HS', 'ST', 'dhs', 'dS', 'dT', 'dWl', 'dbl', 'dbd'))
+    if strided:
+        ops_ = ('S', 'T', 'dST') + (('gHS',) if ghs else ())
+        assert all(bool(torch.isnan(c[k].parent[:, :4]).all()) and bool(torch.isnan(c[k].parent[:, -4:]).all()) and c[k].ld == c[k].w + 8 for k in ops_)
+
+
+def test_pair_case_is_built_as_designed():
+    c = DR.pair_case(129)
+    for k, w in (('S', 64), ('T', 64), ('dST', 128), ('gHS', 64)):
+        m = c[k].v.abs().amax(1)
+        assert c[k].v.shape == (129, w) and float(m.max() / m.min()) > 1e4 and float(m[-1]) > 1e3      # a power of ten per row, the last row on top
+    assert c['Wl'].shape == (64, 128) and c['Wd'].shape == (128, 64) and c['bl'].shape == (64,) and c['bd'].shape == (128,)
+    q = DR.pair_case(129, coherent=True)
+    assert all(float(q[k].v.min()) >= 0 for k in ('S', 'T', 'dST', 'gHS'))
+    for W in (q['Wl'], q['Wd']):
+        hi = W.to(torch.bfloat16).to(F32)
+        assert bool((torch.log2(hi) % 1 == 0).all()) and torch.equal((W - hi), hi * 2.0 ** -9)
+
+
 @pytest.mark.parametrize('M,K', DR.GROUPED_FWD)
 @pytest.mark.parametrize('subset', [False, True])
 def test_grouped_is_the_per_slot_index_add_form(M, K, subset):
@@ -168,10 +219,14 @@ def test_float32_list_order_is_the_order_of_a_plain_loop():
 
 
 # ------------------------------------------------------------------------------------------------ designed sizes
-LARGE = [('linear_fwd', (64, 64)), ('linear_wgrad', (64, 64)), ('linear_fwd_x3', (64, 128)), ('linear_wgrad_x3', (64, 128)), ('linear_wgrad_x3', (32, 32))]
+LARGE = [('linear_fwd', (64, 64)), ('linear_wgrad', (64, 64)), ('linear_fwd_x3', (64, 128)), ('linear_wgrad_x3', (64, 128)), ('linear_wgrad_x3', (32, 32)),
+         ('linear_pair_fwd_x3', DR.PAIR), ('linear_pair_bwd_x3', DR.PAIR)]
 
 
 def test_workgroups_per_cu_as_the_launchers_compute_them():
+    for k in ('linear_pair_fwd_x3', 'linear_pair_bwd_x3'):
+        assert DR.per_cu(k, DR.PAIR) == 2 and DR.unit_rows(k, DR.PAIR) == 64 and DR.cap_rows(k, DR.PAIR) == 32768 and DR.large_rows(k, DR.PAIR) == 65875
+    assert DR.per_cu('linear_pair_bwd_x3', DR.PAIR) == DR.per_cu('linear_wgrad_x3', (64, 128))      # "the grid of hs_linear's backward"
     assert [DR.per_cu('linear_fwd_x3', s) for s in DR.X3_SHAPES] == [3, 3, 4, 4, 4, 4]
     assert [DR.per_cu('linear_wgrad_x3', s) for s in DR.X3_SHAPES] == [2, 2, 2, 2, 2, 4]
     assert DR.per_cu('linear_fwd', (64, 64)) == 8 and DR.per_cu('linear_wgrad', (64, 64)) == 2
@@ -298,6 +353,46 @@ def _defects():
             ('the second in-flight segment member lost', lambda: rows(lambda: DR.seg_case(64, 129), DR.seg_ref, ('drop_member', 1))),
             ('class 8 folded into class 0', lambda: rows(lambda: DR.class_case(64, 1000, 9), DR.class_ref, ('fold_class', 8, 0))),
             ('the row u = 3 past the stride lost', lambda: rows(lambda: DR.class_case(128, DR.pull_sizes(128)[2], 40), DR.class_ref, ('lost_u', 3, s128)))]
+    out += _pair_defects()
+    return out
+
+
+PAIR_CAP = DR.cap_rows('linear_pair_bwd_x3', DR.PAIR)
+PAIR_BIG = DR.large_rows('linear_pair_bwd_x3', DR.PAIR)
+
+
+@functools.lru_cache(maxsize=None)
+def _pair(N, coherent=False):
+    c = DR.pair_case(N, coherent=coherent)
+    r64, rx3, tau = DR.pair_runs(c)
+    return c, r64, rx3, tau
+
+
+def _pair_defect(mutate, only, N, coherent=False):
+    """The defect in the bf16x3 run, with the given HS of the bound's own runs: the worst of the outputs `only` over its bound."""
+    c, r64, rx3, tau = _pair(N, coherent)
+    return _worst(DR.pair_ref(c, rx3['HS'], F32, 'x3', mutate), r64, tau, only)
+
+
+def _pair_defects():
+    out = []
+    for N in (PAIR_CAP + 1, PAIR_BIG):
+        g = DR.grid('linear_pair_bwd_x3', DR.PAIR, N)
+        assert g == DR.grid('linear_pair_fwd_x3', DR.PAIR, N) == 512
+        at = ' [pair, N=%d]' % N
+        out += [('the second tile of a workgroup from its first tile\'s S | T (forward)' + at, lambda N=N, g=g: _pair_defect(('stale_fwd', g), ('HS', 'ST'), N)),
+                ('the second tile of a workgroup from its first tile\'s dST / HS (backward)' + at, lambda N=N, g=g: _pair_defect(('stale_bwd_gh', g), ('dS', 'dT', 'dWd', 'dbd'), N)),
+                ('the second tile of a workgroup from its first tile\'s S | T (backward)' + at, lambda N=N, g=g: _pair_defect(('stale_bwd_x', g), ('dWl',), N)),
+                ('the second tile of a workgroup from its first tile\'s gHS alone (backward)' + at, lambda N=N, g=g: _pair_defect(('stale_bwd_ghs', g), ('dS', 'dT', 'dWl', 'dbl'), N))]
+        out += [('a workgroup\'s %s kept from its last visited tile only' % k + at, lambda N=N, g=g, k=k: _pair_defect(('last_visit', k, g), (k,), N))
+                for k in ('dWd', 'dWl', 'dbl', 'dbd')]
+    out += [('gHS not added to dhs [pair]', lambda: _pair_defect(('no_ghs',), ('dS', 'dT', 'dWl', 'dbl'), 129)),
+            ('dbl summed without gHS [pair]', lambda: _pair_defect(('dbl_no_ghs',), ('dbl',), 129)),
+            ('ST formed from the unbiased hs [pair]', lambda: _pair_defect(('st_unbiased',), ('ST', 'ST_given'), 129)),
+            ('a partial tile\'s last row dropped (forward) [pair]', lambda: _pair_defect(('drop_last_row',), ('HS', 'ST', 'ST_given'), 65)),
+            ('a partial tile\'s last row dropped (gradients) [pair]', lambda: _pair_defect(('drop_last_row',), ('dWl', 'dbl', 'dWd', 'dbd'), 65)),
+            ('the hi.lo term dropped from dST Wd (coherent inputs) [pair]', lambda: _pair_defect(('drop_hilo_dhs',), ('dS', 'dT', 'dWl', 'dbl'), 65, True)),
+            ('rows 32 to 63 of each tile missing from dbd [pair]', lambda: _pair_defect(('dbd_half',), ('dbd',), 129))]
     return out
 
 
@@ -330,3 +425,70 @@ def test_workspace_query_knows_the_supported_widths():
     for H in DR.WIDTHS:
         assert lib.mgv_class_pull_sum_ws_floats(H, 5, 4) == 4 * H and lib.mgv_class_pull_sum_ws_floats(H, 0, 4) == 0
         assert lib.mgv_class_pull_sum_ws_floats(H, DR.pull_sizes(H)[3], 4) == DR.GRID_CAP * 8 * 4 * H
+
+
+def _lib():
+    from deepgate import _hip
+    if not os.path.exists(_hip.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _hip.load()
+
+
+def test_pair_workspace_query_is_one_slab_row_pair_per_workgroup():
+    """mgv_linear_pair_bwd_x3_ws_floats: per workgroup one row of (dWl, dbl) and one of (dWd, dbd) partials; never negative."""
+    lib = _lib()
+    assert DR.PAIR_SLAB == 64 * 128 + 64 + 128 * 64 + 128
+    for N in DR.SMALL_ROWS + (PAIR_CAP, PAIR_CAP + 1, PAIR_BIG, 1 << 22):
+        assert lib.mgv_linear_pair_bwd_x3_ws_floats(N) == DR.grid('linear_pair_bwd_x3', DR.PAIR, N) * DR.PAIR_SLAB, N
+    assert lib.mgv_linear_pair_bwd_x3_ws_floats(PAIR_CAP + 1) == 512 * DR.PAIR_SLAB
+    for N in (0, -1, -(1 << 40)):
+        assert lib.mgv_linear_pair_bwd_x3_ws_floats(N) >= 0, N
+
+
+def _pair_call(lib, name, N=65, **over):
+    """The entry with arguments that pass every check (dummy non-NULL pointers, never dereferenced on the host: a refused call
+    returns before anything is launched; an accepted one is made with N = 0 only, which returns before the launch too)."""
+    import ctypes
+    import re
+    from deepgate import _hip
+    with open(_hip.HEADER_PATH) as f:
+        text = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S))
+    decl = re.search(r'\bint\s+%s\s*\(([^;{]*?)\)\s*;' % name, text, flags=re.S).group(1)
+    names = [re.findall(r'\w+', a)[-1] for a in decl.split(',')]
+    wide = {'lddst': 136, 'ldst': 136}
+    args = []
+    for k, (n, t) in enumerate(zip(names, _hip.parse_header()[name])):
+        if n in over:
+            v = over[n]
+            args.append(v if t is not ctypes.c_void_p or v is None else ctypes.c_void_p(v))
+        elif n == 'stream':
+            args.append(None)
+        elif t is ctypes.c_void_p:
+            args.append(ctypes.c_void_p(64 * (k + 1)))
+        else:
+            args.append(N if n == 'N' else 1 << 30 if n == 'workspace_floats' else wide.get(n, 72))
+    assert set(over) <= set(names), (name, over)
+    return getattr(lib, name)(*args)
+
+
+@pytest.mark.parametrize('name,arg,value', DR.PAIR_REFUSALS, ids=['%s-%s-%s' % r for r in DR.PAIR_REFUSALS])
+def test_pair_entries_refuse_every_clause_of_their_argument_checks(name, arg, value):
+    """MGV_EINVAL for a NULL required pointer, a row stride narrower than its matrix or no multiple of 4 (float4 rows), N < 0: every
+    clause of the MGV_CHECK_ARG lines of mgv_linear_pair_fwd_x3 / _bwd_x3, before N = 0 is looked at and before any launch (so
+    nothing is written; the device test repeats the table over real buffers and looks)."""
+    lib = _lib()
+    assert _pair_call(lib, name, 0) == 0                      # the base call is valid: N = 0 is MGV_OK
+    assert _pair_call(lib, name, **{arg: value}) == -1
+    if arg != 'N':
+        assert _pair_call(lib, name, 0, **{arg: value}) == -1
+
+
+def test_pair_backward_looks_at_ldghs_only_where_ghs_is_given():
+    lib = _lib()
+    for ld in DR.PAIR_GHS_NULL_ACCEPTS:
+        assert _pair_call(lib, 'mgv_linear_pair_bwd_x3', 0, gHS=None, ldghs=ld) == 0
+    for k in ('bl', 'bd'):
+        assert _pair_call(lib, 'mgv_linear_pair_fwd_x3', 0, **{k: None}) == 0
+    for k in ('dbl', 'dbd'):
+        assert _pair_call(lib, 'mgv_linear_pair_bwd_x3', 0, **{k: None}) == 0

@@ -4,7 +4,11 @@ pass each way, through the C ABI, against the two launches each replaces — mgv
 dWd and dbd are summed over the pair kernel's own partition of the tiles: each entry is held to a float64 restatement within 1e-4 of
 the restatement's largest entry, the bound tests/test_hip_linear_x3.py holds the weight and bias gradients of these kernels to.
 
-Sizes: 1, 63, 64, 65, 129 rows (tile edge, ragged last tile, three tiles) and 4,097 (65 tiles).  s and t are column slices of one
+Sizes: 1, 63, 64, 65, 129 rows (tile edge, ragged last tile, three tiles) and 4,097 (65 tiles): up to there every workgroup takes ONE
+tile (the grid is min(tiles, 512)), so the loop-carried prefetch, the barrier before a workgroup's next tile and the sums carried
+from tile to tile are not executed.  32,769 rows (513 tiles: workgroup 0 takes two) and 65,875 (1,030 tiles, the last of 19 rows:
+workgroups 0..5 take three, the others two) execute them; the product's batches (from 131,072 rows: four tiles and more per
+workgroup) run the same loop.  Against float64 entry by entry: tests/test_hip_linear_pair_reference.py.  s and t are column slices of one
 wider matrix; outputs have guard rows of NaN behind row N and the workspace is NaN-filled with a NaN guard behind it; every call is
 made twice and must give the same bytes.  Model level: one Trainer.train_step on a small batch with ops.LINEAR_PAIR on and off."""
 import itertools
@@ -19,7 +23,7 @@ F32, F64, I32, BF16 = torch.float32, torch.float64, torch.int32, torch.bfloat16
 GUARD = 64
 NAN = float('nan')
 NANBITS = torch.tensor(NAN, dtype=F32).view(I32).item()
-SIZES = [1, 63, 64, 65, 129, 4097]
+SIZES = [1, 63, 64, 65, 129, 4097, 32769, 65875]
 WGRAD_TOL = 1e-4            # of the largest entry: tests/test_hip_linear_x3.py
 MGV_OK, MGV_EINVAL = 0, -1
 
