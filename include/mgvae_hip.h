@@ -492,6 +492,45 @@ int mgv_sim_hist(int H, int64_t N, const float* y, int ldy, const int32_t* graph
  * T > 0: MGV_EINVAL.  N = 0 or T = 0 launches nothing. */
 int mgv_pair_rank_counts(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int skip_self,
                          const int32_t* thr_ptr, const float* thr, int32_t* n_gt, int32_t* n_eq, void* stream);
+/* ---- decode embeddings into a LEGAL circuit: fan-ins by arity, acyclic (added functionality; the decoder of digae_layer.py:31-33,
+ * digae_model.py:118-122 under the constraints of a netlist; csrc/pair_scores.hip).  One more consumer of the walk of mgv_pair_topk.
+ * The rows are TARGETS v: x [N][ldx] is the row operand and y [N][ldy] the column operand — on the models x = t and y = s, the
+ * by='dst' convention of the selection entries; every product commutes and k keeps its order, so a score is the bits
+ * mgv_pair_scores_at(s, t, sigmoid = 0) reports for (u, v).  key [N] int32: an order key per node (a level, a topological position);
+ * want [N] int32: how many fan-ins the node takes (its gate's arity); 1 <= K <= 8 the width of the lists.
+ * Candidate of row v: a column u of v's own graph (graph_ptr [G+1] int32, NULL = one graph of all N) with key[u] < key[v] whose score
+ * is not NaN — strict, so v is never its own candidate and every decoded edge runs from a smaller key to a larger one: the result is
+ * a DAG whatever the scores are.  Row v keeps its kk = min(max(want[v], 0), K) best candidates by raw dot product descending, ties by
+ * ascending id (the order of mgv_pair_topk).  A row with kk = 0 takes part in nothing: it has no candidates.
+ * idx [N][K] int32: batch-wide ids, -1 past the end; score [N][K]: the raw dot product, -inf where idx is -1; n_cand [N] int32: the
+ * number of candidates of the row regardless of score (0 where kk = 0): n_cand < want marks a gate that could not be completed.  Every
+ * row below N writes all K entries and its n_cand; no atomics, two calls give the same bytes.  A row tile none of whose rows wants
+ * anything walks nothing.
+ * tile_min int32 [ceil(N / 64)] or NULL, SCRATCH: when given, a small kernel on the same stream first writes the least key of every 64-column
+ * tile, and a workgroup steps over a column tile whose least key is not below the greatest key among its rows that want something
+ * (uniform per workgroup; such a tile holds nobody's candidate, so the output keeps every byte).  With keys that ascend with the id
+ * inside each graph that is half the walk.
+ * Refused before anything is launched: H outside {16, 32, 64, 128} (MGV_EUNSUPPORTED); K outside [1, 8], N < 0 or N > (2^31 - 1) / 8,
+ * a graph_ptr that does not start at 0 and end at N (its two ends are read back: the only blocking step, skipped for NULL), a bad row
+ * stride or alignment, and with N > 0 a NULL key, want, idx, score or n_cand: MGV_EINVAL.  N = 0 launches nothing. */
+int mgv_fanin_decode(int H, int64_t N, const float* x, int ldx, const float* y, int ldy, const int32_t* graph_ptr, int G,
+                     const int32_t* key, const int32_t* want, int K, int32_t* tile_min, int32_t* idx, float* score, int32_t* n_cand,
+                     void* stream);
+/* exact gate recovery of decoded lists against the true fan-in sets (added functionality; the strictest form of the reconstruction
+ * question of digae_model.py:118-122; csrc/fanin_recovery.hip).  idx [N][K] int32 as mgv_fanin_decode writes it (1 <= K <= 32): the
+ * distinct entries of a row other than -1 are its decoded set.  tru_ptr [N+1] int64 and tru_src [T] int32, T = tru_ptr[N] < 2^31: row
+ * v's true fan-ins, STRICTLY ascending (a set).  A decoded id is looked up in the row's list by value (binary search) and never used
+ * as an address: an id outside [0, N) is a miss.  Whatever tru_ptr holds between its ends, a row's range is clamped into [0, T].
+ * n_hit [N] int32 (or NULL): decoded fan-ins found in the row's true list, written for every row.  rec int64 [max(G, 1)][5], zeroed
+ * by the launcher: over the rows with a NON-EMPTY true list (the gates; a primary input counts nowhere) of each graph (graph_ptr
+ * [G+1] int32, NULL: row 0 for all) {gates, exact, hits, true_total, decoded_total}, exact = the decoded set equals the true set.
+ * 64-bit integer atomics only, one per non-zero (graph, field) of a workgroup after a segmented wave reduction: the same bytes from
+ * run to run.  Refused before anything is zeroed or launched: K outside [1, 32], N < 0 or N > (2^31 - 1) / 32, a NULL rec, G < 0
+ * with a graph_ptr, with N > 0 a NULL idx or tru_ptr, a graph_ptr that does not start at 0 and end at N, a tru_ptr that does not start
+ * at 0 or whose end lies outside [0, 2^31) (the four ends are read back in one small blocking step), a NULL tru_src with T > 0:
+ * MGV_EINVAL.  N = 0 zeroes rec and launches nothing. */
+int mgv_fanin_recovery(int64_t N, int K, const int32_t* idx, const int64_t* tru_ptr, const int32_t* tru_src, const int32_t* graph_ptr,
+                       int G, int32_t* n_hit, int64_t* rec, void* stream);
 /* ---- connected components on the device (added functionality; csrc/components.hip, csrc/mgv_unionfind.h): candidate classes of the
  * relation "same graph and cosine > threshold" on hf (trainer.py:158-160) and components of decoded link lists (digae_layer.py:31-33).
  * One forest parent[N] int32, N < 2^31, with 0 <= parent[x] <= x at all times: a root is only ever hooked under a smaller root

@@ -42,6 +42,9 @@ def get_parse_args(argv=None):
     parser.add_argument('--val_func_acc', action='store_true', help='validation phase: also count, per circuit, every comparison of two '
                         'listed truth-table pairs at least 0.05 apart on the device and log the mean share the functional embeddings '
                         'order correctly (utils/utils.py:111-147, exact where the reference samples 100)')
+    parser.add_argument('--val_recovery', action='store_true', help='validation phase: also decode every circuit\'s embeddings into a legal '
+                        'circuit (fan-ins by gate arity among the gates of lower level, acyclic) on the device and log the mean share of '
+                        'gates whose whole fan-in set came back exactly (Model.circuit_recovery; added functionality)')
     parser.add_argument('--neg_scope', type=str, default='batch', choices=['batch', 'graph'], help='negative edges of the reconstruction '
                         'loss: batch = both ends uniform over the nodes of the batch (dg_ae_model_aig.py:115-119, the reference); graph = the '
                         'destination uniform over the source\'s own circuit, the candidates the link-ranking tools rank against')

@@ -392,6 +392,159 @@ __global__ __launch_bounds__(kThreads) void k_pair_topk(int64_t N, const float* 
     topk_write(N, su, k, sigmoid, cnt, lv, li, idx, score, n_above, srow, sub);
 }
 
+// ---------------------------------------------------------------------------------- fan-ins by arity: a legal circuit from the walk
+// The walk of k_pair_topk with the rows as TARGETS v (the caller passes t as the row operand and s as the column operand; every product
+// commutes and k keeps its order, so a score is the bits of mgv_pair_scores_at for (u, v)) and two differences in its consumer:
+//   who is a candidate — a column u of v's graph whose order key is BELOW v's (fanin_candidate): never v itself, and every decoded edge
+//                        runs from a smaller key to a larger one, so the result is acyclic whatever the scores are;
+//   how many a row keeps — its own kk = min(max(want[v], 0), K), not one k for all rows: the list_insert of the top-k lists on lists of
+//                        kFaninLd entries per row.
+// A row that wants nothing has NO candidates (its range is empty, n_cand = 0): col_span then leaves a tile whose rows want nothing
+// without a walk, and what a tile walks depends only on its rows that want something.  The column keys of a tile travel through LDS
+// with the tile (kl, prefetched with it; INT_MAX past N: below no key).
+// Tile skip: tile_min[ct] is the least key of column tile ct (k_tile_min, launched in front on the same stream).  No column of a tile
+// whose least key is not below kmax — the greatest key among the tile's rows that want something — is anybody's candidate, so the
+// workgroup steps over it (a scalar compare, uniform per workgroup) and the output keeps its bytes.  With keys that ascend with the
+// id inside a graph (a levelised netlist in topological order) that is every tile behind the row tile's own: half the walk.
+// LDS at H = 128: score tile 33,792 B + sc 4,352 B + lists 2 x 2,304 B + five row tables 1,280 B = 44,032 B (k_pair_topk: 55,040 B).
+constexpr int kFaninMax = 8;
+constexpr int kFaninLd = kFaninMax + 1;    // row stride of the lists: the 16 rows of a wave lie in 16 banks
+
+// WHO is a candidate of target row v: a column of v's graph [lo, hi) whose key is strictly below v's; a NaN score is nobody's candidate.
+__device__ __forceinline__ bool fanin_candidate(const float& v, const int64_t& col, const int& lo, const int& hi, const int& ckey,
+                                                const int& rkey) {
+    return col >= lo && col < hi && ckey < rkey && v == v;
+}
+
+// topk_block's sorted-list insert on a list of k >= 1 entries L / I, by one lane of the row at a time: (v, col) goes where it is better
+// than the k-th.  Restated here: with the text taken out of topk_block into a function the two top-k kernels compile to other
+// instructions at every width (NOTEBOOK 2026-10-21).
+__device__ __forceinline__ void list_insert(float* L, int* I, const int& k, const float& v, const int64_t& col) {
+    if (pair_better(v, (int)col, L[k - 1], I[k - 1])) {
+        int pos = k - 1;
+        while (pos > 0 && pair_better(v, (int)col, L[pos - 1], I[pos - 1])) {
+            L[pos] = L[pos - 1]; I[pos] = I[pos - 1]; --pos;
+        }
+        L[pos] = v; I[pos] = (int)col;
+    }
+}
+
+// tile_min[ct] = min key[64 ct .. 64 ct + 63] over the columns below N: one wave per column tile
+__global__ __launch_bounds__(kThreads) void k_tile_min(int64_t N, const int32_t* key, int32_t* tile_min) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ct = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6), c = ct * kPairTile + lane;
+    if (ct * kPairTile >= N) return;                       // the whole wave leaves
+    int m = c < N ? key[c] : INT_MAX;
+    for (int d = 32; d > 0; d >>= 1) { const int o = __shfl_xor(m, d, 64); m = o < m ? o : m; }
+    if (lane == 0) tile_min[ct] = m;
+}
+
+// the keys of columns c0 .. c0 + 63 beside tile_load / tile_store: one per thread of the first wave
+__device__ __forceinline__ int key_load(const int32_t* key, int64_t c0, int64_t n) {
+    return (threadIdx.x < kPairTile && c0 + threadIdx.x < n) ? key[c0 + threadIdx.x] : INT_MAX;
+}
+
+// the wave's block of columns cb .. cb + 15 (keys kb[0 .. 15]): its candidates counted (cnt) and offered to the list of row srow
+__device__ __forceinline__ void fanin_block(const f32x4& acc, const int64_t& cb, const int* kb, const int& mylo, const int& myhi,
+                                            const int& mykey, const int& myk, float* sc, float* lv, int* li, int& cnt, const int& w,
+                                            const int& r, const int& q, const int& srow, const int& sub) {
+    wave_lds_fence();                              // the previous block's reads are done
+#pragma unroll
+    for (int g = 0; g < 4; ++g) sc[(16 * w + 4 * q + g) * kTopkScLd + r] = acc[g];
+    wave_lds_fence();
+    float* L = lv + srow * kFaninLd;
+    int* I = li + srow * kFaninLd;
+    const int last = myk > 0 ? myk - 1 : 0;        // myk = 0: an empty range, nothing is valid
+    for (int st = 0; st < 4; ++st) {
+        const int64_t col = cb + 4 * st + sub;
+        const float v = sc[srow * kTopkScLd + 4 * st + sub];
+        const bool valid = fanin_candidate(v, col, mylo, myhi, kb[4 * st + sub], mykey);
+        cnt += valid ? 1 : 0;
+        const bool pass = valid && pair_better(v, (int)col, L[last], I[last]);
+        if (__ballot(pass) == 0ull) continue;
+        for (int turn = 0; turn < 4; ++turn) {      // the row's four lanes insert one after the other, lowest column first
+            if (pass && sub == turn) list_insert(L, I, myk, v, col);
+            wave_lds_fence();
+        }
+    }
+}
+
+template <int H>
+__global__ __launch_bounds__(kThreads) void k_fanin_decode(int64_t N, const float* x, int ldx, const float* y, int ldy, const int32_t* gp,
+                                                           int G, const int32_t* key, const int32_t* want, int K, const int32_t* tile_min,
+                                                           int32_t* idx, float* score, int32_t* n_cand) {
+    __shared__ __attribute__((aligned(16))) float tl[kPairTile * PairCfg<H>::LDT];
+    __shared__ float sc[kPairTile * kTopkScLd];
+    __shared__ float lv[kPairTile * kFaninLd];
+    __shared__ int li[kPairTile * kFaninLd];
+    __shared__ int rlo[kPairTile], rhi[kPairTile], rkey[kPairTile], rk[kPairTile], kl[kPairTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 15, q = lane >> 4;
+    const int64_t u0 = (int64_t)blockIdx.x * kPairTile;
+    row_ranges(N, u0, gp, G, rlo, rhi);
+    if (threadIdx.x < kPairTile) {                         // the row's key and how many it keeps; a row that wants nothing: no candidates
+        const int64_t u = u0 + threadIdx.x;
+        int kk = u < N ? want[u] : 0;
+        kk = kk < 0 ? 0 : (kk > K ? K : kk);
+        rkey[threadIdx.x] = u < N ? key[u] : INT_MIN;
+        rk[threadIdx.x] = kk;
+        if (kk == 0) rhi[threadIdx.x] = rlo[threadIdx.x];  // (row_ranges wrote both from this thread)
+    }
+    const int srow = 16 * w + (lane >> 2), sub = lane & 3;
+    for (int j = sub; j < kFaninMax; j += 4) { lv[srow * kFaninLd + j] = -INFINITY; li[srow * kFaninLd + j] = INT_MAX; }
+    __syncthreads();
+    int64_t clo, chi;
+    col_span(N, rlo, rhi, clo, chi);
+    int kmax = INT_MIN;                                    // the greatest key among the rows that want something
+    for (int i = 0; i < kPairTile; ++i) kmax = (rlo[i] < rhi[i] && rkey[i] > kmax) ? rkey[i] : kmax;
+    const int64_t su = u0 + srow;                          // the row this lane scans for
+    const int mylo = rlo[srow], myhi = rhi[srow], mykey = rkey[srow], myk = rk[srow];
+    const int64_t row0 = u0 + 16 * w;
+    float a[H / 4];
+    load_row_frags<H>(a, x, ldx, row0 + r, row0 + r < N, q);
+    int cnt = 0;
+    if (clo < chi) {
+        int64_t ct0, ct1;
+        tile_span<false>(clo, chi, ct0, ct1);
+        // the next tile from `ct` on that can hold a candidate (without tile_min: ct itself)
+        auto next_tile = [&](int64_t ct) {
+            if (tile_min != nullptr) { while (ct < ct1 && tile_min[ct] >= kmax) ++ct; }
+            return ct;
+        };
+        int64_t ct = next_tile(ct0);
+        float4 nxt[H / 16];
+        int nkey = INT_MAX;
+        if (ct < ct1) { tile_load<H>(nxt, y, ldy, ct * kPairTile, N); nkey = key_load(key, ct * kPairTile, N); }
+        while (ct < ct1) {
+            __syncthreads();
+            tile_store<H, PairCfg<H>::LDT>(tl, nxt);
+            if (threadIdx.x < kPairTile) kl[threadIdx.x] = nkey;
+            __syncthreads();
+            const int64_t nct = next_tile(ct + 1);
+            if (nct < ct1) { tile_load<H>(nxt, y, ldy, nct * kPairTile, N); nkey = key_load(key, nct * kPairTile, N); }
+            f32x4 acc[4];
+            tile_scores<H>(acc, a, tl, r, q);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int64_t cb = ct * kPairTile + 16 * c;
+                fanin_block(acc[c], cb, kl + 16 * c, mylo, myhi, mykey, myk, sc, lv, li, cnt, w, r, q, srow, sub);
+            }
+            ct = nct;
+        }
+    }
+    wave_lds_fence();
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    if (su < N) {                                          // every row below N writes its count and all K entries
+        if (sub == 0) n_cand[su] = cnt;
+#pragma unroll 1
+        for (int j = sub; j < K; j += 4) {
+            const int id = li[srow * kFaninLd + j];
+            idx[su * K + j] = id == INT_MAX ? -1 : id;
+            score[su * K + j] = id == INT_MAX ? -INFINITY : lv[srow * kFaninLd + j];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- thresholded links as per-row lists
 // The walk of k_pair_topk without its lists: one workgroup per 64 rows u, the rows' s fragments in registers, the t tiles through
 // LDS with the next one prefetched.  Nothing leaves the accumulators: lane (r, q) holds column 16 c + r of rows 4 q + g, so the 16
@@ -1337,6 +1490,29 @@ static int select_fill_run(const WalkIn& in, float threshold, const int64_t* row
 extern "C" int mgv_pair_topk(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G, int k,
                              int sigmoid, float threshold, int skip_self, int32_t* idx, float* score, int32_t* n_above, void* stream) {
     return topk_run(pair_walk(H, N, s, lds, t, ldt, graph_ptr, G, sigmoid, skip_self, stream), k, threshold, idx, score, n_above);
+}
+
+extern "C" int mgv_fanin_decode(int H, int64_t N, const float* x, int ldx, const float* y, int ldy, const int32_t* graph_ptr, int G,
+                                const int32_t* key, const int32_t* want, int K, int32_t* tile_min, int32_t* idx, float* score,
+                                int32_t* n_cand, void* stream) {
+    if (!mgv::pair_h_ok(H)) return MGV_EUNSUPPORTED;
+    MGV_CHECK_ARG(K >= 1 && K <= mgv::kFaninMax);
+    MGV_CHECK_ARG(N >= 0 && N <= 0x7fffffffLL / mgv::kFaninMax);         // node ids and idx offsets are int32 on the host side
+    hipStream_t st = (hipStream_t)stream;
+    bool launch;
+    const int rc = pair_walk_args(H, N, x, ldx, y, ldy, graph_ptr, G, st, &launch);
+    if (rc != MGV_OK || !launch) return rc;
+    MGV_CHECK_ARG(key != nullptr && want != nullptr && idx != nullptr && score != nullptr && n_cand != nullptr);
+    if (tile_min != nullptr) {
+        const int64_t nct = (N + mgv::kPairTile - 1) / mgv::kPairTile, per = mgv::kThreads / 64;
+        hipLaunchKernelGGL(mgv::k_tile_min, dim3((unsigned)((nct + per - 1) / per)), dim3(mgv::kThreads), 0, st, N, key, tile_min);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return launch_width(mgv::AllWidths{}, H, [&](auto w) {
+        launch_row_tiles(mgv::k_fanin_decode<w>, N, st, N, x, ldx, y, ldy, graph_ptr, G, key, want, K, (const int32_t*)tile_min, idx, score,
+                         n_cand);
+    });
 }
 
 extern "C" int mgv_pair_select_count(int H, int64_t N, const float* s, int lds, const float* t, int ldt, const int32_t* graph_ptr, int G,

@@ -4,6 +4,7 @@ per-gate-type attention + GRU sweep -> (hs, hf); readout, reconstruction loss, c
 Sub-module names and construction order follow the reference so state_dicts and seeded
 initialisation line up."""
 import os
+from collections import namedtuple
 
 import torch
 from torch import nn
@@ -20,9 +21,13 @@ DEVICE_SAMPLER = True             # fused device sampler whenever the batch has 
 MAX_LOGSTD = 10
 
 
+DecodedCircuit = namedtuple('DecodedCircuit', 'edge_index fanin score short')
+
+
 class FunctionalModel(nn.Module):
     ENCODER_ATTR = 'struct_encoder'
     GATES = ()            # ((name, gate id), ...) in the order the reference creates aggr_*/update_* modules
+    ARITY = {'and': 2, 'or': 2, 'xor': 2, 'not': 1, 'maj': 3}           # fan-ins per gate of the libraries (decode_circuit)
 
     VAR_HEADS = ('fc_s_mu', 'fc_s_logstd', 'fc_t_mu', 'fc_t_logstd')      # DirectedGVAE's names (digvae_model.py:112-115)
 
@@ -352,6 +357,53 @@ class FunctionalModel(nn.Module):
         circuit; -1 where no comparison is eligible, as there.  A tie in the prediction is not correct, as there."""
         gaps = [min_gap] if isinstance(min_gap, (int, float)) else list(min_gap)
         return metrics.function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=graph_ptr, gaps=gaps)
+
+    # ---- decode a legal circuit ------------------------------------------------------------------------
+    def gate_arity(self, gate):
+        """int32 like `gate`: the number of fan-ins the library gives each gate id (ARITY through this model's GATES); a primary input
+        and an id the model does not know take none."""
+        gate = torch.as_tensor(gate)
+        ids = gate.flatten().to(torch.int64)
+        table = torch.zeros(max([gid for _, gid in self.GATES] + [0]) + 1, dtype=torch.int32, device=ids.device)
+        for name, gid in self.GATES:
+            table[gid] = self.ARITY[name]
+        known = (ids >= 0) & (ids < table.numel())
+        return torch.where(known, table[ids.clamp(0, table.numel() - 1)], torch.zeros_like(ids, dtype=torch.int32)).view(gate.shape)
+
+    def decode_circuit(self, hs, G, key=None, want=None, K=None):
+        """DecodedCircuit(edge_index int64 [2, E'], fanin int32 [N, K], score [N, K], short bool [N]) on st = hs_decompose(hs) (of a
+        variational model the posterior means): the embeddings of CircuitBatch G decoded into a circuit of this model's gate library —
+        every gate gets its `want` best fan-ins among the nodes of its own circuit with a smaller `key`, so arities hold and the
+        result is acyclic whatever the scores are (ops.fanin_decode, streamed without an N x N array).  key: G.forward_level by
+        default (the plan's ASAP levels where the batch has none): every true fan-in of a levelised circuit is then a candidate.
+        want: the library arity of each gate (gate_arity) by default, 'degree': the true in-degree, or a tensor.  fanin: -1 past a
+        list's end; edge_index: sources on row 0, by target, then by rank; short: the gates with fewer candidates than they want.
+        Added functionality: the reference decodes only scores (digae_layer.py:31-33)."""
+        with torch.no_grad():
+            s, t = self._decoder_halves(hs)
+            N, dev = s.shape[0], s.device
+            if key is None:
+                if getattr(G, 'forward_level', None) is None:
+                    plan_of(G, [gid for _, gid in self.GATES])            # levelises on the device and keeps the levels on the batch
+                key = G.forward_level
+            if want is None:
+                want = self.gate_arity(G.gate.flatten())
+            elif isinstance(want, str):
+                if want != 'degree':
+                    raise ValueError("want must be None (library arity), 'degree' (true in-degree) or a tensor, got %r" % (want,))
+                want = torch.bincount(G.edge_index[1].to(dev), minlength=N)
+            want = torch.as_tensor(want).to(dev)
+            idx, score, n_cand = pairs.fanin_decode(s, t, torch.as_tensor(key).to(dev).flatten(), want, graph_ptr=getattr(G, 'graph_ptr', None),
+                                                    K=K)
+            return DecodedCircuit(pairs.fanin_edges(idx), idx, score, n_cand < want.flatten().to(torch.int32))
+
+    def circuit_recovery(self, hs, G, key=None, want=None, K=None):
+        """(FaninRecovery, DecodedCircuit): decode_circuit counted against G.edge_index — per circuit {gates, exact, hits, true_total,
+        decoded_total} and the exact-recovery rate exact / gates (ops.fanin_recovery): whether the WHOLE fan-in set of a gate came
+        back, the strictest reconstruction metric.  Added functionality."""
+        with torch.no_grad():
+            dec = self.decode_circuit(hs, G, key=key, want=want, K=K)
+            return metrics.fanin_recovery(dec.fanin, G.edge_index, graph_ptr=getattr(G, 'graph_ptr', None)), dec
 
     def recon_loss(self, hs, pos_edge_index, neg_edge_index=None, want_pred=True, edge_keys=None, plan=None, want_rank=False,
                    expect_scale=1.0, graph_ptr=None, return_hs=False, sample=None, seed=None, eps=None, st=None):

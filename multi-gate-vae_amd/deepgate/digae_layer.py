@@ -50,6 +50,11 @@ class DirectedInnerProductDecoder(nn.Module):
         int64 [G, B, 4] of ops.reconstruction_curve — true positives, predicted positives, edges, ordered pairs per graph."""
         return pairs.reconstruction_curve(s, t, edge_index, graph_ptr, thresholds)
 
+    def decode_fanins(self, s, t, key, want, graph_ptr=None, K=None, skip=True):
+        """A legal circuit from the scores (added functionality): per node its `want` best fan-ins among the nodes of its own graph
+        with a smaller order `key` — acyclic whatever the scores are — as (idx, score, n_cand) of ops.fanin_decode."""
+        return pairs.fanin_decode(s, t, key, want, graph_ptr=graph_ptr, K=K, skip=skip)
+
     def rank(self, s, t, edge_index, graph_ptr=None, by='src', skip_self=False, filtered=True, plan=None):
         """Where every listed link stands among ALL candidates of its node by raw score (added functionality: the reference's `test`
         ranks against sampled non-edges): LinkRanks(rank_lo, rank_hi, valid) of ops.link_ranks, in the caller's edge order."""

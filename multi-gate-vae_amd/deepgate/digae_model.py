@@ -4,6 +4,7 @@ part of the DG_AE / AE training paths and is left out."""
 import torch
 
 from . import metrics, ops, pairs, similarity
+from ._model_base import DecodedCircuit
 from .digae_layer import DirectedInnerProductDecoder
 from .sampling import negative_sampling
 
@@ -52,6 +53,26 @@ class DirectedGAE(torch.nn.Module):
         with torch.no_grad():
             return pairs.reconstruct_edges(s, t, graph_ptr=graph_ptr, threshold=threshold, skip_self=skip_self, by=by,
                                            with_scores=with_scores, max_edges=max_edges)
+
+    def decode_circuit(self, s, t, key, want, graph_ptr=None, K=None):
+        """DecodedCircuit(edge_index int64 [2, E'], fanin int32 [N, K], score [N, K], short bool [N]): every node's `want` best fan-ins
+        among the nodes of its own graph with a smaller order `key` (a level), so the result has the asked in-degrees and is acyclic
+        whatever the scores are (ops.fanin_decode).  short: fewer candidates than wanted.  Added functionality."""
+        with torch.no_grad():
+            want = torch.as_tensor(want).to(s.device).flatten()
+            idx, score, n_cand = pairs.fanin_decode(s, t, key, want, graph_ptr=graph_ptr, K=K)
+            return DecodedCircuit(pairs.fanin_edges(idx), idx, score, n_cand < want.to(torch.int32))
+
+    def circuit_recovery(self, s, t, edge_index, key, want='degree', graph_ptr=None, K=None):
+        """(FaninRecovery, DecodedCircuit): decode_circuit counted against edge_index per graph — {gates, exact, hits, true_total,
+        decoded_total} and exact / gates (ops.fanin_recovery); want='degree': the true in-degree.  Added functionality."""
+        with torch.no_grad():
+            if isinstance(want, str):
+                if want != 'degree':
+                    raise ValueError("want must be 'degree' (true in-degree) or a tensor, got %r" % (want,))
+                want = torch.bincount(edge_index[1].to(s.device), minlength=s.shape[0])
+            dec = self.decode_circuit(s, t, key, want, graph_ptr=graph_ptr, K=K)
+            return metrics.fanin_recovery(dec.fanin, edge_index, graph_ptr=graph_ptr), dec
 
     def reconstructed_components(self, edge_index, N):
         """label int32 [N]: the weakly connected components of a decoded link list (reconstruct_edges' edge_index, direction ignored) —

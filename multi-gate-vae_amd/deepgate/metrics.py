@@ -392,3 +392,48 @@ def function_accuracy(hf, tt_pair_index, tt_sim, graph_ptr=None, gaps=(MIN_GAP,)
         el, co = counts[..., 0], counts[..., 1]
         acc = torch.where(el > 0, co.double() / el.clamp(min=1).double(), torch.full_like(el, -1, dtype=torch.float64))
         return acc, counts
+
+
+# ------------------------------------------------------------------------------------------------
+# exact gate recovery of a decoded circuit (added functionality: mgv_fanin_recovery against pairs.fanin_decode's lists)
+# ------------------------------------------------------------------------------------------------
+FaninRecovery = namedtuple('FaninRecovery', 'counts n_hit recovery precision recall')
+FANIN_RECORD = ('gates', 'exact', 'hits', 'true_total', 'decoded_total')
+
+
+def true_fanin_lists(edge_index, N):
+    """(tru_ptr int64 [N + 1], tru_src int32 [T]) on edge_index's device: every node's true fan-ins, strictly ascending and without
+    repeats — one sort of dst * N + src, unique_consecutive, a bincount and a scan."""
+    src, dst = edge_rows(edge_index)
+    if src.numel() > 0 and (int(torch.min(torch.minimum(src, dst))) < 0 or int(torch.max(torch.maximum(src, dst))) >= N):
+        raise ValueError('edge_index holds node ids outside [0, %d)' % N)
+    code = torch.unique_consecutive(torch.sort(dst * N + src).values)
+    tru_ptr = torch.zeros(N + 1, dtype=torch.int64, device=src.device)
+    if N > 0:
+        torch.cumsum(torch.bincount(torch.div(code, N, rounding_mode='floor'), minlength=N), 0, out=tru_ptr[1:])
+    return tru_ptr, (code % max(N, 1)).to(I32).contiguous()
+
+
+def fanin_recovery(idx, edge_index, graph_ptr=None):
+    """FaninRecovery(counts int64 [G, 5], n_hit int32 [N], recovery, precision, recall float64 [G]) on the device (G = 1 without
+    graph_ptr): decoded fan-in lists idx [N, K] (pairs.fanin_decode; -1: no entry) against the true fan-in sets of `edge_index`
+    (repeated edges count once).  counts per graph over the gates — the nodes with at least one true fan-in —: FANIN_RECORD =
+    {gates, exact, hits, true_total, decoded_total}, exact: the decoded SET equals the true set.  recovery = exact / gates,
+    precision = hits / decoded_total, recall = hits / true_total, -1 where the divisor is 0.  n_hit: decoded fan-ins of each node that
+    are true.  Integer atomics: the same bytes from call to call.  One read-back (the range of edge_index).  No grad."""
+    with torch.no_grad():
+        idx = check(idx.detach().contiguous(), I32, 'idx')
+        if idx.dim() != 2 or not 1 <= idx.shape[1] <= 32:
+            raise HipLibraryError('idx must be [N, K] with 1 <= K <= 32 (got shape %s)' % (tuple(idx.shape),))
+        N, K = idx.shape
+        dev = idx.device
+        tru_ptr, tru_src = true_fanin_lists(edge_index.to(dev), N)
+        gp, G = _pair_graphs(graph_ptr, dev)
+        rec = torch.empty((max(G, 1), len(FANIN_RECORD)), dtype=torch.int64, device=dev)
+        n_hit = torch.empty(N, dtype=I32, device=dev)
+        _hip.call('mgv_fanin_recovery', N, K, ptr(idx), ptr(tru_ptr), ptr(tru_src), ptr(gp), G, ptr(n_hit), ptr(rec))
+        rec = rec if gp is None else rec[:G]
+
+        def ratio(a, b):
+            return torch.where(b > 0, a.double() / b.clamp(min=1).double(), torch.full_like(b, -1, dtype=torch.float64))
+        return FaninRecovery(rec, n_hit, ratio(rec[:, 1], rec[:, 0]), ratio(rec[:, 2], rec[:, 4]), ratio(rec[:, 2], rec[:, 3]))

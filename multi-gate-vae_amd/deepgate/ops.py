@@ -1499,11 +1499,12 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, gr
 # the analysis surface lives in pairs / similarity / metrics (none of them imports this module); the documented public names are
 # re-bound here.  Their underscored helpers are not: patch those in their home module.
 # ------------------------------------------------------------------------------------------------
-from .pairs import (PROFILE_MAX_EDGES, PairScoresFn, counts_above, dense_scores, pair_profile, pair_scores,  # noqa: E402,F401
-                    pair_scores_at, pair_select, pair_topk, reconstruct_edges, reconstruction_counts, reconstruction_curve)
+from .pairs import (FANIN_MAX, PROFILE_MAX_EDGES, PairScoresFn, counts_above, dense_scores, fanin_decode, fanin_edges,  # noqa: E402,F401
+                    pair_profile, pair_scores, pair_scores_at, pair_select, pair_topk, reconstruct_edges, reconstruction_counts,
+                    reconstruction_curve)
 from .similarity import (SIM_THRESHOLD, class_table, components, cross_classes, cross_mutual, cross_pairs,  # noqa: E402,F401
                          cross_profile, cross_threshold_for, cross_topk, row_unit, sim_at, sim_classes, sim_pairs, sim_profile, sim_threshold_for, sim_topk,
                          threshold_search)
-from .metrics import (CONCORD_MAX_GAPS, CONCORD_TILE, LINK_RECORD_WORDS, MIN_GAP, LinkRanks, RankLists, RankMetrics,  # noqa: E402,F401
-                      concord_counts, function_accuracy, link_auc_ap, link_rank_filter, link_rank_lists, link_ranks, link_record,
-                      pair_rank_counts, pair_segments, rank_metrics, read_link_records, segment_table)
+from .metrics import (CONCORD_MAX_GAPS, CONCORD_TILE, FANIN_RECORD, LINK_RECORD_WORDS, MIN_GAP, FaninRecovery, LinkRanks,  # noqa: E402,F401
+                      RankLists, RankMetrics, concord_counts, fanin_recovery, function_accuracy, link_auc_ap, link_rank_filter, link_rank_lists, link_ranks, link_record,
+                      pair_rank_counts, pair_segments, rank_metrics, read_link_records, segment_table, true_fanin_lists)

@@ -319,3 +319,56 @@ def reconstruction_curve(s, t, edge_index, graph_ptr, thresholds):
         edges = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gid, torch.ones_like(gid))
         n = gp[1:] - gp[:-1]
         return torch.stack([tp, pp, edges[:, None].expand(G, B), (n * n)[:, None].expand(G, B)], dim=2)
+
+
+# ------------------------------------------------------------------------------------------------
+# decode embeddings into a legal circuit (added functionality: fan-ins by arity, acyclic; mgv_fanin_decode)
+# ------------------------------------------------------------------------------------------------
+FANIN_MAX = 8                             # csrc/pair_scores.hip kFaninMax
+
+
+def _node_ints(x, N, name, dev):
+    x = torch.as_tensor(x).detach().to(device=dev, dtype=I32).contiguous().flatten()
+    if x.numel() != N:
+        raise HipLibraryError('fanin_decode: %s needs one entry per node, %d (got %d)' % (name, N, x.numel()))
+    return x
+
+
+def fanin_decode(s, t, key, want, graph_ptr=None, K=None, skip=True):
+    """(idx [N, K] int32, score [N, K], n_cand [N] int32): for every node v the fan-ins a legal circuit gives it.  A candidate of v is a
+    node u of v's own graph (graph_ptr [G + 1], None: one graph) with key[u] < key[v] whose score <s_u, t_v> is not NaN — never v
+    itself, and every edge runs from a smaller key to a larger one, so the result is acyclic whatever the scores are.  v keeps its
+    min(max(want[v], 0), K) best candidates by raw dot product (ties: lower id first; -1 / -inf past the end); n_cand counts them all
+    (0 for a node that wants nothing), so n_cand < want marks a gate that could not be completed.  The scores are the bits of
+    pair_scores_at(s, t, sigmoid=False).  K defaults to want.max() clamped to [1, 8] (ONE read-back, avoided when K is given).
+    skip: allocate the per-tile key minima by which the walk steps over column tiles that hold no candidate (the same bytes either
+    way).  Streaming: nothing of size N x N; no atomics.  No grad."""
+    if s.dim() == 2 and t.dim() == 2 and s.shape[1] == t.shape[1]:
+        _pair_width(s, 'fanin_decode')
+    with torch.no_grad():
+        td, ldt, sd, lds, H = _pair_operands(t, s)                 # rows are targets: by='dst'
+        N = _same_rows(sd, td, 'fanin_decode decodes the nodes of one batch')
+        dev = sd.device
+        key = _node_ints(key, N, 'key', dev)
+        want = _node_ints(want, N, 'want', dev)
+        if K is None:
+            K = min(max(int(want.max()) if N > 0 else 1, 1), FANIN_MAX)          # the read-back
+        K = int(K)
+        gp, G = _pair_graphs(graph_ptr, dev)
+        kk = min(max(K, 1), FANIN_MAX)
+        idx = torch.empty((N, kk), dtype=I32, device=dev)
+        score = torch.empty((N, kk), dtype=F32, device=dev)
+        n_cand = torch.empty(N, dtype=I32, device=dev)
+        tile_min = torch.empty((N + 63) // 64, dtype=I32, device=dev) if skip and N > 0 else None
+        _hip.call('mgv_fanin_decode', H, N, ptr(td), ldt, ptr(sd), lds, ptr(gp), G, ptr(key), ptr(want), K, ptr(tile_min), ptr(idx),
+                  ptr(score), ptr(n_cand))
+        return idx, score, n_cand
+
+
+def fanin_edges(idx):
+    """edge_index int64 [2, E'] of decoded fan-in lists idx [N, K] (-1: no entry): sources on row 0, ordered by target, then by rank."""
+    with torch.no_grad():
+        N, K = idx.shape
+        keep = (idx >= 0).flatten()
+        dst = torch.arange(N, dtype=torch.int64, device=idx.device).repeat_interleave(K)[keep]
+        return torch.stack([idx.flatten()[keep].to(torch.int64), dst])

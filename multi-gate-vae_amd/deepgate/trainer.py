@@ -63,7 +63,7 @@ class GraphLoader:
 
 class Trainer():
     # the phase line of the reference's log (trainer.py:259-262); --val_auc appends ' |AUC: x.xxxx |AP: x.xxxx' to the val line,
-    # --val_func_acc ' |FuncAcc: x.xxxx' behind it
+    # --val_func_acc ' |FuncAcc: x.xxxx' behind it, --val_recovery ' |Recov: x.xxxx' behind that
     LOG_LINE = '{}| Epoch: {:}/{:} |Recon: {:.4f} |ACC: {:.2f} |Prob: {:.4f} |Func: {:.4f}|Net: {:.2f}s'
 
     def __init__(self, args, model, training_id='default', save_dir='./exp', lr=1e-4,
@@ -170,13 +170,15 @@ class Trainer():
             return True
         return False
 
-    def run_batch(self, batch, want_pred=True, want_rank=False, want_func_acc=False):
+    def run_batch(self, batch, want_pred=True, want_rank=False, want_func_acc=False, want_recovery=False):
         """Forward + the three losses (trainer.py:131-174).  `general_train_test_split_edges` with zero
         val/test ratios only permutes the edges (preprocessing.py:41-50), to which the mean over edges is
         invariant: train_pos_edge_index is the batch's edge_index.  `want_rank`: also rank the loss's own pairs on the device
         (ROC-AUC / average precision, ops.link_record); the record is returned under 'link_metrics'.  `want_func_acc`: also count
         every comparison of two listed truth-table pairs per circuit at gap 0.05 (ops.function_accuracy); the int64 [G, 3] counts
-        {eligible, concordant, tied} are returned under 'func_counts', on the device."""
+        {eligible, concordant, tied} are returned under 'func_counts', on the device.  `want_recovery`: also decode hs into a legal
+        circuit and count the gates whose whole fan-in set came back (Model.circuit_recovery); the int64 [G, 2] counts {gates, exact}
+        are returned under 'recovery_counts', on the device."""
         batch.train_pos_edge_index = batch.edge_index
         neg = getattr(batch, 'neg_edge_index', None)
         # the batch's plan is Model.forward's to build and to pass (every batch has one from there on: the device sampler draws).
@@ -209,6 +211,8 @@ class Trainer():
         if want_func_acc:
             loss_status['func_counts'] = metrics.function_accuracy(hf, batch['tt_pair_index'], batch['tt_sim'],
                                                                    graph_ptr=getattr(batch, 'graph_ptr', None), cache=batch)[1][:, 0]
+        if want_recovery:
+            loss_status['recovery_counts'] = self.model.circuit_recovery(hs, batch)[0].counts[:, :2]
         return loss_status
 
     def _encoder_half_rounds(self):
@@ -303,12 +307,15 @@ class Trainer():
 
         val_auc = bool(getattr(self.args, 'val_auc', False))
         val_func_acc = bool(getattr(self.args, 'val_func_acc', False))
+        val_recovery = bool(getattr(self.args, 'val_recovery', False))
         for epoch in range(num_epoch):
             for phase in ['train', 'val']:
                 rank = val_auc and phase == 'val'
                 facc = val_func_acc and phase == 'val'
+                recov = val_recovery and phase == 'val'
                 records = []             # per-batch link records of the phase, on the device until the phase ends
                 func_counts = []         # per-batch [G, 3] comparison counts of the phase, likewise
+                recovery_counts = []     # per-batch [G, 2] {gates, exact} of the phase, likewise
                 loader = train_loader if phase == 'train' else val_loader
                 self.model.train() if phase == 'train' else self.model.eval()
                 # collate, host-to-device copy and plan build of the next batches run on worker threads / their own HIP streams
@@ -324,11 +331,14 @@ class Trainer():
                         else:
                             with torch.no_grad():
                                 loss_status = self.run_batch(batch, want_pred=False, **({'want_rank': True} if rank else {}),
-                                                             **({'want_func_acc': True} if facc else {}))
+                                                             **({'want_func_acc': True} if facc else {}),
+                                                             **({'want_recovery': True} if recov else {}))
                             if rank:
                                 records.append(loss_status['link_metrics'])
                             if facc:
                                 func_counts.append(loss_status['func_counts'])
+                            if recov:
+                                recovery_counts.append(loss_status['recovery_counts'])
                         # one small device->host copy per step (3 losses + 4 counters), read one step behind so that the host
                         # never waits for the step it has just enqueued
                         account(self.enqueue_metrics(loss_status))
@@ -351,6 +361,12 @@ class Trainer():
                     c = c[c[:, 0] > 0].double()
                     if c.shape[0] > 0:
                         rank_cols += ' |FuncAcc: {:.4f}'.format(float((c[:, 1] / c[:, 0]).mean()))
+                if recov and recovery_counts:
+                    # one host read for the whole phase: the mean of exact / gates over the circuits that have a gate
+                    c = torch.cat(recovery_counts).cpu()
+                    c = c[c[:, 0] > 0].double()
+                    if c.shape[0] > 0:
+                        rank_cols += ' |Recov: {:.4f}'.format(float((c[:, 1] / c[:, 0]).mean()))
                 if getattr(self.model, 'variational', False):
                     rank_cols = ' |KL: {:.4f}'.format(stats['kl'].avg) + rank_cols
                 if self.local_rank == 0:

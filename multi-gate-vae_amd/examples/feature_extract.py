@@ -18,6 +18,7 @@ state_dict keys), run `model(G) -> (hs, hf)` over a dataset and save the embeddi
     python examples/feature_extract.py --type aig --synthetic 4 --recon_curve 9        # + the decoder's confusion at 0.1, 0.2 .. 0.9
     python examples/feature_extract.py --type aig --synthetic 4 --link_ranking 1,10    # + exact MRR / Hits@1 / Hits@10 of the true fan-ins
     python examples/feature_extract.py --type aig --synthetic 4 --function_acc 0.05,0.1   # + exact functional ordering accuracy per circuit
+    python examples/feature_extract.py --type aig --synthetic 4 --decode_circuit dec.npz  # + a legal circuit decoded from every graph's hs
 """
 import argparse
 import os
@@ -104,6 +105,12 @@ def main(argv=None):
                     'that 1 - cos(hf) orders the way the truth-table distance does: name/func_acc [B] (-1 where no comparison is '
                     'eligible) and name/func_counts [B, 3] = eligible, concordant, tied (Model.function_accuracy; exact counts of what '
                     'get_function_acc samples)')
+    ap.add_argument('--decode_circuit', default='', metavar='OUT.npz', help='also decode every graph\'s embeddings into a legal circuit of the '
+                    'gate library — every gate its arity\'s best fan-ins among the gates of lower level, acyclic whatever the scores are '
+                    '(Model.decode_circuit) — and write it to OUT.npz: name/edge_index [2, E\'] (sources on row 0, ids local to the graph, by '
+                    'target, then by rank), name/fanin [n, K] (-1 past the end), name/score [n, K], name/short [n] (fewer candidates than '
+                    'the arity) and, where the graph has edges, name/recovery [5] = gates, exact, hits, true_total, decoded_total '
+                    '(Model.circuit_recovery); the mean exact-recovery rate is printed')
     ap.add_argument('--variational', action='store_true', help='the checkpoint is of a model trained with train.py --variational: build '
                     'the four heads fc_{s,t}_{mu,logstd} so that it loads in full; the link tools then decode the posterior means')
     a = ap.parse_args(argv)
@@ -125,6 +132,7 @@ def main(argv=None):
                                         a.type, random_shuffle=False, trainval_split=1.0).get_dataset()
         graphs = train + val
     out, t0, records, counts = {}, time.time(), [], []
+    dec_out, dec_rates = {}, []
     with torch.no_grad():
         for b0 in range(0, len(graphs), a.batch_size):
             chunk = graphs[b0:b0 + a.batch_size]
@@ -188,8 +196,22 @@ def main(argv=None):
                 cl_label, cl_ptr, cl_mem = (x.cpu().numpy() for x in model.equivalence_classes(hf, graph_ptr=batch.graph_ptr,
                                                                                                threshold=a.classes))
                 cptr = np.searchsorted(cl_mem[cl_ptr[:-1]], ptr).tolist()      # classes come by label and never cross graphs
+            if a.decode_circuit:
+                recov, dec = model.circuit_recovery(hs, batch)
+                d_ei, d_fanin, d_score, d_short = (x.cpu().numpy() for x in dec)
+                d_rec = recov.counts.cpu().numpy()
+                eptr_d = np.searchsorted(d_ei[1], ptr).tolist()                                # listed by target: the graphs' places
             for k, g in enumerate(chunk):
                 name = g.get('name') or 'graph%d' % (b0 + k)
+                if a.decode_circuit:
+                    loc = d_fanin[ptr[k]:ptr[k + 1]]
+                    dec_out[name + '/edge_index'] = (d_ei[:, eptr_d[k]:eptr_d[k + 1]] - ptr[k]).astype(np.int32)
+                    dec_out[name + '/fanin'] = np.where(loc >= 0, loc - ptr[k], -1).astype(np.int32)
+                    dec_out[name + '/score'] = d_score[ptr[k]:ptr[k + 1]]
+                    dec_out[name + '/short'] = d_short[ptr[k]:ptr[k + 1]]
+                    if d_rec[k, 0] > 0:
+                        dec_out[name + '/recovery'] = d_rec[k]
+                        dec_rates.append(d_rec[k, 1] / d_rec[k, 0])
                 if rank_ks:
                     n = max(int(rm[0][k]), 1)
                     hits = ' '.join('Hits@%d %.4f..%.4f' % (K, int(rm[2][k, j]) / n, int(rm[1][k, j]) / n) for j, K in enumerate(rank_ks))
@@ -255,6 +277,10 @@ def main(argv=None):
     torch.cuda.synchronize()
     np.savez(a.out, **out)
     print('[INFO] %d graphs embedded in %.2f s -> %s' % (len(graphs), time.time() - t0, a.out))
+    if a.decode_circuit:
+        np.savez(a.decode_circuit, **dec_out)
+        print('[INFO] decoded circuits of %d graphs -> %s; exact gate recovery over the %d graphs with edges: %s'
+              % (len(graphs), a.decode_circuit, len(dec_rates), '%.4f' % (sum(dec_rates) / len(dec_rates)) if dec_rates else 'n/a'))
     if a.link_metrics:
         pairs = deepgate.metrics.read_link_records(records)      # one host read for all batches
         print('[INFO] link prediction over %d batches: AUC %.4f, AP %.4f' % (len(pairs), sum(x for x, _ in pairs) / len(pairs),
